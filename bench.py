@@ -10,12 +10,17 @@ A step = one pass of the hot path over one object (default --config c2: N=4096 p
 (per-point layer-0 projection, fused PPF+MLP+decode of the two centre heads -- the 64 logits nocs/inference.py:185-188 consumes up
 to the arg-max -- LDS-tiled vote, reduce+arg-max) replayed from a hipGraph.  Steps ROTATE over 9 distinct objects (~70 MB each: more
 than the Infinity Cache holds).  With N GPUs every rank steps through its own objects (weak scaling) and ONE all_gather of the
-result records closes the batch inside the timed region; rank 0 then checks EVERY rank's arg-max against the oracle.
+result records closes the batch inside the timed region; with --full rank 0 then checks EVERY rank's arg-max against the oracle.
 
   --config c1        BASELINE.json configs[0] (N=1024 K=64, the CPU path): the oracle chain swept over thread counts
   --config c3 | c5   the same chain at configs[2] (N=4096 K=256) / configs[4] (N=8192 K=256, res 2e-3) sizes
   --config c4        configs[3]: 64 mixed-category objects (C2 size), object j on rank j mod N, FULL pose per object through
                      BatchPoseRunner on device-resident objects, one gather of the finished records; strong scaling
+
+A plain run sets up, warms up, times ONE region of exactly --steps steps, writes the last step's outputs (--dump-outputs DIR) and
+prints the line.  --full adds everything else: the timed region repeated (median of at least 5, --min-seconds), the one-instance
+latencies, the rooflines, the secondary figures (--no-secondary drops them), the CPU baseline and the oracle checks of the
+arg-maxes (--no-cpu-baseline drops them).
 
 This file: the contract line and the timed regions.  bench_secondary.py: the rooflines' kernel timings and every secondary figure;
 bench_cpu.py: cpu_baseline and the oracle checks (a worker process); bench_util.py: pipeline sets, the stepper, emit / compact."""
@@ -34,7 +39,7 @@ sys.path.insert(0, ROOT)
 import bench_cpu                                       # noqa: E402
 import cppf_amd.synthetic as syn                       # noqa: E402
 from bench_dist import bind_rank_cpus, binding_dict, dist_info, self_launch      # noqa: E402
-from bench_util import (CONFIGS, METRIC, TRAINED_WEIGHTS, compact, emit, events_per_chain, make_center_set,      # noqa: E402,F401
+from bench_util import (CONFIGS, METRIC, TRAINED_WEIGHTS, compact, dump_outputs, emit, events_per_chain, make_center_set,  # noqa: E402,F401
                         make_stepper, mlp_batch, settle, vote_width, workload_text)
 from cppf_amd import sharding                          # noqa: E402
 from cppf_amd._torch_util import lane_streams          # noqa: E402
@@ -43,11 +48,14 @@ from cppf_amd.models.model import PPFEncoder           # noqa: E402
 
 
 def timed_regions(region, args, group, dev):
-    """The timed region repeated: at least 5 times and until --min-seconds of regions have run (one region of 20 steps is ~2 ms).
+    """The timed region, --regions times (a plain run: once by default, i.e. exactly --steps timed steps); with --full at least 5
+    times and, with --regions 0, until --min-seconds of regions have run (one region of 20 steps is ~2 ms).
     Every region's time is the MAX over the ranks; the sorted list is returned and the caller reports its MEDIAN.  All ranks run
     the same number of regions: the decision to stop is taken on rank-reduced times."""
     times, total, rec = [], 0.0, None
-    while len(times) < max(5, args.regions) or (args.regions == 0 and total < args.min_seconds and len(times) < 100000):
+    least = max(5, args.regions) if args.full else max(1, args.regions)
+    until = args.full and args.regions == 0
+    while len(times) < least or (until and total < args.min_seconds and len(times) < 100000):
         t, rec = region()
         if group:
             tmax = torch.tensor([t], dtype=torch.float64, device=sharding.collective_device(dev))
@@ -94,6 +102,13 @@ def run_center_config(name, enc, sd, dev, rank, world, args):
     calib = run_steps.calibrate()           # (--vote-batch-workgroups -1: the chains' vote width, timed on this workload)
     close_batch()                           # warm-up of the gather too (RCCL communicators are created on first use)
     settle()
+    # right before the timed region (the collection above leaves the device idle): the --warmup steps in whole chains, then twice the
+    # steps of `steps` past its last whole rotation -- which captures and replays the shorter chain of the remainder steps mod B the
+    # timed region ends with (the same objects in the same order: the stepper's chain key), so that no capture falls inside the region
+    run_steps(-(-args.warmup // run_steps.batch) * run_steps.batch)
+    for _ in range(2):
+        run_steps(steps % n_obj)
+    torch.cuda.synchronize()
     ev0, ev1, own_ms = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True), []
 
     def region():
@@ -116,10 +131,23 @@ def run_center_config(name, enc, sd, dev, rank, world, args):
 
     regions, allrec = timed_regions(region, args, group, dev)
     elapsed = regions[len(regions) // 2]
-    lat = events_per_chain(dev, pipes, max(20, steps))
+    outputs = center_outputs(pipes[(steps - 1) % n_obj], allrec, (steps - 1) * world) if args.dump_outputs and rank == 0 else None
+    lat = events_per_chain(dev, pipes, max(20, steps)) if args.full else None
     return dict(objs=objs, pipes=pipes, P=P, n_points=n_points, k=k, n_obj=n_obj, n_streams=n_streams, elapsed=elapsed,
                 mlp_batch=run_steps.batch, vote_batch_workgroups=run_steps.vote_batch_workgroups, vote_batch_calibration=calib,
-                regions=regions, allrec=allrec, lat=lat, what=c["what"], own_ms=sorted(own_ms))
+                regions=regions, allrec=allrec, lat=lat, what=c["what"], own_ms=sorted(own_ms), outputs=outputs)
+
+
+def center_outputs(pipe, allrec, last):
+    """What the timed path computed, read right after the timed regions (before anything else runs the pipelines): rank 0's last
+    step's arg-max and peak (row `last` of the gathered records), the (mu, nu) its pair kernel wrote and its vote grid (`pipe` = the
+    object of that step: step i runs object i mod n_obj), and the arg-max / peak of every step of the last region of every rank (rows
+    of the gathered records: rank + step x world)"""
+    torch.cuda.synchronize()
+    rec = allrec.cpu().numpy()
+    return {"argmax": rec[last:last + 1, 12].astype(np.float64), "peak": rec[last:last + 1, 13].astype(np.float32),
+            "outputs": pipe.outputs.cpu().numpy(), "grid": pipe.grid.cpu().numpy(),
+            "step_argmax": rec[:, 12].astype(np.float64), "step_peak": rec[:, 13].astype(np.float32)}
 
 
 def step_argmaxes(m, steps, rank=0, world=1):
@@ -222,7 +250,9 @@ def run_c1(args):
                                   "arg-max on the HOST cores (BASELINE.json configs[0]: the CPU path, no GPU); a step = one pass over "
                                   "the object at the best thread count", "pairs_per_step": P, "parallelism": "host threads"},
            "cpu_baseline": cb, "argmax_cpu": int(flat)}
-    if torch.cuda.is_available():       # the same workload on the GPU, for the ratio
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"argmax": np.array([flat], dtype=np.float64)})
+    if args.full and torch.cuda.is_available():       # the same workload on the GPU, for the ratio
         dev = torch.device("cuda", 0)
         torch.cuda.set_device(dev)
         args.regions, args.min_seconds = 0, 1.0
@@ -269,7 +299,10 @@ def main_c4(args, dev, rank, world, binding):
            "objects_per_s": m["reps"] * m["n_objects"] / m["elapsed"],
            "regions": len(m["regions"]), "region_ms_min_max": [m["regions"][0] * 1e3, m["regions"][-1] * 1e3],
            "dist": dinfo, "cpu_binding": binding_dict(binding)}
-    if not args.no_cpu_baseline:      # >= 1 object of every rank against the oracle's full pose (the worker reproduces the device's draws)
+    if args.dump_outputs:             # the last batch's records: what BatchPoseRunner.run returns to its caller
+        dump_outputs(args.dump_outputs, {"records": m["recs"].astype(np.float64)})
+    if args.full and not args.no_cpu_baseline:      # >= 1 object of every rank against the oracle's full pose (the worker reproduces
+        #                                             the device's draws)
         sample = sorted({r + world * s for r in range(world) for s in range(max(1, args.c4_check // world))
                          if r + world * s < m["n_objects"]})
         out.update(bench_cpu.check_c4_records(m, sample, seed=0))
@@ -283,12 +316,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", choices=["c1", "c2", "c3", "c4", "c5"], default="c2",
                     help="BASELINE.json configuration (default c2 = the headline; see the module docstring)")
-    ap.add_argument("--regions", type=int, default=0, help="timed regions of --steps steps each (the median is reported); 0 = at "
-                    "least 5 and until --min-seconds of regions have run")
-    ap.add_argument("--min-seconds", type=float, default=6.0, help="with --regions 0: keep repeating the timed region until this "
-                    "much region time has accumulated")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU worker: no cpu_baseline, no oracle check of the arg-maxes")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary stage timings")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the timed region repeated (--regions 0), the "
+                    "one-instance latencies, the rooflines, the secondary figures and the CPU baseline with the oracle checks")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the timed path computed "
+                    "in its last step as DIR/<name>.npy (float32 / float64, at most 64 MB; inputs are seeded)")
+    ap.add_argument("--regions", type=int, default=None, help="timed regions of --steps steps each (the median is reported); "
+                    "default 1, with --full 0 = at least 5 and until --min-seconds of regions have run")
+    ap.add_argument("--min-seconds", type=float, default=6.0, help="with --full and --regions 0: keep repeating the timed region "
+                    "until this much region time has accumulated")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU worker (no cpu_baseline, no oracle "
+                    "check of the arg-maxes)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary stage timings")
     ap.add_argument("--vote-workgroups", type=int, default=-1, help="width of the vote launches of the timed pipelines: 0 = one "
                     "workgroup per CU, 64..256 = at most that many (cppf.h CPPF_VOTE_WORKGROUPS); -1 = chosen from the pairs per "
                     "tile when more than one instance is in flight (--streams > 1), one per CU otherwise")
@@ -319,6 +357,8 @@ def main():
                     help="where rank 0 writes the full record ('' = nowhere)")
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.regions is None:
+        args.regions = 0 if args.full else 1
 
     if args.cpu_worker is not None:
         return bench_cpu.cpu_worker(args.cpu_worker)
@@ -347,13 +387,18 @@ def main():
     enc = enc.to(dev)
     m = run_center_config(args.config, enc, sd, dev, rank, world, args)
     P, steps, elapsed = m["P"], args.steps, m["elapsed"]
-    secondary = rank == 0 and world == 1 and not args.no_secondary
-    import bench_secondary
-    ctx = types.SimpleNamespace(args=args, enc=enc, sd=sd, dev=dev, rank=rank, world=world, m=m, secondary=secondary,
-                                run_center_config=run_center_config, run_c4=run_c4, workload_text=workload_text,
-                                step_argmaxes=step_argmaxes, c4_prediction=c4_prediction)
-    roof = bench_secondary.rooflines(ctx)            # every run: the dominant kernels between HIP events -> `roofline`, `roofline_vote`
-    extra, pending_checks = bench_secondary.collect(ctx, roof) if secondary else ({}, {})
+    if m["outputs"] is not None:
+        dump_outputs(args.dump_outputs, m["outputs"])
+    secondary = args.full and rank == 0 and world == 1 and not args.no_secondary
+    roof, extra, pending_checks = {"line": {}}, {}, {}
+    if args.full:
+        import bench_secondary
+        ctx = types.SimpleNamespace(args=args, enc=enc, sd=sd, dev=dev, rank=rank, world=world, m=m, secondary=secondary,
+                                    run_center_config=run_center_config, run_c4=run_c4, workload_text=workload_text,
+                                    step_argmaxes=step_argmaxes, c4_prediction=c4_prediction)
+        roof = bench_secondary.rooflines(ctx)        # the dominant kernels between HIP events -> `roofline`, `roofline_vote`
+        if secondary:
+            extra, pending_checks = bench_secondary.collect(ctx, roof)
     dinfo = dist_info(world, dev, m["own_ms"], binding)
     if torch.distributed.is_initialized():
         torch.distributed.barrier()                  # every rank is done with the device before rank 0 starts the CPU legs
@@ -372,16 +417,16 @@ def main():
             # value / ms_per_step come from the MEDIAN region (max over ranks per region)
             "regions": len(m["regions"]), "region_ms_min_max": [m["regions"][0] * 1e3, m["regions"][-1] * 1e3],
             "dist": dinfo, "cpu_binding": binding_dict(binding),      # (this process's CPUs: the ones next to its GPU, bench_dist.py)
-            # hipEvents around the whole chain on one object, one at a time, objects rotating
-            "median_ms_one_instance": lat[len(lat) // 2], "one_instance_ms_min_max": [lat[0], lat[-1]], "one_instance_runs": len(lat),
             "vote_workgroups": m["objs"][0]["pipe"].vote_workgroups,      # width of the single chains' vote launches (0 = one per CU)
             "mlp_batch": m["mlp_batch"],                                  # objects per launch of the pair kernel in the timed regions
             "vote_batch": bool(m["mlp_batch"] > 1 and not args.no_vote_batch),
             "vote_batch_workgroups": m["vote_batch_workgroups"], "vote_batch_calibration_ms_per_step": m["vote_batch_calibration"],
         }
+        if lat:         # (--full) SURVEY.md 8(d): hipEvents around the whole chain on one object, one at a time, objects rotating
+            out.update(median_ms_one_instance=lat[len(lat) // 2], one_instance_ms_min_max=[lat[0], lat[-1]], one_instance_runs=len(lat))
         out.update(roof["line"])
         out.update(extra)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             bench_cpu.attach_checks(out, m, args, rank, world, pending_checks, step_argmaxes)
         emit(out, args)
     if torch.distributed.is_initialized():

@@ -366,6 +366,31 @@ def emit(line, args=None):
 
 
 
+DUMP_ROWS = 1 << 20      # rows of one array --dump-outputs writes whole; beyond that a fixed sample (the 6 arrays of the centre
+                         # chain: <= 56 MB in all, sampled row numbers included)
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 / float64, so that two builds can be compared output for output.
+    An array of more than DUMP_ROWS rows (first axis; a grid: its cells) is replaced by DUMP_ROWS of them drawn without replacement
+    by a generator seeded with 0 and kept in order, and their row numbers go to DIR/<name>_rows.npy (float64)."""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if a.shape[0] > DUMP_ROWS or (a.ndim > 2 and a.size > DUMP_ROWS):
+            if a.ndim > 2:
+                a = a.reshape(-1)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_ROWS, replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
+            total += rows.size * 8
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+        total += a.nbytes
+    assert total <= 64 << 20, total
+
+
 def compact(out):
     """The line rank 0 prints (< 4 KB): the contract's fields, the two rooflines, the CPU baseline's summary and the secondaries a
     reader needs first.  The full record (every stage, sweep and note: ~15 KB) goes to bench_full.json -- a harness that keeps

@@ -1,16 +1,16 @@
 #!/bin/bash
-# Collect the round's rocprofv3 evidence on the GPU box (run through gpurun from the repo root):
-#   1. --kernel-trace --stats of the default benchmark command  -> gpurun_out/prof/kernel_trace_stats.txt
-#      (and with --streams 1: each launch alone on the chip      -> gpurun_out/prof/kernel_trace_stats_one_stream.txt)
-#   2. PMC passes, one counter group per pass, no trace domains -> gpurun_out/prof/pmc_counters.txt
-#   3. the HBM-traffic summary bench.py reads                   -> gpurun_out/prof/pmc_traffic.json  (kernels at full width)
-#      and the same for the default command's narrower vote     -> gpurun_out/prof/pmc_traffic_timed_width.json
+# Collect the round's rocprofv3 evidence on an MI355X (run from the repo root; $OUT = $PROFILE_OUT/prof, default profile_out/prof):
+#   1. --kernel-trace --stats of the benchmark command with --full  -> $OUT/kernel_trace_stats.txt
+#      (and with --streams 1: each launch alone on the chip      -> $OUT/kernel_trace_stats_one_stream.txt)
+#   2. PMC passes, one counter group per pass, no trace domains -> $OUT/pmc_counters.txt
+#   3. the HBM-traffic summary bench.py reads                   -> $OUT/pmc_traffic.json  (kernels at full width)
+#      and the same for the default command's narrower vote     -> $OUT/pmc_traffic_timed_width.json
 # Copy the three files into profiles/ (renamed r<round>_*) to have them judged.
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-OUT=$R/gpurun_out/prof
+OUT=${PROFILE_OUT:-$R/profile_out}/prof
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --min-seconds 0.3"
+BENCH="python $R/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --min-seconds 0.3"
 timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/kt -- $BENCH > $OUT/bench_under_trace.log 2>&1
 python $R/profiles/kstats.py $(find /tmp/kt -name '*.db' | head -1) > $OUT/kernel_trace_stats.txt 2>&1
 # the same chain with ONE object in flight: every launch alone on the chip, so a kernel's average here is its own duration (in the
@@ -29,7 +29,7 @@ for set in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum" "TCC_EA0_RDREQ_s
   i=$((i+1))
   # (--vote-workgroups 0: every kernel at its full width, one workgroup per CU -- the launches bench.py's stage timings and
   #  rooflines are about; the timed regions' narrower vote is counted separately below)
-  timeout 600 rocprofv3 --pmc $set --output-format csv -d /tmp/pmc$i -- python $R/bench.py --steps 12 --mlp-batch 4 --warmup 2 --no-cpu-baseline --no-secondary --regions 5 --vote-workgroups 0 > /tmp/pmc$i.log 2>&1
+  timeout 600 rocprofv3 --pmc $set --output-format csv -d /tmp/pmc$i -- python $R/bench.py --full --steps 12 --mlp-batch 4 --warmup 2 --no-cpu-baseline --no-secondary --regions 5 --vote-workgroups 0 > /tmp/pmc$i.log 2>&1
   f=$(find /tmp/pmc$i -name '*counter_collection.csv' | head -1)
   python $R/profiles/pmcstats.py $f >> $OUT/pmc_counters.txt
 done
@@ -38,7 +38,7 @@ python $R/profiles/make_traffic_json.py $OUT/pmc_counters.txt > $OUT/pmc_traffic
 : > $OUT/pmc_counters_timed_width.txt
 for set in "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc $set --output-format csv -d /tmp/pmc$i -- python $R/bench.py --steps 12 --mlp-batch 4 --warmup 2 --no-cpu-baseline --no-secondary --regions 5 --vote-batch-workgroups 64 > /tmp/pmc$i.log 2>&1
+  timeout 600 rocprofv3 --pmc $set --output-format csv -d /tmp/pmc$i -- python $R/bench.py --full --steps 12 --mlp-batch 4 --warmup 2 --no-cpu-baseline --no-secondary --regions 5 --vote-batch-workgroups 64 > /tmp/pmc$i.log 2>&1
   f=$(find /tmp/pmc$i -name '*counter_collection.csv' | head -1)
   python $R/profiles/pmcstats.py $f >> $OUT/pmc_counters_timed_width.txt
 done

@@ -178,7 +178,7 @@ def test_eight_rank_line_checks_every_rank_against_the_oracle(extra, n_checked):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT") and not k.startswith("CPPF_")}
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--warmup", "1", "--no-secondary"] + extra,
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--warmup", "1", "--full", "--no-secondary"] + extra,
                        env=env, capture_output=True, text=True, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     out_lines = [ln for ln in p.stdout.splitlines() if ln.strip()]

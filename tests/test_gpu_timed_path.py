@@ -128,3 +128,32 @@ def test_center_batch_pipeline_of_four_c2_objects(oracle, dev, vote_batch, vote_
         check_argmax(oracle, int(oi.item()), ref, o["ob"], o["idx"], o["cfg"].res)
         assert int(oi.item()) == int(np.argmax(g64))            # and the exact sum's, always
         np.testing.assert_allclose(float(ov.item()), opeak, rtol=2e-5)
+
+
+def test_plain_bench_run_times_exactly_its_steps_and_dumps_its_last_step(tmp_path):
+    """`bench.py --steps K` without --full: ONE timed region of exactly K steps, no secondary legs; --dump-outputs writes the last
+    step's arg-max, peak, (mu, nu) and vote grid and every step's arg-max / peak, and two runs with the same arguments write the
+    same arrays (seeded inputs).  K = 7 with chains of 2: the last step runs as a single chain."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "1",
+                            "--objects", "3", "--full-record", "", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-3000:]
+        d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+        assert d["steps"] == 7 and d["regions"] == 1 and d["mlp_batch"] == 2 and d["value"] > 0
+        assert d["region_ms_min_max"][0] == pytest.approx(d["ms_per_step"] * 7, rel=1e-5)      # (the line rounds to 6 digits)
+        assert d.get("cpu_baseline") is None and d.get("roofline") is None and "median_ms_one_instance" not in d
+        dumps.append({f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))})
+    a = dumps[0]
+    assert sorted(a) == ["argmax", "grid", "outputs", "peak", "step_argmax", "step_peak"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert a["outputs"].shape == (P, 2) and a["step_argmax"].shape == (7,) and a["step_peak"].shape == (7,)
+    assert a["step_argmax"][-1] == a["argmax"][0] and a["step_peak"][-1] == a["peak"][0]
+    assert a["grid"].reshape(-1)[int(a["argmax"][0])] == a["peak"][0] == a["grid"].max()
+    assert sorted(dumps[1]) == sorted(a) and all(np.array_equal(a[k], dumps[1][k]) for k in a)
