@@ -953,7 +953,9 @@ __global__ __launch_bounds__(RED_THREADS) void axis_sign_kernel(const float* __r
     }
 }
 
-// nocs/inference.py:335 (sums; the caller finishes exp(mean)*scale_mean*2)
+// nocs/inference.py:335 (sums; the caller finishes exp(mean)*scale_mean*2).  EXP: sums of expf(logit) instead, for the mean of
+// exp of nocs/zero_shot.ipynb cell 11 (np.mean(np.exp(preds_scale) * scale_mean * 2, 0))
+template <bool EXP>
 __global__ __launch_bounds__(RED_THREADS) void scale_sum_kernel(const float* __restrict__ scale_logits, int stride,
                                                                 const int32_t* __restrict__ sel,
                                                                 const int32_t* __restrict__ n_sel_dev, int64_t n_sel_host,
@@ -965,7 +967,8 @@ __global__ __launch_bounds__(RED_THREADS) void scale_sum_kernel(const float* __r
     for (int64_t k = (int64_t)blockIdx.x * RED_THREADS + threadIdx.x; k < n_sel; k += (int64_t)RED_BLOCKS * RED_THREADS) {
         const int64_t p = sel ? sel[k] : k;
         const float* s = scale_logits + p * stride;
-        s0 += (double)s[0]; s1 += (double)s[1]; s2 += (double)s[2];
+        if (EXP) { s0 += (double)expf(s[0]); s1 += (double)expf(s[1]); s2 += (double)expf(s[2]); }
+        else { s0 += (double)s[0]; s1 += (double)s[1]; s2 += (double)s[2]; }
     }
     const double a = block_sum(s0, sh), b = block_sum(s1, sh), c = block_sum(s2, sh);
     if (threadIdx.x == 0) {
@@ -1002,18 +1005,31 @@ extern "C" int cppf_axis_sign(const float* pc, const float* nrm, const int32_t* 
     return 0;
 }
 
-extern "C" int cppf_scale_sum(const float* scale_logits, int stride, const int32_t* sel, const int32_t* n_sel_dev,
-                              int64_t n_sel_host, double* out, void* workspace, size_t workspace_bytes, void* stream)
+template <bool EXP>
+static int scale_sum_impl(const float* scale_logits, int stride, const int32_t* sel, const int32_t* n_sel_dev,
+                          int64_t n_sel_host, double* out, void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!scale_logits || !out || stride < 3 || n_sel_host < 0) return CPPF_EINVAL;
     if (!workspace || workspace_bytes < cppf_reduce_workspace_bytes()) return CPPF_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     double* partial = static_cast<double*>(workspace);
-    hipLaunchKernelGGL(scale_sum_kernel, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, scale_logits, stride, sel,
+    hipLaunchKernelGGL(scale_sum_kernel<EXP>, dim3(RED_BLOCKS), dim3(RED_THREADS), 0, st, scale_logits, stride, sel,
                        n_sel_dev, n_sel_host, partial);
     hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(64), 0, st, partial, 3, n_sel_dev, n_sel_host, out);
     CPPF_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int cppf_scale_sum(const float* scale_logits, int stride, const int32_t* sel, const int32_t* n_sel_dev,
+                              int64_t n_sel_host, double* out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return scale_sum_impl<false>(scale_logits, stride, sel, n_sel_dev, n_sel_host, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int cppf_scale_exp_sum(const float* scale_logits, int stride, const int32_t* sel, const int32_t* n_sel_dev,
+                                  int64_t n_sel_host, double* out, void* workspace, size_t workspace_bytes, void* stream)
+{
+    return scale_sum_impl<true>(scale_logits, stride, sel, n_sel_dev, n_sel_host, out, workspace, workspace_bytes, stream);
 }
 
 // One launch for what follows the orientation vote (nocs/inference.py:283-301,335): np.argmax of every direction's bin

@@ -1,0 +1,348 @@
+"""Zero-shot instance segmentation and pose estimation (the reference README's "Zero-Shot Instance Segmentation and Pose
+Estimation", nocs/zero_shot.ipynb): one depth frame with NO instance masks in, every object's pose and point mask out.
+
+  cell 3   whole-frame cloud, two-level de-duplication, SPRIN features   zero_shot_frame (frames.instance_cloud, sparse_quantize)
+  cell 5   5 M uniform pairs over the sparse cloud                       frames.draw_pairs (cppf_sample_pairs)
+  cell 6   drop "indistinguishable" pairs                                distinct_pairs (cppf_pair_filter_distinct + compaction)
+  cell 7-8 9-wide regression head, scene vote                            PPFEncoder.forward_with_idx, cppf_vote_argmax
+  cell 9   Gaussian smoothing + iterative peak proposals                 smooth_grid / scene_proposals (cppf_scene_proposals)
+  cell 11  back-vote, segmentation, orientation, axis sign, scale        segment_instance / zero_shot_poses
+
+The notebook does cells 9 and 11 in scipy / numpy on the host after copying the grid off the device; here everything runs on the
+device and the host reads back the proposal count (to size the per-proposal work) and one small record per proposal.  The
+semantics where the notebook has none (thin grids, a peak on a last plane, a first diff equal to the threshold) are documented at
+cppf_scene_proposals in include/cppf.h.  The notebook's "fine-grained centre vote" of cell 11 is computed and discarded there (T
+stays the proposal); it is not run here."""
+import numpy as np
+import torch
+
+from . import _lib
+from ._torch_util import require_cuda, stream_ptr, workspace
+from .models import voting
+from .utils.util import fibonacci_sphere, num_sphere_bins
+
+F32, I32, U8 = torch.float32, torch.int32, torch.uint8
+MAX_RADIUS, MAX_MARGIN = 32, 64          # csrc/scene.hip: SCN_MAX_RADIUS, SCN_MAX_MARGIN
+
+
+def gaussian_weights(sigma=1.0, truncate=4.0):
+    """The 1-D kernel of scipy.ndimage.gaussian_filter (order 0): fp64 [2r+1], r = int(truncate * sigma + 0.5)"""
+    sigma, truncate = float(sigma), float(truncate)
+    if not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError(f"sigma must be a positive number, got {sigma}")
+    if not (np.isfinite(truncate) and truncate >= 0):
+        raise ValueError(f"truncate must be >= 0, got {truncate}")
+    r = int(truncate * sigma + 0.5)
+    if r > MAX_RADIUS:
+        raise ValueError(f"the filter radius int(truncate * sigma + 0.5) = {r} exceeds {MAX_RADIUS}")
+    x = np.arange(-r, r + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    return np.ascontiguousarray(phi / phi.sum())
+
+
+def _grid_tensor(grid):
+    """numpy or torch f32[gx,gy,gz] -> (contiguous device tensor, whether numpy came in)"""
+    require_cuda()
+    was_np = isinstance(grid, np.ndarray)
+    t = torch.from_numpy(np.ascontiguousarray(grid, dtype=np.float32)) if was_np else grid
+    if not isinstance(t, torch.Tensor) or t.dim() != 3:
+        raise ValueError(f"grid must be a 3-D array, got {getattr(t, 'shape', type(t).__name__)}")
+    if t.dtype != F32:
+        raise TypeError(f"grid must be float32, got {t.dtype}")
+    if not t.is_cuda:
+        t = t.cuda()
+    return t.contiguous(), was_np
+
+
+def smooth_grid(grid, sigma=1.0, truncate=4.0):
+    """scipy.ndimage.gaussian_filter(grid, sigma) (cell 9), bit for bit, on the device.  numpy in -> numpy out."""
+    g, was_np = _grid_tensor(grid)
+    w = gaussian_weights(sigma, truncate)
+    gx, gy, gz = g.shape
+    out = torch.empty_like(g)
+    L = _lib.lib()
+    ws = workspace(L.cppf_gaussian_filter3d_workspace_bytes(gx, gy, gz), g.device, "gauss")
+    with torch.cuda.device(g.device):
+        _lib.check(L.cppf_gaussian_filter3d(g.data_ptr(), out.data_ptr(), gx, gy, gz, w.ctypes.data, (w.shape[0] - 1) // 2,
+                                            ws.data_ptr(), ws.numel(), stream_ptr(g.device)), "cppf_gaussian_filter3d")
+    return out.cpu().numpy() if was_np else out
+
+
+def _check_loop_args(thresh, margin, max_proposals, max_iters):
+    if not 1 <= int(margin) <= MAX_MARGIN:
+        raise ValueError(f"margin must be in 1..{MAX_MARGIN}, got {margin}")
+    if int(max_proposals) < 0:
+        raise ValueError(f"max_proposals must be >= 0, got {max_proposals}")
+    max_iters = 4 * int(max_proposals) if max_iters is None else int(max_iters)
+    if max_iters < 0:
+        raise ValueError(f"max_iters must be >= 0, got {max_iters}")
+    if not np.isfinite(float(thresh)):
+        raise ValueError(f"thresh must be finite, got {thresh}")
+    return max_iters
+
+
+def proposals_workspace(dims, device):
+    """device scratch for scene_proposals_device on a grid of `dims` (allocate it before a graph capture)"""
+    return torch.empty(max(int(_lib.lib().cppf_scene_proposals_workspace_bytes(*[int(d) for d in dims])), 256), dtype=U8,
+                       device=device)
+
+
+def scene_proposals_device(grid, sigma=1.0, thresh=50, margin=10, max_proposals=32, max_iters=None, truncate=4.0,
+                           smoothed_out=None, out=None, ws=None):
+    """Cell 9 on a device grid with no host round trip (graph-capturable): the raw scene vote in, the device tensors
+    (loc i32[K,3], value f32[K], diff f32[K], count i32[1]) out, K = max_proposals; rows >= count are unspecified.
+    smoothed_out: optional device f32 grid that receives the smoothed grid (before any suppression); out: a previous result
+    tuple to write into; ws: proposals_workspace(dims) (a fresh one otherwise)."""
+    g, _ = _grid_tensor(grid)
+    max_iters = _check_loop_args(thresh, margin, max_proposals, max_iters)
+    w = gaussian_weights(sigma, truncate)
+    dev, (gx, gy, gz) = g.device, g.shape
+    K = int(max_proposals)
+    if out is None:
+        out = (torch.empty((max(K, 1), 3), dtype=I32, device=dev), torch.empty(max(K, 1), dtype=F32, device=dev),
+               torch.empty(max(K, 1), dtype=F32, device=dev), torch.empty(1, dtype=I32, device=dev))
+    loc, val, diff, count = out
+    if smoothed_out is not None and (tuple(smoothed_out.shape) != tuple(g.shape) or smoothed_out.dtype != F32
+                                     or not smoothed_out.is_contiguous()):
+        raise ValueError("smoothed_out must be a contiguous float32 tensor shaped like the grid")
+    if ws is None:
+        ws = proposals_workspace(g.shape, dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        _lib.check(L.cppf_scene_proposals(g.data_ptr(), gx, gy, gz, w.ctypes.data, (w.shape[0] - 1) // 2,
+                                          float(np.float32(thresh)), int(margin), K, max_iters, loc.data_ptr(), val.data_ptr(),
+                                          diff.data_ptr(), count.data_ptr(),
+                                          None if smoothed_out is None else smoothed_out.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          stream_ptr(dev)), "cppf_scene_proposals")
+    return loc, val, diff, count
+
+
+def scene_proposals(grid, corner, res, sigma=1, thresh=50, margin=10, max_proposals=32, max_iters=None, truncate=4.0):
+    """The notebook's `scene_locs` (cell 9): a list of (world f64[3], cnt = smoothed peak f32, diff f32), world =
+    corners[0] + loc * res in fp64 from the float32 corner."""
+    loc, val, diff, count = scene_proposals_device(grid, sigma, thresh, margin, max_proposals, max_iters, truncate)
+    n = int(count.item())
+    loc, val, diff = loc[:n].cpu().numpy(), val[:n].cpu().numpy(), diff[:n].cpu().numpy()
+    c = np.asarray(corner, np.float32).astype(np.float64)
+    return [(c + loc[k].astype(np.int64) * float(res), val[k], diff[k]) for k in range(n)]
+
+
+def _pairs_tensor(idx, dev):
+    t = torch.as_tensor(idx)
+    if t.dim() != 2 or t.shape[1] != 2:
+        raise ValueError(f"pair list must be [P,2], got {tuple(t.shape)}")
+    if t.dtype not in (torch.int32, torch.int64):
+        t = t.long()
+    return t.to(dev).contiguous()
+
+
+def _compact(mask, dev):
+    """positions of the non-zero bytes of a device u8 mask, in order (cppf_compact_mask) -> (i32[n] device, n)"""
+    L = _lib.lib()
+    P = mask.numel()
+    surv = torch.empty(max(P, 1), dtype=I32, device=dev)
+    count = torch.zeros(1, dtype=I32, device=dev)
+    if P:
+        cws = workspace(L.cppf_compact_workspace_bytes(P), dev, "compact")
+        _lib.check(L.cppf_compact_mask(mask.data_ptr(), P, surv.data_ptr(), count.data_ptr(), cws.data_ptr(), cws.numel(),
+                                       stream_ptr(dev)), "cppf_compact_mask")
+    n = int(count.item())
+    return surv[:n], n
+
+
+def distinct_pairs(pc, nrm, idx):
+    """Cell 6: the pairs of `idx` that are not "indistinguishable", in their order (same dtype as idx, on pc's device)."""
+    require_cuda()
+    dev = pc.device
+    pc, nrm = pc.float().contiguous(), nrm.float().contiguous()
+    idx = _pairs_tensor(idx, dev)
+    P = idx.shape[0]
+    keep = torch.empty(max(P, 1), dtype=U8, device=dev)
+    L = _lib.lib()
+    with torch.cuda.device(dev):
+        if P:
+            _lib.check(L.cppf_pair_filter_distinct(pc.data_ptr(), nrm.data_ptr(), idx.data_ptr(), 1 if idx.dtype == torch.int64 else 0,
+                                                   pc.shape[0], P, keep.data_ptr(), stream_ptr(dev)), "cppf_pair_filter_distinct")
+        pos, _ = _compact(keep[:P], dev)
+    return idx[pos.long()]
+
+
+def _segment_enqueue(pc, outputs, idx32, T32, corner, res, dims, num_rots, tol, min_contrib):
+    """back-vote at T32 + segmentation, all enqueued: (point_mask u8[N], positions i32[P], count i32[1]) device tensors"""
+    dev = pc.device
+    L = _lib.lib()
+    st = stream_ptr(dev)
+    N, P = pc.shape[0], idx32.shape[0]
+    surv = torch.empty(max(P, 1), dtype=U8, device=dev)
+    point_mask = torch.empty(N, dtype=U8, device=dev)
+    pairs = torch.empty(max(P, 1), dtype=I32, device=dev)
+    count = torch.zeros(1, dtype=I32, device=dev)
+    gx, gy, gz = (int(d) for d in dims)
+    if P:
+        _lib.check(L.cppf_backvote_ws(pc.data_ptr(), outputs.data_ptr(), None, idx32.data_ptr(), corner.data_ptr(), float(res), P,
+                                      int(num_rots), gx, gy, gz, None, T32.data_ptr(), float(tol), surv.data_ptr(), None, st),
+                   "cppf_backvote_ws")
+    sws = workspace(L.cppf_segment_instance_workspace_bytes(N, P), dev, "segment")
+    _lib.check(L.cppf_segment_instance(idx32.data_ptr(), surv.data_ptr(), P, N, int(min_contrib), point_mask.data_ptr(),
+                                       pairs.data_ptr(), count.data_ptr(), sws.data_ptr(), sws.numel(), st), "cppf_segment_instance")
+    return point_mask, pairs, count
+
+
+def _prep(pc, outputs, idx, corner):
+    require_cuda()
+    dev = pc.device
+    pc = pc.float().contiguous()
+    idx32 = _pairs_tensor(idx, dev).to(I32).contiguous()
+    outputs = outputs.to(dev).float()[:, :2].contiguous()
+    corner = corner.float() if isinstance(corner, torch.Tensor) else torch.from_numpy(np.asarray(corner, np.float32).copy())
+    corner = corner.to(dev).contiguous()
+    return dev, pc, outputs, idx32, corner
+
+
+def segment_instance(pc, outputs, idx, center, corner, res, dims, num_rots=72, tol=None, min_contrib=12):
+    """Cell 11's back-vote and "unsupervised instance segmentation" for one proposal centre: the survivors of the back-vote at
+    `center` (tol = 3 res by default), the points that are endpoints of more than `min_contrib` of them, and the survivors with an
+    endpoint among those points.  outputs: [P,2+] device (columns 0-1 = (mu, nu)); corner / dims: the scene grid's.
+    Returns dict(point_mask bool[N] device, pairs i64[M] device = positions in idx, n_pairs M)."""
+    dev, pc, outputs, idx32, corner = _prep(pc, outputs, idx, corner)
+    tol = float(np.float32(3 * res)) if tol is None else float(np.float32(tol))
+    T32 = torch.as_tensor(np.asarray(center, np.float64).astype(np.float32)).to(dev)
+    with torch.cuda.device(dev):
+        pm, pairs, count = _segment_enqueue(pc, outputs, idx32, T32, corner, res, dims, num_rots, tol, min_contrib)
+    n = int(count.item())
+    return dict(point_mask=pm.bool(), pairs=pairs[:n].long(), n_pairs=n)
+
+
+def _sphere(angle_tol, dev):
+    S = num_sphere_bins(angle_tol)
+    sph64 = np.array(fibonacci_sphere(S), np.float64)
+    return sph64, torch.from_numpy(sph64.astype(np.float32)).to(dev), torch.from_numpy(sph64).to(dev)
+
+
+def zero_shot_poses(encoder9, pc, nrm, feat, idx, cfg, angle_tol=2, max_rot_pairs=10000, rot_order=None, preds=None, num_rots=72,
+                    sigma=1.0, thresh=50, margin=10, max_proposals=32, max_iters=None, min_contrib=12):
+    """Cells 7-11 on a scene: the 9-wide regression head (out_dim = 2+2+2+3: mu nu | up right | aux up, aux right | log-scales)
+    on every pair, the scene vote, the proposals, then per proposal the back-vote, the segmentation, the orientation vote on
+    column 2 of the kept pairs (the first `max_rot_pairs`, or the positions `rot_order` in their list), the axis sign from column
+    4, right = (0, -up_z, up_y) and scale_3d = mean(exp(columns 6..8)) scale_mean 2.
+    pc, nrm f32[N,3], feat f32[N,F], idx [P,2] device tensors; preds: precomputed [P,9] head outputs (then encoder9 is unused).
+    Returns one dict per proposal: T (the proposal, f64[3]), R f64[3,3], up, scale_3d f64[3], scale (its norm), RT f64[4,4],
+    cnt (smoothed peak), diff, point_mask bool[N] (numpy), n_pairs (kept pairs).  zero_shot_scene also returns the grid and
+    the proposals."""
+    return zero_shot_scene(encoder9, pc, nrm, feat, idx, cfg, angle_tol, max_rot_pairs, rot_order, preds, num_rots, sigma, thresh,
+                           margin, max_proposals, max_iters, min_contrib)["poses"]
+
+
+def zero_shot_scene(encoder9, pc, nrm, feat, idx, cfg, angle_tol=2, max_rot_pairs=10000, rot_order=None, preds=None, num_rots=72,
+                    sigma=1.0, thresh=50, margin=10, max_proposals=32, max_iters=None, min_contrib=12):
+    """zero_shot_poses with the intermediate results: dict(poses, preds [P,9] device, grid (raw vote, device), corner f32[3],
+    dims, proposals (loc i32[K,3], value, diff numpy))"""
+    from .inference import grid_shape
+    require_cuda()
+    dev = pc.device
+    pc, nrm = pc.float().contiguous(), nrm.float().contiguous()
+    idx = _pairs_tensor(idx, dev)
+    idx32 = idx.to(I32).contiguous()
+    P = idx.shape[0]
+    if preds is None:
+        if encoder9.out_dim != 9:
+            raise ValueError(f"the zero-shot path needs the 9-wide regression head, the encoder has out_dim {encoder9.out_dim}")
+        with torch.no_grad():
+            preds = encoder9.forward_with_idx(pc, nrm, feat, idx)                             # cell 7
+    preds = torch.as_tensor(preds).to(dev).float().contiguous()
+    if tuple(preds.shape) != (P, 9):
+        raise ValueError(f"preds must be [{P}, 9], got {tuple(preds.shape)}")
+    outputs = preds[:, :2].contiguous()
+    corners, dims = grid_shape(pc.cpu().numpy(), cfg.res)                                    # cell 8
+    corner = torch.from_numpy(corners[0].copy()).to(dev)
+    grid = torch.empty(dims, dtype=F32, device=dev)
+    voting.vote_argmax(pc, outputs, None, idx32, grid, corner, cfg.res, num_rots, True, accumulate=False)
+    loc, val, diff, count = scene_proposals_device(grid, sigma, thresh, margin, max_proposals, max_iters)   # cell 9
+    n = int(count.item())
+    loc, val, diff = loc[:n].cpu().numpy(), val[:n].cpu().numpy(), diff[:n].cpu().numpy()
+    worlds = [corners[0].astype(np.float64) + loc[k].astype(np.int64) * float(cfg.res) for k in range(n)]
+
+    # cell 11, every proposal enqueued before the one read-back
+    L = _lib.lib()
+    st = stream_ptr(dev)
+    sph64, sph32_d, sph64_d = _sphere(angle_tol, dev)
+    S = sph64.shape[0]
+    thr = float(np.float32(np.cos(angle_tol / 180 * np.pi)))
+    tol = float(np.float32(3 * cfg.res))
+    if rot_order is not None:
+        rot_order = torch.as_tensor(rot_order).to(device=dev, dtype=I32).contiguous()
+    rws = workspace(L.cppf_reduce_workspace_bytes(), dev, "zs_reduce")
+    recs, masks, counts_d = [], [], []
+    with torch.cuda.device(dev):
+        for k in range(n):
+            T32 = torch.as_tensor(worlds[k].astype(np.float32)).to(dev)
+            pm, sel, cnt = _segment_enqueue(pc, outputs, idx32, T32, corner, cfg.res, dims, num_rots, tol, min_contrib)
+            counts = torch.zeros(S, dtype=I32, device=dev)
+            rec = torch.zeros(10, dtype=torch.float64, device=dev)          # best_dir[3] | sign sums[3] | exp-scale sums[4]
+            best_idx = torch.empty(1, dtype=torch.int64, device=dev)
+            rot = preds.data_ptr() + 4 * 2
+            if rot_order is None:
+                _lib.check(L.cppf_rot_sphere_count(pc.data_ptr(), rot, 9, idx32.data_ptr(), sel.data_ptr(), cnt.data_ptr(), P,
+                                                   int(max_rot_pairs), int(num_rots), sph32_d.data_ptr(), S, thr, 1,
+                                                   counts.data_ptr(), st), "cppf_rot_sphere_count")
+            else:
+                _lib.check(L.cppf_rot_sphere_count_dirs_order(pc.data_ptr(), rot, 9, 1, 1, idx32.data_ptr(), sel.data_ptr(),
+                                                              cnt.data_ptr(), P, rot_order.data_ptr(), rot_order.numel(),
+                                                              int(max_rot_pairs), int(num_rots), sph32_d.data_ptr(), S, thr, 1,
+                                                              counts.data_ptr(), S, st), "cppf_rot_sphere_count_dirs_order")
+            _lib.check(L.cppf_counts_argmax_select(counts.data_ptr(), S, sph64_d.data_ptr(), best_idx.data_ptr(),
+                                                   rec[0:3].data_ptr(), st), "cppf_counts_argmax_select")
+            _lib.check(L.cppf_axis_sign(pc.data_ptr(), nrm.data_ptr(), idx32.data_ptr(), sel.data_ptr(), cnt.data_ptr(), P,
+                                        preds.data_ptr() + 4 * 4, 9, rec[0:3].data_ptr(), rec[3:6].data_ptr(), rws.data_ptr(),
+                                        rws.numel(), st), "cppf_axis_sign")
+            _lib.check(L.cppf_scale_exp_sum(preds.data_ptr() + 4 * 6, 9, sel.data_ptr(), cnt.data_ptr(), P, rec[6:10].data_ptr(),
+                                            rws.data_ptr(), rws.numel(), st), "cppf_scale_exp_sum")
+            recs.append(rec)
+            masks.append(pm)
+    poses = []
+    for k in range(n):
+        poses.append(_assemble(recs[k].cpu().numpy(), worlds[k], cfg, val[k], diff[k], masks[k].cpu().numpy().astype(bool)))
+    return dict(poses=poses, preds=preds, grid=grid, corner=corners[0], dims=dims, proposals=(loc, val, diff))
+
+
+def _assemble(rec, T, cfg, cnt, diff, point_mask):
+    """host end of cell 11 from one proposal's record"""
+    best = rec[0:3].copy()
+    n_sign = max(rec[5], 1.0)
+    up = -best if rec[4] / n_sign < rec[3] / n_sign else best                   # down_loss < up_loss
+    right = np.array([0, -up[2], up[1]])
+    right = right / np.linalg.norm(right)
+    R = np.stack([right, up, np.cross(right, up)], -1)
+    n = int(rec[9])
+    scale_3d = rec[6:9] / max(n, 1) * np.asarray(cfg.scale_mean, np.float64) * 2
+    scale = float(np.linalg.norm(scale_3d))
+    RT = np.eye(4)
+    RT[:3, :3] = R * scale
+    RT[:3, -1] = T
+    return dict(T=np.asarray(T, np.float64), R=R, up=up, scale_3d=scale_3d, scale=scale, RT=RT, cnt=float(cnt), diff=float(diff),
+                point_mask=point_mask, n_pairs=n)
+
+
+def zero_shot_frame(depth, intrinsics, encoder9, point_encoder, cfg, n_pairs=5_000_000, seed=0, jitter=None, **kw):
+    """Cells 3-11 end to end on the device: depth [H,W] (millimetres, numpy uint16 or device) with no instance masks ->
+    dict(poses (zero_shot_poses' list), hi_pc / hi_normals (the cloud de-duplicated at res), indices (its de-duplication at
+    4 res), pc / normals (the sparse cloud), n_pairs (after the cell 6 filter), and zero_shot_scene's other entries).
+    jitter: f32[n_pixels,3] standard-normal draws for cell 3's augmentation (None: none).  Pairs: frames.draw_pairs(seed, 0, ...)
+    (the notebook's np.random.randint).  kw: zero_shot_poses' options."""
+    from .frames import draw_pairs, instance_cloud
+    from .utils.util import sparse_quantize
+    require_cuda()
+    d = np.asarray(depth) if not isinstance(depth, torch.Tensor) else depth
+    ones = np.ones(tuple(d.shape), bool)
+    hi, hi_nrm = instance_cloud(depth, intrinsics, ones, cfg, jitter)                      # cell 3: res
+    if hi.shape[0] == 0:
+        raise ValueError("the depth frame has no valid pixels")
+    _, ind = sparse_quantize(hi, return_index=True, quantization_size=4 * cfg.res)         # cell 3: 4 res
+    pc, nrm = hi[ind].contiguous(), hi_nrm[ind].contiguous()
+    with torch.no_grad():
+        feat = point_encoder(hi[None], hi_nrm[None])[0][ind].contiguous()                 # cell 7 (kNN on the hi-res cloud)
+    idx, _ = draw_pairs(seed, 0, int(n_pairs), pc.device, pc.shape[0])                     # cell 5
+    idx = distinct_pairs(pc, nrm, idx)                                                     # cell 6
+    out = zero_shot_scene(encoder9, pc, nrm, feat, idx, cfg, **kw)
+    out.update(hi_pc=hi, hi_normals=hi_nrm, indices=ind, pc=pc, normals=nrm, feat=feat, idx=idx, n_pairs=int(idx.shape[0]))
+    return out

@@ -480,6 +480,10 @@ int cppf_axis_sign(const float* pc, const float* nrm, const int32_t* point_idxs,
                    const double* best_dir, double* out, void* workspace, size_t workspace_bytes, void* stream);
 int cppf_scale_sum(const float* scale_logits, int stride, const int32_t* sel, const int32_t* n_sel_dev,
                    int64_t n_sel_host, double* out, void* workspace, size_t workspace_bytes, void* stream);
+/* cppf_scale_exp_sum: the same sums of expf(logit) -- the mean of exp of nocs/zero_shot.ipynb cell 11
+ *   (np.mean(np.exp(preds_scale) * scale_mean * 2, 0)); out = {sum e^sx, sum e^sy, sum e^sz, n}. */
+int cppf_scale_exp_sum(const float* scale_logits, int stride, const int32_t* sel, const int32_t* n_sel_dev,
+                       int64_t n_sel_host, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * The pose tail in six launches (nocs/inference.py:209-303,335 after the centre vote).  The entry points above map one
@@ -758,6 +762,60 @@ size_t cppf_voxel_dedupe_workspace_bytes(int64_t n_points);
 int cppf_voxel_dedupe(const float* pc, int64_t n_points, double res, int32_t* keep_idx, int32_t* count, void* workspace,
                       size_t workspace_bytes, void* stream);
 int cppf_estimate_normals(const float* pc, const int32_t* nbrs, int64_t n_points, int k, float* normals, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Zero-shot scene path (nocs/zero_shot.ipynb cells 6, 9, 11: one depth frame with no instance masks -> proposals, point masks,
+ * poses; csrc/scene.hip).  The Python side is cppf_amd/zero_shot.py; tests/zero_shot_ref.py restates every result bit for bit.
+ *
+ * cppf_pair_filter_distinct (cell 6): keep[p] = 0 for the "indistinguishable" pairs, |n1.n2| > 0.9 & |ab.n1| < 0.1 & |ab.n2| < 0.1
+ *   with ab = (a - b) / (||a - b|| + 1e-7), float32 like numpy; 1 otherwise.  point_idxs device i32 / i64 [n_pairs,2]; a pair with an
+ *   endpoint outside [0, n_points) gets 0.  keep device u8[n_pairs]; the ordered list of the kept pairs is cppf_compact_mask's.
+ *
+ * cppf_gaussian_filter3d (cell 9, scipy.ndimage.gaussian_filter(grid, sigma), mode 'reflect'): bit for bit scipy's result for
+ *   float32 grids.  One pass per axis (0, 1, 2); each output is w[r] x[c] + sum_{d = r..1} (x[c-d] + x[c+d]) w[r-d] in fp64 from the
+ *   float32 input, rounded to float32 per pass; 'reflect' boundaries (= np.pad 'symmetric', repeated for axes shorter than r) for
+ *   any dims >= 1.  weights: HOST f64[2 radius + 1], symmetric (scipy's _gaussian_kernel1d; radius = int(truncate sigma + 0.5) <= 32).
+ *   grid, out device f32[gx,gy,gz], distinct; gx gy gz < 2^30; workspace >= cppf_gaussian_filter3d_workspace_bytes().
+ *
+ * cppf_scene_proposals (cell 9, the whole proposal loop, on the device: graph-capturable, no host round trip): smooths `grid` (the
+ *   raw scene vote) as cppf_gaussian_filter3d does, writes that smoothed grid to smoothed_out when it is not NULL (the caller's copy
+ *   is never suppressed), then loops:
+ *     loc = first arg-max (C order); lll = max(0, loc - margin), rrr = min(dim - 1, loc + margin);
+ *     diff = smoothed[loc] - (the mean of the notebook's 12 float32 edge means, slices half-open lll:rrr, np.mean's order);
+ *     diff > thresh: record (loc, smoothed[loc], diff), the first recorded diff is max_val;
+ *     stop when diff < thresh or diff < 0.7 max_val; else zero smoothed[lll:rrr, lll:rrr, lll:rrr] and repeat.
+ *   Outputs (device): loc i32[max_proposals,3], value f32[max_proposals], diff f32[max_proposals], count i32[1].
+ *   Defined where the notebook is not:
+ *     - an axis < 2 gives 0 proposals (the notebook's edge slices are empty: NaN, then a TypeError);
+ *     - while max_val is unset the 0.7 max_val clause is false (the notebook raises a TypeError when its first diff is exactly
+ *       thresh);
+ *     - the loop stops when an iteration would repeat the previous one's (loc, diff) exactly -- a peak on the last plane of an axis
+ *       that the half-open box never clears: the notebook repeats it forever, so the proposals are the notebook's with the repeats
+ *       removed;
+ *     - at most max_proposals records and max_iters iterations.
+ *   margin 1..64 (an edge slice holds <= 128 cells); the grid must be finite.  Workspace: cppf_scene_proposals_workspace_bytes()
+ *   (two grid copies and a table of one (max, first index) per 8^3 cells: one workgroup runs the loop and rescans only the tiles
+ *   a suppressed box touches).
+ *
+ * cppf_segment_instance (cell 11, "unsupervised instance segmentation"): from the back-vote survivors of one proposal
+ *   (surv_mask device u8[n_pairs], cppf_backvote* at the proposal's centre): point_mask[n] = (n is an endpoint of more than
+ *   min_contrib survivors, pairs (i, i) counting twice), then the survivors with either endpoint in the mask, in pair order:
+ *   pairs_out device i32[n_pairs] (positions in the pair list), count device i32[1].  Integer atomics: the same result on every
+ *   run.  point_idxs device i32[n_pairs,2]; workspace >= cppf_segment_instance_workspace_bytes().
+ * ------------------------------------------------------------------------------------------- */
+int cppf_pair_filter_distinct(const float* pc, const float* nrm, const void* point_idxs, int idx_is_i64, int64_t n_points,
+                              int64_t n_pairs, uint8_t* keep, void* stream);
+size_t cppf_gaussian_filter3d_workspace_bytes(int gx, int gy, int gz);
+int cppf_gaussian_filter3d(const float* grid, float* out, int gx, int gy, int gz, const double* weights, int radius,
+                           void* workspace, size_t workspace_bytes, void* stream);
+size_t cppf_scene_proposals_workspace_bytes(int gx, int gy, int gz);
+int cppf_scene_proposals(const float* grid, int gx, int gy, int gz, const double* weights, int radius, float thresh, int margin,
+                         int max_proposals, int max_iters, int32_t* loc, float* value, float* diff, int32_t* count,
+                         float* smoothed_out, void* workspace, size_t workspace_bytes, void* stream);
+size_t cppf_segment_instance_workspace_bytes(int64_t n_points, int64_t n_pairs);
+int cppf_segment_instance(const int32_t* point_idxs, const uint8_t* surv_mask, int64_t n_pairs, int64_t n_points, int min_contrib,
+                          uint8_t* point_mask, int32_t* pairs_out, int32_t* count, void* workspace, size_t workspace_bytes,
+                          void* stream);
 
 #ifdef __cplusplus
 }
