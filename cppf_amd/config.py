@@ -1,7 +1,7 @@
 """Path parameters of the reference's hydra configs (config/config.yaml, config/category/*.yaml):
 only the keys the hot path reads."""
 from dataclasses import dataclass, field
-from typing import List
+from typing import List, Optional
 
 
 @dataclass
@@ -17,6 +17,8 @@ class CategoryConfig:
     rot_num_bins: int = 36         # config/config.yaml:8
     knn: int = 60                  # config/config.yaml:22
     ppffcs: List[int] = field(default_factory=lambda: [84, 32, 32, 16])   # train.py:35
+    scale_range: Optional[List[float]] = None   # config/category/*.yaml: the object scale drawn per training view (utils/dataset.py:166)
+    npoint_max: int = 10000        # config/config.yaml: views with more points are redrawn (utils/dataset.py:221-222)
 
     @property
     def out_dim(self):             # train.py:35
@@ -43,3 +45,15 @@ CATEGORIES = {
     "table": _c("table", 3e-2, 1.2363029403529906, [0.4305247031772566, 0.35199163168896463, 0.6905431275083608], True),
 }
 NOCS_CATEGORIES = ["bottle", "bowl", "camera", "can", "laptop", "mug"]   # nocs/inference.py synset order
+
+
+# config/category/*.yaml:scale_range (training views only, cppf_amd/meshes.py)
+_SCALE_RANGE = {
+    "bottle": [0.2300, 0.4594], "bowl": [0.1851, 0.2381], "camera": [0.1430, 0.2567], "can": [0.128, 0.18],
+    "laptop": [0.3862, 0.5353], "mug": [0.1501, 0.1995],
+    "bathtub": [0.9871392690983584, 2.3263480392772227], "bed": [1.484997764725992, 4.096944229262802],
+    "bookshelf": [0.1640900157049736, 4.339695465933739], "chair": [0.7999364364268209, 1.559057241958137],
+    "sofa": [0.7900343820741655, 3.7988801202149647], "table": [0.027254089050664287, 3.6816547320083073],
+}
+for _cat, _sr in _SCALE_RANGE.items():
+    CATEGORIES[_cat].scale_range = _sr

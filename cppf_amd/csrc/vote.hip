@@ -2116,6 +2116,7 @@ extern "C" const char* cppf_error_string(int code)
     case CPPF_EWORKSPACE: return "cppf: workspace missing or too small";
     case CPPF_EUNSUPPORTED: return "cppf: unsupported layer shape";
     case CPPF_ENONFINITE: return "cppf: the cloud holds non-finite coordinates";
+    case CPPF_ECAPACITY: return "cppf: a device-side bound (bin list capacity) was exceeded";
     default: return code > 0 ? hipGetErrorString((hipError_t)code) : "cppf: unknown error";
     }
 }

@@ -117,6 +117,40 @@ def train(category, dev, steps=400, n_points=1024, n_pairs=60000, lr=2e-3, seed=
     return penc, enc, losses
 
 
+def train_on_meshes(category, mesh_paths, dev, steps=400, n_pairs=60000, lr=2e-3, seed=0, log=None, encoders=None, sampler=None):
+    """train()'s step, loss and schedule fed by training views of meshes (cppf_amd.meshes.MeshViewSampler: the sample of
+    utils/dataset.py:103-250) instead of analytic shapes.  mesh_paths: OBJ files of the category.  Returns (point_encoder,
+    ppf_encoder, losses)."""
+    from .meshes import MeshViewSampler
+    cfg = syn.CATEGORIES[category]
+    sampler = sampler or MeshViewSampler(mesh_paths, category, dev, seed=seed, n_pairs=n_pairs)
+    penc, enc = encoders or new_encoders(cfg, dev, seed)
+    penc.train()
+    enc.train()
+    opt = torch.optim.Adam([*penc.parameters(), *enc.parameters()], lr=lr)
+    sched = torch.optim.lr_scheduler.CosineAnnealingLR(opt, steps, eta_min=lr * 0.05)
+    losses = []
+    for it in range(steps):
+        s = sampler.sample()
+        pcs, nrms, idx = s["pc"][None], s["normals"][None], s["point_idxs"]
+        opt.zero_grad()
+        with torch.no_grad():
+            dist = torch.cdist(pcs, pcs)                                                     # train.py:61-62
+        feat = penc(pcs, nrms, dist)
+        preds = enc(pcs, nrms, feat, idxs=idx)
+        loss = loss_fn(preds, s["targets_tr"], s["targets_rot"], s["targets_rot_aux"], s["targets_scale"], cfg)
+        loss.backward()
+        opt.step()
+        sched.step()
+        if it % 20 == 0 or it == steps - 1:
+            losses.append(float(loss.item()))
+            if log:
+                log(f"{category} step {it:4d} loss {losses[-1]:.4f} points {pcs.shape[1]}")
+    penc.eval()
+    enc.eval()
+    return penc, enc, losses
+
+
 def infer(penc, enc, ob, dev, n_pairs=100000, seed=0, sphere=None):
     """nocs/inference.py:177-339 on one posed object: kNN + SPRIN features, then cppf_amd.inference.estimate_pose"""
     from .inference import estimate_pose

@@ -50,6 +50,7 @@ extern "C" {
 #define CPPF_EWORKSPACE (-2) /* workspace too small / missing */
 #define CPPF_EUNSUPPORTED (-3) /* layer shape not supported by any device kernel */
 #define CPPF_ENONFINITE (-4) /* a host cloud holds NaN / inf coordinates (cppf_host_grid_shape) */
+#define CPPF_ECAPACITY (-5) /* a device-side bound was exceeded (cppf_raster_depth: the bin list); nothing was dropped silently */
 
 int cppf_abi_version(void);
 const char* cppf_error_string(int code);
@@ -816,6 +817,62 @@ size_t cppf_segment_instance_workspace_bytes(int64_t n_points, int64_t n_pairs);
 int cppf_segment_instance(const int32_t* point_idxs, const uint8_t* surv_mask, int64_t n_pairs, int64_t n_points, int min_contrib,
                           uint8_t* point_mask, int32_t* pairs_out, int32_t* count, void* workspace, size_t workspace_bytes,
                           void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Training views (utils/dataset.py:103-207, csrc/raster.hip): the pyrender `RenderFlags.DEPTH_ONLY` render of one mesh through
+ * the dataset's PinholeCamera (:108-138), and the covered pixels as the dataset's point cloud.  Parity with pyrender is UNPINNED
+ * (pyrender and its 24-bit depth buffer are not part of the project); the definition below is, to the operation, and
+ * tests/mesh_ref.py restates it in numpy bit for bit.  All fp32 arithmetic is IEEE single with no contraction
+ * (-ffp-contract=off), divisions correctly rounded.
+ *
+ * cppf_raster_depth
+ *   verts device f64[n_verts,3] (model frame), faces device i32[n_faces,3], model_view_host HOST f64[12] = rows 0..2 of the
+ *   row-major 4x4 model-view matrix M (NULL = identity).  Camera frame: OpenGL, the camera looks down -z.
+ *   1. Transform (fp64, then rounded):  c_r = ((M[r][0] x + M[r][1] y) + M[r][2] z) + M[r][3];  X = (float)c_0, Y = (float)c_1,
+ *      d = -(float)c_2 (view depth).  A face index outside [0, n_verts) makes the call fail with CPPF_EINVAL.
+ *   2. Near plane (znear; pyrender's default 0.05): vertex inside iff d >= zn (zn = (float)znear).  Sutherland-Hodgman over the
+ *      edges (v0,v1), (v1,v2), (v2,v0): an inside vertex is kept; an edge with one end inside adds the point
+ *      t = (a.d - zn) / (a.d - b.d), x = a.x + t (b.x - a.x), y likewise, d = zn, with a the INSIDE end.  The 3 or 4 vertices p0..
+ *      are fanned: (p0,p1,p2) and (p0,p2,p3).  Nothing is projected through w <= 0; a triangle wholly in front of the plane
+ *      yields nothing.
+ *   3. Projection (P[0][0] = 2 fx / W, P[1][1] = 2 fy / H, no principal-point offset, infinite far plane), GL window coordinates
+ *      (y UP): p00 = (float)(2.0 * fx / W), p11 = (float)(2.0 * fy / H), hw = 0.5f * W, hh = 0.5f * H;
+ *      sx = ((p00 * x) / d + 1.0f) * hw;  sy = ((p11 * y) / d + 1.0f) * hh;  i = 1.0f / d.
+ *   4. Orientation: A = (sx1 - sx0) * (sy2 - sy0) - (sx2 - sx0) * (sy1 - sy0).  A > 0 = CCW in window coordinates (y up) = front
+ *      face (CW in the y-down image).  cull_back != 0: drop unless A > 0.  cull_back == 0: A < 0 swaps v1 and v2 (and their i)
+ *      and negates A.  Then anything with !(A > 0) (zero area, NaN) covers nothing.
+ *      ASSUMPTION: pyrender's Mesh.from_trimesh gives an untextured trimesh a single-sided material, so pyrender culls back
+ *      faces with GL's default CCW front face.  pyrender's source is not part of the project; cull_back = 0 renders both sides.
+ *   5. Bbox (decides which pixels are tested, so it is part of the definition): clampf(v, hi) = fminf(fmaxf(v, -1), hi);
+ *      c0 = max(0, (int)floorf(clampf(min sx - 1, W))), c1 = min(W-1, (int)floorf(clampf(max sx + 1, W))); j0, j1 likewise from
+ *      sy and H.  Pixel (col c, row r; row 0 at the top) is tested when c0 <= c <= c1 and j0 <= H-1-r <= j1.
+ *   6. Coverage at the pixel centre px = c + 0.5f, py = (H - 1 - r) + 0.5f, with E(a,b) = (bx - ax) * (py - ay) - (by - ay) *
+ *      (px - ax):  w0 = E(v1,v2), w1 = E(v2,v0), w2 = E(v0,v1).  Covered iff every w_k > 0, or w_k == 0 on a top-left edge:
+ *      edge a->b is top-left iff (by - ay) < 0, or (by - ay) == 0 and (bx - ax) < 0 (left edges and horizontal top edges).
+ *   7. Depth (1/d affine in screen space): d = ((w0 + w1) + w2) / ((w0 * i0 + w1 * i1) + w2 * i2).  The pixel keeps the MINIMUM
+ *      over the fragments that cover it (independent of order); background is 0.0f, as pyrender returns it.  depth: device
+ *      f32[H,W], every pixel written.
+ *   Limits: 1 <= n_faces <= 2^28, W, H <= 8192.  The work is binned into 16x16 tiles; the bin list holds max_bin_entries
+ *   (primitive, tile) pairs (<= 2^31 - 1).  Workspace: cppf_raster_workspace_bytes(n_faces, W, H, max_bin_entries); its first 8
+ *   bytes hold the status {code, bin entries needed} of the last call.  When the bin list is too small (or a face index is out
+ *   of range) every depth pixel is NaN and the status code is CPPF_ECAPACITY (CPPF_EINVAL): no fragment is dropped silently.
+ *   sync != 0: the call waits for its stream and RETURNS that code; sync == 0: it returns at once and the caller reads the
+ *   status words from the workspace.
+ *
+ * cppf_depth_points (:203-207 with utils/util.py:598-631): the pixels with depth > 0 in row-major order (np.where), through
+ *   kinv_host (HOST f64[9], row-major inv(K); the dataset's K = [[591.0125,0,320],[0,590.16775,240],[0,0,1]]) with
+ *   cppf_backproject's arithmetic, xyz = (fma(k01, v, k00 u) + k02, ...), (X, Y, Z) = xyz * z / xyz.z; backproject's x/y negation
+ *   and the dataset's x/z negation give pts = (X, -Y, -Z) device f64[H*W,3].  u, v are the INTEGER pixel coordinates while the
+ *   render samples pixel centres: the dataset's half-pixel shift, kept.  pix device i32[H*W] = r*W + c, count device i32[1].
+ *   H*W <= 8192 * 1024; workspace >= cppf_depth_points_workspace_bytes(H, W).
+ * ------------------------------------------------------------------------------------------- */
+size_t cppf_raster_workspace_bytes(int64_t n_faces, int W, int H, int64_t max_bin_entries);
+int cppf_raster_depth(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const double* model_view_host,
+                      double fx, double fy, int W, int H, double znear, int cull_back, float* depth, int64_t max_bin_entries, int sync,
+                      void* workspace, size_t workspace_bytes, void* stream);
+size_t cppf_depth_points_workspace_bytes(int H, int W);
+int cppf_depth_points(const float* depth, int H, int W, const double* kinv_host, double* pts, int32_t* pix, int32_t* count,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
