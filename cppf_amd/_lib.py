@@ -88,6 +88,10 @@ _SIGS = {
     "cppf_raster_depth": (C.c_int, [vp, i64, vp, i64, vp, C.c_double, C.c_double, i32, i32, C.c_double, i32, vp, i64, i32, vp, sz, vp]),
     "cppf_depth_points_workspace_bytes": (sz, [i32, i32]),
     "cppf_depth_points": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "cppf_surface_sample_workspace_bytes": (sz, [i32, i64]),
+    "cppf_surface_sample_batch": (C.c_int, [vp, vp, vp, vp, i32, i64, C.c_uint64, i64, vp, vp, vp, vp, sz, vp]),
+    "cppf_mesh_vote_stats_workspace_bytes": (sz, [i32, i64, i64]),
+    "cppf_mesh_vote_stats_batch": (C.c_int, [vp, i32, i64, i64, C.c_uint64, i64, vp, vp, vp, sz, vp]),
     "cppf_pair_mlp_backward_workspace_bytes": (sz, [i64, i64, i32, C.POINTER(C.c_int), i32, i32]),
     "cppf_pair_mlp_backward": (C.c_int, [vp, vp, vp, vp, i32, vp, C.POINTER(C.c_int64), i64, i32, C.POINTER(C.c_int), i32,
                                          i64, i32, vp, vp, vp, vp, sz, vp]),

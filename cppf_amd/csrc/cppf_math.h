@@ -12,6 +12,20 @@
 
 #define CPPF_PI 3.14159265358979323846264338327950288  // reference models/voting.py:6
 
+// Philox-4x32-10 (Salmon et al., SC'11; the Random123 constants): counter c, key k -> four 32-bit words.  Stateless, so a draw
+// depends on (key, counter) only.  Counter layouts: cppf_sample_pairs / cppf_stage_batch (csrc/preproc.hip) use {index lo, index hi,
+// 0 | 1, 0}; the mesh statistics (csrc/mesh_stats.hip, include/cppf.h) use {index, mesh, 2 | 3, 0}.
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k)
+{
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c.x, p1 = (unsigned long long)0xCD9E8D57u * c.z;
+        c = make_uint4((unsigned)(p1 >> 32) ^ c.y ^ k.x, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k.y, (unsigned)p0);
+        k.x += 0x9E3779B9u; k.y += 0xBB67AE85u;
+    }
+    return c;
+}
+
 namespace cppf {
 
 struct f3 { float x, y, z; };

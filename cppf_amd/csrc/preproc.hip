@@ -12,6 +12,7 @@
 #include <string.h>
 #include "../../include/cppf.h"
 #include "compact.h"
+#include "cppf_math.h"
 
 namespace {
 
@@ -330,18 +331,8 @@ FcLayout fc_layout(int H, int W, int n_cap, int k)
     return L;
 }
 
-// ---- pair list + bin uniforms drawn on the device (cppf_sample_pairs): Philox-4x32-10 (Salmon et al., SC'11), counter = pair index,
+// ---- pair list + bin uniforms drawn on the device (cppf_sample_pairs): Philox-4x32-10 (cppf_math.h), counter = pair index,
 // key = the caller's 64-bit seed; stateless, so a pair's draw depends on (seed, pair index) only -- whichever rank or stream draws it.
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c.x, p1 = (unsigned long long)0xCD9E8D57u * c.z;
-        c = make_uint4((unsigned)(p1 >> 32) ^ c.y ^ k.x, (unsigned)p1, (unsigned)(p0 >> 32) ^ c.w ^ k.y, (unsigned)p0);
-        k.x += 0x9E3779B9u; k.y += 0xBB67AE85u;
-    }
-    return c;
-}
 __global__ __launch_bounds__(256) void sample_pairs_kernel(long long* __restrict__ idx, float* __restrict__ u_tr, float* __restrict__ u_rot,
                                                            int64_t P, int64_t n_points, const int32_t* __restrict__ n_dev,
                                                            unsigned long long seed, const unsigned long long* __restrict__ seed_dev)

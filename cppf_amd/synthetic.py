@@ -214,24 +214,29 @@ def make_posed_object(category="bottle", n_points=2048, seed=0, size_range=(0.8,
                 half_extents=np.array([sx, sy, sz]), cfg=cfg, category=category)
 
 
+def philox4x32_10(counter, seed):
+    """Philox-4x32-10 (csrc/cppf_math.h) on the host: counter = four arrays (or scalars) of 32-bit words, key = the 64-bit `seed`
+    -> the four output words as uint64 arrays holding 32-bit values"""
+    M0, M1, W0, W1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+    mask, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    c = np.broadcast_arrays(*[np.asarray(w, dtype=np.uint64) for w in counter])
+    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32)
+    for _ in range(10):
+        p0, p1 = M0 * c[0], M1 * c[2]                           # 32 x 32 -> 64 bit products
+        c = [(p1 >> s32) ^ c[1] ^ k0, p1 & mask, (p0 >> s32) ^ c[3] ^ k1, p0 & mask]
+        k0, k1 = (k0 + W0) & mask, (k1 + W1) & mask
+    return c
+
+
 def philox_pairs(seed, n_pairs, n_points):
     """Host twin of the device sampler (cppf_sample_pairs / cppf_stage_batch, csrc/preproc.hip): Philox-4x32-10 keyed by the 64-bit
     `seed`, counter = {pair index, 0 | 1} -> (idx i64[P,2] uniform over [0, n_points), u_tr f32[P,2], u_rot f32[P,2] in [0, 1)), the
     same numbers bit for bit (tests/test_gpu_resident.py), so that a checker on the host can reproduce the pairs a captured chain
     drew on the device (the reference draws them with np.random.randint / torch.multinomial, nocs/inference.py:177,186,250)."""
-    M0, M1, W0, W1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
     mask, s32 = np.uint64(0xFFFFFFFF), np.uint64(32)
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     p = np.arange(int(n_pairs), dtype=np.uint64)
-
-    def block(c2):
-        c = [p & mask, p >> s32, np.full_like(p, c2), np.zeros_like(p)]
-        k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32)
-        for _ in range(10):
-            p0, p1 = M0 * c[0], M1 * c[2]                       # 32 x 32 -> 64 bit products
-            c = [(p1 >> s32) ^ c[1] ^ k0, p1 & mask, (p0 >> s32) ^ c[3] ^ k1, p0 & mask]
-            k0, k1 = (k0 + W0) & mask, (k1 + W1) & mask
-        return c
+    block = lambda c2: philox4x32_10([p & mask, p >> s32, np.full_like(p, c2), np.zeros_like(p)], seed)
     a, b = block(0), block(1)
     N = np.uint64(int(n_points))
     idx = np.stack([(a[0] * N) >> s32, (a[1] * N) >> s32], -1).astype(np.int64)

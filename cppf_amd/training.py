@@ -26,10 +26,7 @@ def real2prob(val, max_val, num_bins):
 def targets(pc, normals, idx, center, R, half_extents, cfg):
     """utils/dataset.py:27-60 (generate_target) + :229-246 for an object whose centre / axes / half extents are known, as soft
     bin distributions: (tr [P,2,tr_bins], rot [P,2,rot_bins], aux [P,2], scale [3]) on pc.device (pc in the WORLD frame).
-    generate_target's `right_sym` branch (utils/dataset.py:49-50) is not restated: every config of the reference leaves it False
-    (config/category/*.yaml), and a config that sets it is refused rather than silently trained without it."""
-    if getattr(cfg, "right_sym", False):
-        raise NotImplementedError("right_sym categories are not supported by cppf_amd.training.targets (no reference config uses them)")
+    cfg.right_sym: generate_target's right_sym branch (utils/dataset.py:49-50), th_right = min(th_right, arccos(-u . right))."""
     dev = pc.device
     c = torch.as_tensor(center, dtype=torch.float32, device=dev)
     Rm = torch.as_tensor(R, dtype=torch.float32, device=dev)
@@ -45,6 +42,8 @@ def targets(pc, normals, idx, center, R, half_extents, cfg):
     if cfg.up_sym:
         th_up = torch.minimum(th_up, torch.arccos(torch.clamp(-(u @ up), -1, 1)))
     th_right = torch.arccos(torch.clamp(u @ right, -1, 1))
+    if getattr(cfg, "right_sym", False):
+        th_right = torch.minimum(th_right, torch.arccos(torch.clamp(-(u @ right), -1, 1)))
     n = normals[idx[:, 0]].clone()
     n[(n * u).sum(-1) < 0] *= -1
     aux = torch.stack([(n @ up > 0), (n @ right > 0)], -1).float()
@@ -117,13 +116,16 @@ def train(category, dev, steps=400, n_points=1024, n_pairs=60000, lr=2e-3, seed=
     return penc, enc, losses
 
 
-def train_on_meshes(category, mesh_paths, dev, steps=400, n_pairs=60000, lr=2e-3, seed=0, log=None, encoders=None, sampler=None):
+def train_on_meshes(category, mesh_paths, dev, steps=400, n_pairs=60000, lr=2e-3, seed=0, log=None, encoders=None, sampler=None,
+                    cfg=None):
     """train()'s step, loss and schedule fed by training views of meshes (cppf_amd.meshes.MeshViewSampler: the sample of
-    utils/dataset.py:103-250) instead of analytic shapes.  mesh_paths: OBJ files of the category.  Returns (point_encoder,
-    ppf_encoder, losses)."""
+    utils/dataset.py:103-250) instead of analytic shapes.  mesh_paths: OBJ files of the category.  cfg: the category's
+    CategoryConfig (e.g. config.load_category_yaml of a file written by scripts/gen_stats.py) in place of CATEGORIES[category];
+    a name outside NOCS_CATEGORIES draws the SUN RGB-D views (utils/dataset.py:101).  Returns (point_encoder, ppf_encoder,
+    losses)."""
     from .meshes import MeshViewSampler
-    cfg = syn.CATEGORIES[category]
-    sampler = sampler or MeshViewSampler(mesh_paths, category, dev, seed=seed, n_pairs=n_pairs)
+    cfg = cfg or syn.CATEGORIES[category]
+    sampler = sampler or MeshViewSampler(mesh_paths, category, dev, seed=seed, n_pairs=n_pairs, cfg=cfg)
     penc, enc = encoders or new_encoders(cfg, dev, seed)
     penc.train()
     enc.train()

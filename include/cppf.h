@@ -874,6 +874,65 @@ size_t cppf_depth_points_workspace_bytes(int H, int W);
 int cppf_depth_points(const float* depth, int H, int W, const double* kinv_host, double* pts, int32_t* pix, int32_t* count,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Mesh statistics (gen_stats.py, csrc/mesh_stats.hip): the per-mesh figures a new category's config is written from -- surface
+ * samples of each mesh, then the bounding box and the maxima of generate_target's targets_tr (utils/dataset.py:20-36) over random
+ * pairs.  Both calls take a batch of M meshes (one launch sequence per batch) and have no host synchronisation.  Parity with
+ * Open3D's SamplePointsUniformly (its mt19937 stream, its summation) is UNPINNED: Open3D is not part of the project.  The
+ * definition below is, to the operation, and tests/mesh_stats_ref.py restates it in numpy bit for bit.  All arithmetic is IEEE
+ * double with no contraction (-ffp-contract=off); division and sqrt are correctly rounded.
+ *
+ * Two facts keep the device side small:
+ *   - the normals only feed target_rot_aux, which gen_stats.py discards: the statistics need no normals;
+ *   - up_sym / right_sym / z_right change target_rot only, never targets_tr: the statistics need no flags (they matter only once
+ *     written into a config).
+ *
+ * Uniforms: Philox-4x32-10 (csrc/cppf_math.h) keyed by `seed` (key = {seed lo, seed hi}).  Counter {index, mesh, stream, 0} with
+ * mesh = first_mesh + the mesh's position in the batch, stream 2 = surface points (index = point k), stream 3 = pairs (index =
+ * pair p); streams 0 and 1 are cppf_sample_pairs'.  So a mesh's draws depend on (seed, first_mesh + m) alone: a batch of M equals
+ * M calls of one mesh with first_mesh = 0 .. M-1.  u53(w0, w1) = ((w0 >> 5) * 2^26 + (w1 >> 6)) * 2^-53, in [0, 1).
+ *
+ * cppf_surface_sample_batch (Open3D's SamplePointsUniformly): n_points points per mesh.
+ *   verts device f64[V,3] and faces device i32[F,3] of all meshes, concatenated; face indices are LOCAL to their mesh.
+ *   vert_off_host / face_off_host HOST i64[M+1], starting at 0: mesh m has vertices [vo[m], vo[m+1]) and faces [fo[m], fo[m+1]),
+ *   at least one of each and at most 2^31 - 1.
+ *   1. Area (Open3D's formula): x = v0 - v1, y = v0 - v2, c = x cross y (c0 = x1 y2 - x2 y1, c1 = x2 y0 - x0 y2,
+ *      c2 = x0 y1 - x1 y0), a_t = 0.5 * sqrt((c0 c0 + c1 c1) + c2 c2).  A face index outside its mesh gives NaN and status bit 2.
+ *   2. Total S, blocked: K = ceil(F / 1024); block l (0..1023) holds faces [l K, min(F, (l+1) K)); s_l = ((0 + a) + a) ... left to
+ *      right over its block, S = ((0 + s_0) + s_1) ... + s_1023.  S not in (0, inf) (every face degenerate, or a NaN / inf
+ *      coordinate) sets status bit 1.
+ *   3. q_t = a_t / S.  Cumulative area, blocked as in 2: T_l = ((0 + q) + q) ... over block l, B_0 = 0, B_l = B_l-1 + T_l-1, and
+ *      within block l C_t = ((B_l + q_first) + ...) + q_t left to right.  For F <= 1024 (K = 1) this is Open3D's serial chain.
+ *   4. Counts (Open3D's rule): E_t = min(N, round(C_t * N)) with round = halves away from zero (std::round, not numpy's
+ *      round-half-even), E_{F-1} = N.  Face t gets the points [E_{t-1}, E_t) (E_{-1} = 0): point k lies on the first face with
+ *      E_t > k.  Zero-area faces get none.
+ *   5. Point k on face (v0, v1, v2): {w} = Philox({k, mesh, 2, 0}), r1 = u53(w.x, w.y), r2 = u53(w.z, w.w), s = sqrt(r1),
+ *      a = 1 - s, b = s * (1 - r2), c = s * r2, p_j = (a * v0_j + b * v1_j) + c * v2_j.
+ *   points device f64[M, n_points, 3]; face_ids device i32[M, n_points] (local face index; NULL = not written); status device
+ *   i32[M] (0 = sampled).  A mesh with a status bit gets NaN points and face id -1; the other meshes are unaffected.
+ *   n_points <= 2^31 - 1, first_mesh + M <= 2^32.  Workspace >= cppf_surface_sample_workspace_bytes(M, fo[M]).  The offsets are
+ *   copied to the device inside the call.
+ *
+ * cppf_mesh_vote_stats_batch (the loop body of gen_stats.py): points device f64[M, n_points, 3] (e.g. the samples above).
+ *   1. Bounding box lo, hi per axis, centre c = (lo + hi) / 2; the centred maximum / minimum hc = hi - c, lc = lo - c (rounding is
+ *      monotonic, so these are the max / min of the centred points); e = hc - lc, diag = sqrt((e0 e0 + e1 e1) + e2 e2).
+ *   2. Pair p < n_pairs: {w} = Philox({p, mesh, 3, 0}), i = (w.x * N) >> 32, j = (w.y * N) >> 32 (cppf_sample_pairs' rule; i == j
+ *      is kept, as np.random.randint keeps it).  a = P_i - c, b = P_j - c (per coordinate), d = a - b, u = d / (sqrt((dx dx +
+ *      dy dy) + dz dz) + 1e-7), proj = (ax ux + ay uy) + az uz, o = a - proj u, dist2o = sqrt((ox ox + oy oy) + oz oz).
+ *   3. Max of |proj| and of dist2o over the pairs (exact in any order), then cast to float32 (the reference's max over float32
+ *      values: the cast is monotonic).
+ *   stats device f64[M,6] = {diag, max|proj| (a float32 value), max dist2o (a float32 value), hc_x, hc_y, hc_z}; status device
+ *   i32[M]: 1 = a non-finite point (that row is NaN).  n_pairs <= 2^32 - 1.  Workspace >= cppf_mesh_vote_stats_workspace_bytes.
+ * ------------------------------------------------------------------------------------------- */
+size_t cppf_surface_sample_workspace_bytes(int n_meshes, int64_t n_faces_total);
+int cppf_surface_sample_batch(const double* verts, const int32_t* faces, const int64_t* vert_off_host, const int64_t* face_off_host,
+                              int n_meshes, int64_t n_points, unsigned long long seed, int64_t first_mesh, double* points,
+                              int32_t* face_ids, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+size_t cppf_mesh_vote_stats_workspace_bytes(int n_meshes, int64_t n_points, int64_t n_pairs);
+int cppf_mesh_vote_stats_batch(const double* points, int n_meshes, int64_t n_points, int64_t n_pairs, unsigned long long seed,
+                               int64_t first_mesh, double* stats, int32_t* status, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,11 @@ line, resolved against --shapenet-root):
 
     python scripts/train_meshes.py --category bottle --meshes ShapeNetCore.v2/02876657 --steps 20000 --out bottle.npz
     python scripts/train_meshes.py --category bottle --meshes data/shapenet_names/bottle.txt --shapenet-root ShapeNetCore.v2
+
+A category outside cppf_amd.config.CATEGORIES trains from a category file (the flat form of config/category/*.yaml, e.g. written
+by scripts/gen_stats.py --write-config):
+
+    python scripts/train_meshes.py --category mycat --config mycat.yaml --meshes my_meshes/ --steps 2000
 """
 import argparse
 import json
@@ -18,7 +23,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cppf_amd import meshes, training     # noqa: E402
+from cppf_amd import config, meshes, training     # noqa: E402
 
 
 def main():
@@ -31,7 +36,13 @@ def main():
     ap.add_argument("--lr", type=float, default=2e-3)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None, help="weights file (default: trained_<category>_meshes.npz)")
+    ap.add_argument("--config", default=None, help="category file (flat YAML of config/category/*.yaml) in place of the built-in one")
     args = ap.parse_args()
+    cfg = config.load_category_yaml(args.config) if args.config else None
+    if cfg is not None and cfg.category != args.category:
+        sys.exit(f"{args.config} is for category {cfg.category!r}, not {args.category!r}")
+    if cfg is None and args.category not in config.CATEGORIES:
+        sys.exit(f"category {args.category!r} has no built-in config: pass --config FILE.yaml (scripts/gen_stats.py --write-config)")
     paths = meshes.mesh_paths(args.meshes, args.shapenet_root)
     missing = [p for p in paths if not os.path.exists(p)]
     if not paths or missing:
@@ -40,7 +51,7 @@ def main():
     print(f"{args.category}: {len(paths)} meshes")
     t0 = time.perf_counter()
     penc, enc, losses = training.train_on_meshes(args.category, paths, dev, steps=args.steps, n_pairs=args.n_pairs, lr=args.lr,
-                                                 seed=args.seed, log=print)
+                                                 seed=args.seed, log=print, cfg=cfg)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     out = args.out or f"trained_{args.category}_meshes.npz"
