@@ -143,7 +143,118 @@ def grid_class(dims):
     return hit
 
 
-class CenterPipeline:
+class _GraphCache:
+    """The captured hipGraphs of one pipeline or chain and the one way they are captured and replayed.  One entry per FORM (None for
+    the classes with one form, `full_first` False / True for PosePipeline and PoseChain) = (graph, the key it was captured under,
+    the tensors its launches write): a captured form owns its outputs / heads / feat, so whoever switches the form gets the other
+    form's tensors back from run()."""
+
+    def __init__(self, owner, use_graph):
+        # scratch requested by a chain belongs to its owner (see workspace_scope): pipelines replay concurrently
+        self.scope, self.device, self.use_graph, self.entries = id(owner), owner.device, use_graph, {}
+
+    def graph(self, form=None):
+        entry = self.entries.get(form)
+        return entry[0] if entry is not None else None
+
+    def clear(self):
+        self.entries = {}
+
+    def _images(self, members, check_weights, entry):
+        """the weight-image part of the key.  check_weights=True (or nothing captured yet): a changed parameter is re-packed here, on
+        this stream, into the buffer the captured launches read, and the images' addresses are returned; None: the caller refreshed
+        the images itself (BatchPoseRunner, once per batch), only their addresses are looked at; False: nothing is (a caller that
+        runs many instances between parameter updates)"""
+        if check_weights or entry is None:
+            return tuple(p._weight_images() for p in members)
+        return tuple(p._image_ptrs() for p in members) if check_weights is None else entry[1][0]
+
+    def run(self, chain_fn, members, check_weights=True, extra=None, form=None, eager=False):
+        """Run `chain_fn` (the launches of `members`, CenterPipelines; returns the tensors it wrote) as the replay of its captured
+        graph -> those tensors.  The graph is captured on first use and again when its key = (weight images, `extra`: whatever else
+        the launches bake in) changed: a moved / resized image, another vote width, other member buffers.  eager (or use_graph
+        False): launch instead.  Either way the run is ordered after a weight image rebuilt in place on another stream, and a later
+        rebuild after it."""
+        with torch.no_grad(), workspace_scope(self.scope):
+            entry = None
+            if self.use_graph and not eager:
+                entry = self.entries.get(form)
+                key = (self._images(members, check_weights, entry), extra)
+                if entry is None or entry[1] != key:
+                    self.entries.pop(form, None)
+                    entry = None                          # (a stale graph's memory goes before the new one's is taken)
+                    # warm up on a side stream (lazy attribute setting, weight packing, scratch allocation), then capture; the
+                    # captured launches read the static buffers, so later loads just change the data
+                    cur = torch.cuda.current_stream(self.device)
+                    s = torch.cuda.Stream(device=self.device)
+                    s.wait_stream(cur)
+                    with torch.cuda.stream(s):
+                        chain_fn()
+                        chain_fn()
+                    cur.wait_stream(s)
+                    graph = torch.cuda.CUDAGraph()
+                    # thread_local: other threads (the RCCL watchdog of a multi-rank run) may touch the runtime meanwhile
+                    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                        tensors = chain_fn()
+                    entry = self.entries[form] = (graph, key, tensors)
+            for p in members:
+                p._await_images()
+            if entry is None:
+                tensors = chain_fn()
+            else:
+                entry[0].replay()
+                tensors = entry[2]
+            for p in members:
+                p._note_images_read()
+        return tensors
+
+
+class _Captured:
+    """what the pipelines and chains share: a _GraphCache in `_cache`, the form the next run uses, and the way out"""
+
+    full_first = None       # None: the class has one captured form
+
+    @property
+    def _graph(self):
+        """the graph the next replay (of the current form) uses, None before its capture"""
+        return self._cache.graph(self.full_first)
+
+    def release(self):
+        """drop the captured graphs and this object's scratch buffers (BatchPoseRunner's cache eviction)"""
+        self._cache.clear()
+        release_scope(id(self))      # scratch is keyed by id(self): it must not outlive the object
+
+    def __del__(self):
+        try:
+            self.release()
+        except Exception:
+            pass
+
+
+def _point_features(p):
+    """the per-point features of member `p` (nocs/inference.py:180-181, no N x N matrix): its point encoder's launches, or the
+    features it was loaded with"""
+    if p.point_encoder is None:
+        return p.feat
+    if p.dynamic:
+        return p.point_encoder.forward_dyn(p.pc, p.nrm, p.shape, out=p._feat_out, nbrs=p._nbrs, nbrs_ready=p.nbrs_ready)
+    return p.point_encoder(p.pc[None], p.nrm[None])[0]
+
+
+def _decode_items(pipes, feats, with_heads):
+    """the members as models.model.forward_decode_batch takes them"""
+    return [dict(encoder=p.encoder, pc=p.pc, pc_normal=p.nrm, feat=f, idxs=p.idx, u_tr=p.u_tr, vote_range=p.cfg.vote_range,
+                 **(dict(u_rot=p.u_rot) if with_heads else {})) for p, f in zip(pipes, feats)]
+
+
+def _vote_items(pipes, outputs):
+    """the members as models.voting.vote_argmax_batch takes them"""
+    return [dict(points=p.pc, outputs=o, point_idxs=p.idx, corner=p.corner, res=p.cfg.res, out_idx=p.out_idx, out_val=p.out_val,
+                 **(dict(grid=p.grid_flat, shape=p.shape, many_tiles=p.many_tiles) if p.dynamic else dict(grid=p.grid)))
+            for p, o in zip(pipes, outputs)]
+
+
+class CenterPipeline(_Captured):
     """The centre chain (PPF -> MLP -> decode -> vote -> arg-max) for a fixed problem shape, with static
     device buffers and -- by default -- the three kernel launches captured once in a hipGraph, so that a
     replay costs one launch on the host instead of ~0.25 ms of Python per object.
@@ -217,9 +328,9 @@ class CenterPipeline:
         self.out_idx = self.result[:8].view(torch.int64)
         self.out_val = self.result[8:12].view(F32)
         self.outputs = self.heads = None
-        self._graph = None
-        self._use_graph = use_graph
-        self._images = None
+        self.nbrs_ready = False      # dynamic + point encoder: `_nbrs` already holds the cloud's neighbour sets (frames.FrameRunner)
+        self._image_gens = {}        # the weight-image rebuilds this pipeline has waited for (_await_images)
+        self._cache = _GraphCache(self, use_graph)
 
     def set_shape(self, n_points, dims, shape_src=None, upload=True):
         """dynamic pipelines: the next run's real shape.  `shape_src`: a (pinned) host i32[4] tensor the caller has filled
@@ -268,25 +379,21 @@ class CenterPipeline:
             dst.copy_(src, non_blocking=True)
 
     def _chain(self):
-        shape = self.shape if self.dynamic else None
-        if self.point_encoder is not None:                                    # nocs/inference.py:180-181, no N x N matrix
-            if self.dynamic:
-                self.feat = self.point_encoder.forward_dyn(self.pc, self.nrm, shape, out=self._feat_out, nbrs=self._nbrs,
-                                                           nbrs_ready=getattr(self, "nbrs_ready", False))
-            else:
-                self.feat = self.point_encoder(self.pc[None], self.nrm[None])[0]
-        self.outputs, self.heads = self.encoder.forward_decode(
-            self.pc, self.nrm, self.feat, self.idx, self.u_tr, self.cfg.vote_range,
+        """enqueue the launches -> (outputs, heads, feat), the tensors they write"""
+        feat = _point_features(self)
+        outputs, heads = self.encoder.forward_decode(
+            self.pc, self.nrm, feat, self.idx, self.u_tr, self.cfg.vote_range,
             self.u_rot if self.with_heads else None, self.cfg.tr_num_bins, self.cfg.rot_num_bins)
         # the vote reads the int64 pair list directly (the reference copies it to int32 first, nocs/inference.py:202)
         if self.dynamic:
-            voting.vote_argmax_dyn(self.pc, self.outputs, None, self.idx, self.grid_flat, shape, self.corner,
+            voting.vote_argmax_dyn(self.pc, outputs, None, self.idx, self.grid_flat, self.shape, self.corner,
                                    self.cfg.res, self.num_rots, self.adaptive, self.out_idx, self.out_val,
                                    many_tiles=self.many_tiles, accumulate=False, workgroups=self.vote_workgroups)
         else:
-            voting.vote_argmax(self.pc, self.outputs, None, self.idx, self.grid, self.corner, self.cfg.res,
+            voting.vote_argmax(self.pc, outputs, None, self.idx, self.grid, self.corner, self.cfg.res,
                                self.num_rots, self.adaptive, self.out_idx, self.out_val, accumulate=False,
                                workgroups=self.vote_workgroups)
+        return outputs, heads, feat
 
     def _weight_images(self):
         """(re)build the encoders' weight images if a parameter changed; returns their identity (addresses)"""
@@ -304,42 +411,13 @@ class CenterPipeline:
         return (enc._packed.data_ptr(),) if penc is None else (enc._packed.data_ptr(), penc._packed[0].data_ptr())
 
     def run(self, check_weights=True):
-        """check_weights=None: the caller refreshed the weight images itself, only their addresses are compared (_image_ptrs).
-        check_weights=False skips the per-run look at the encoders' parameters (a caller that runs many instances
-        between parameter updates checks once per batch: BatchPoseRunner)."""
-        # scratch requested by the chain belongs to this pipeline (see workspace_scope): pipelines replay concurrently
-        with torch.no_grad(), workspace_scope(id(self)):
-            if not self._use_graph:
-                self._chain()
-                return self.out_idx, self.out_val
-            # a changed parameter is re-packed here, on this stream, into the buffer the captured launches read; if the
-            # image itself moved (device change, other size) the captured addresses are stale: capture again
-            images = (self._weight_images() if check_weights or self._graph is None else
-                      (self._image_ptrs() if check_weights is None else self._images))
-            if self._graph is not None and images != self._images:
-                self._graph = None
-            if self._graph is None:
-                # warm up on a side stream (lazy attribute setting, weight packing, scratch allocation), then
-                # capture; the captured launches read the static buffers, so later loads just change the data
-                s = torch.cuda.Stream(device=self.device)
-                s.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(s):
-                    self._chain()
-                    self._chain()
-                torch.cuda.current_stream(self.device).wait_stream(s)
-                self._graph = torch.cuda.CUDAGraph()
-                # thread_local: other threads (the RCCL watchdog of a multi-rank run) may touch the runtime meanwhile
-                with torch.cuda.graph(self._graph, capture_error_mode="thread_local"):
-                    self._chain()
-                self._images = images
-            self._await_images()
-            self._graph.replay()
-            self._note_images_read()
+        """check_weights: how far the encoders' weight images are looked at before the run (_GraphCache._images)"""
+        self.outputs, self.heads, self.feat = self._cache.run(self._chain, (self,), check_weights, None, self.full_first)
         return self.out_idx, self.out_val
 
     def _await_images(self):
         """another stream may have rebuilt a weight image in place since this pipeline last replayed: wait for it"""
-        seen = self.__dict__.setdefault("_image_gens", {})     # per (encoder, stream): a pipeline replayed on a NEW stream must wait too
+        seen = self._image_gens                                # per (encoder, stream): a pipeline replayed on a NEW stream must wait too
         sid = torch.cuda.current_stream(self.device).cuda_stream
         for enc in (self.encoder, self.point_encoder):
             if enc is not None:
@@ -356,20 +434,7 @@ class CenterPipeline:
         n = int(n or 0)
         if n != self.vote_workgroups:
             self.vote_workgroups = n
-            self._graph = None
-            if hasattr(self, "_graphs"):
-                self._graphs = {}
-
-    def release(self):
-        """drop the captured graph and this pipeline's scratch buffers (BatchPoseRunner's cache eviction)"""
-        self._graph = None
-        release_scope(id(self))
-
-    def __del__(self):
-        try:
-            release_scope(id(self))      # scratch is keyed by id(self): it must not outlive the object
-        except Exception:
-            pass
+            self._cache.clear()
 
 
 def estimate_pose(encoder, pc, pc_normal, feat, point_idxs, u_tr, u_rot, cfg, sphere_pts, pc_host=None, num_rots=72,
@@ -563,7 +628,7 @@ def nocs_result(poses, res=None):
     return res
 
 
-class CenterBatchPipeline:
+class CenterBatchPipeline(_Captured):
     """Several CenterPipelines replayed as ONE captured chain: the pair lists of all members in one launch of the pair kernel
     (models.model.forward_decode_batch: the ~9 us a launch spends before its first MFMA are paid once, 70.9 -> 64.0 us per C2
     list in threes), then the members' votes -- by default in ONE vote launch and ONE reduce launch as well
@@ -585,7 +650,7 @@ class CenterBatchPipeline:
                                  "with the same num_rots / adaptive")
         self.pipes, self.device = pipes, pipes[0].device
         self.vote_batch, self.vote_workgroups = bool(vote_batch), int(vote_workgroups or 0)
-        self._use_graph, self._graph, self._images = use_graph, None, None
+        self._cache = _GraphCache(self, use_graph)
         # the members' 16-byte result records side by side in ONE block (`results` u8[n,16]): a caller that logs every step moves
         # a chain's results with one small copy; the members' `result` / `out_idx` / `out_val` become views into it (their own
         # captured graphs, which wrote the old records, are dropped)
@@ -593,7 +658,7 @@ class CenterBatchPipeline:
         for i, p in enumerate(pipes if own_results else []):
             p.result = self.results[i]
             p.out_idx, p.out_val = p.result[:8].view(torch.int64), p.result[8:12].view(F32)
-            p._graph = None
+            p._cache.clear()
             if hasattr(p, "ws"):
                 p.ws.out_idx, p.ws.out_val = p.out_idx, p.out_val
 
@@ -603,65 +668,26 @@ class CenterBatchPipeline:
                                                                for p in self.pipes)
 
     def _chain(self):
+        """enqueue the launches -> [(outputs, heads)] of the members, the tensors they write"""
         from .models.model import forward_decode_batch
-        p0 = self.pipes[0]
-        items = []
-        for p in self.pipes:
-            it = dict(encoder=p.encoder, pc=p.pc, pc_normal=p.nrm, feat=p.feat, idxs=p.idx, u_tr=p.u_tr, vote_range=p.cfg.vote_range)
-            if p.with_heads:
-                it["u_rot"] = p.u_rot
-            items.append(it)
-        outs = forward_decode_batch(items, p0.cfg.tr_num_bins, p0.cfg.rot_num_bins)
-        for p, (o, h) in zip(self.pipes, outs):
-            p.outputs, p.heads = o, h
+        pipes, p0 = self.pipes, self.pipes[0]
+        outs = forward_decode_batch(_decode_items(pipes, [p.feat for p in pipes], p0.with_heads), p0.cfg.tr_num_bins, p0.cfg.rot_num_bins)
         if self.vote_batch:
-            voting.vote_argmax_batch([dict(points=p.pc, outputs=p.outputs, point_idxs=p.idx, grid=p.grid, corner=p.corner, res=p.cfg.res,
-                                           out_idx=p.out_idx, out_val=p.out_val) for p in self.pipes],
-                                     p0.num_rots, p0.adaptive, accumulate=False, workgroups=self.vote_workgroups)
+            voting.vote_argmax_batch(_vote_items(pipes, [o for o, _ in outs]), p0.num_rots, p0.adaptive, accumulate=False,
+                                     workgroups=self.vote_workgroups)
         else:
-            for p in self.pipes:
-                voting.vote_argmax(p.pc, p.outputs, None, p.idx, p.grid, p.corner, p.cfg.res, p.num_rots, p.adaptive, p.out_idx, p.out_val,
+            for p, (o, _) in zip(pipes, outs):
+                voting.vote_argmax(p.pc, o, None, p.idx, p.grid, p.corner, p.cfg.res, p.num_rots, p.adaptive, p.out_idx, p.out_val,
                                    accumulate=False, workgroups=p.vote_workgroups)
+        return outs
 
     def run(self, check_weights=True):
-        """-> [(out_idx, out_val)] of the members (device tensors, as CenterPipeline.run returns them)"""
-        with torch.no_grad(), workspace_scope(id(self)):
-            if not self._use_graph:
-                self._chain()
-            else:
-                # the vote widths / member buffers the launches baked in are compared on every run (cheap), the weight images
-                # when asked: a moved image or a member's set_vote_workgroups() captures again
-                images = ((tuple(tuple(p._weight_images()) for p in self.pipes) if check_weights or self._graph is None else self._images[0]),
-                          self._capture_key())
-                if self._graph is not None and images != self._images:
-                    self._graph = None
-                if self._graph is None:
-                    s = torch.cuda.Stream(device=self.device)
-                    s.wait_stream(torch.cuda.current_stream(self.device))
-                    with torch.cuda.stream(s):
-                        self._chain()
-                        self._chain()
-                    torch.cuda.current_stream(self.device).wait_stream(s)
-                    self._graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(self._graph, capture_error_mode="thread_local"):
-                        self._chain()
-                    self._images = images
-                for p in self.pipes:
-                    p._await_images()
-                self._graph.replay()
-                for p in self.pipes:
-                    p._note_images_read()
+        """-> [(out_idx, out_val)] of the members (device tensors, as CenterPipeline.run returns them).  The vote widths / member
+        buffers the launches baked in are compared on every run (cheap), the weight images as `check_weights` says: a moved image,
+        a member's set_vote_workgroups() or an assigned `vote_workgroups` captures again."""
+        for p, (o, h) in zip(self.pipes, self._cache.run(self._chain, self.pipes, check_weights, self._capture_key())):
+            p.outputs, p.heads = o, h
         return [(p.out_idx, p.out_val) for p in self.pipes]
-
-    def release(self):
-        self._graph = None
-        release_scope(id(self))
-
-    def __del__(self):
-        try:
-            release_scope(id(self))
-        except Exception:
-            pass
 
 
 class PosePipeline(CenterPipeline):
@@ -687,7 +713,6 @@ class PosePipeline(CenterPipeline):
         # only: every head of every pair from the first pass, whose logits + decode-kernel fallback serves any configuration
         self._split_ok = encoder.fused_decode_supported(cfg.tr_num_bins, cfg.rot_num_bins)
         self.full_first = not self._split_ok
-        self._graphs = {}
 
     # Two captured forms of the same computation.  Split (the reference's own order, nocs/inference.py:182-256): the first MLP
     # pass decodes the two centre heads only, the survivors of the back-vote get a second pass for the orientation / scale heads
@@ -708,30 +733,21 @@ class PosePipeline(CenterPipeline):
             want = False
         if not self._split_ok:
             want = True
-        if want != self.full_first:
-            # a captured form owns the tensors its launches write: outputs / heads / feat are part of what is switched
-            self._graphs[self.full_first] = (self._graph, self._images, self.outputs, self.heads, self.feat)
-            self.full_first = want
-            self._graph, self._images, outputs, heads, feat = self._graphs.get(want, (None, self._images, None, None, None))
-            if self._graph is not None:
-                self.outputs, self.heads, self.feat = outputs, heads, feat
-
-    def release(self):
-        self._graphs = {}
-        super().release()
+        self.full_first = want      # (the next run returns the tensors this form's launches write: outputs / heads / feat)
 
     def _chain(self):
         self.with_heads = self.full_first
-        super()._chain()                          # (full first: self.heads = every pair's heads row, from the first pass)
+        outputs, heads, feat = super()._chain()   # (full first: heads = every pair's heads row, from the first pass)
         if not self.full_first:
-            self.heads = self.ws.heads
-        _enqueue_tail(self.ws, self.pc, self.nrm, self.idx32, self.outputs, self.heads, self.corner, self.cfg,
+            heads = self.ws.heads
+        _enqueue_tail(self.ws, self.pc, self.nrm, self.idx32, outputs, heads, self.corner, self.cfg,
                       self.dims, self.num_rots, self.angle_tol, self.max_rot_pairs, *self._sph,
                       shape=self.shape if self.dynamic else None,
-                      second_pass=None if self.full_first else (self.encoder, self.feat, self.idx, self.u_rot),
+                      second_pass=None if self.full_first else (self.encoder, feat, self.idx, self.u_rot),
                       idx64=self.idx if self.idx.dtype == torch.int64 else None,   # the tail's kernels take int32 indices: written
                                                                                   # by the back-vote launch unless the list is int32 already
                       rot_order=self.rot_order)
+        return outputs, heads, feat
 
     def run(self, rng=None, check_weights=True):
         super().run(check_weights)
@@ -765,7 +781,7 @@ class PosePipeline(CenterPipeline):
                                                     None, int(seed) & 0xFFFFFFFFFFFFFFFF, None, stream_ptr(self.device)), "cppf_sample_pairs")
 
 
-class PoseChain:
+class PoseChain(_Captured):
     """Up to 8 PosePipelines -- the instances of a frame on one HIP stream (the reference loops over them, nocs/inference.py:120) --
     replayed as ONE captured chain with the launches SHARED between the members: their point encoders one after the other, then ONE
     launch of the pair kernel for all pair lists (forward_decode_batch), ONE vote + ONE reduce launch (vote_argmax_batch) and the six
@@ -808,7 +824,7 @@ class PoseChain:
         self.pipes, self.device = pipes, p0.device
         self.vote_workgroups = int(vote_workgroups or 0)
         self.full_first = False
-        self._use_graph, self._graphs, self._owned, self.tensors = use_graph, {}, {}, None
+        self._cache, self.tensors = _GraphCache(self, use_graph), None     # tensors: outputs / heads / feat per member, of the last run
         self.staged = bool(staged)
         if self.staged:
             from .sharding import RECORD
@@ -847,40 +863,24 @@ class PoseChain:
         for pre in self.prestages:                                               # nocs/inference.py:131-142 (FrameRunner)
             if pre is not None:
                 pre()
-        feats = []            # (the members' own attributes are left alone: a member may also run on its own captured graph)
+        # (the members' own attributes are left alone: a member may also run on its own captured graph)
         # nocs/inference.py:180-181.  The shape-polymorphic members' encoders share three launches (search, convolution,
         # GlobalInfoProp for all of them: a cloud of 700-2000 points fills a quarter of the chip); others run one after the other.
         enc_members = [p for p in pipes if p.point_encoder is not None and p.dynamic]
-        batched = None
-        if len(enc_members) > 1 and not os.environ.get("CPPF_NO_POINT_BATCH"):      # (the knob: A/B measurements)
+        batched = len(enc_members) > 1 and not os.environ.get("CPPF_NO_POINT_BATCH")      # (the knob: A/B measurements)
+        if batched:
             from .models.model import point_encoder_forward_batch
-            batched = point_encoder_forward_batch([dict(encoder=p.point_encoder, pc=p.pc, nrm=p.nrm, n_dev=p.shape, out=p._feat_out,
-                                                        nbrs=p._nbrs, nbrs_ready=getattr(p, "nbrs_ready", False)) for p in enc_members])
-        for p in pipes:
-            if p.point_encoder is None:
-                feats.append(p.feat)
-            elif p.dynamic:
-                feats.append(p._feat_out if batched is not None else
-                             p.point_encoder.forward_dyn(p.pc, p.nrm, p.shape, out=p._feat_out, nbrs=p._nbrs,
-                                                         nbrs_ready=getattr(p, "nbrs_ready", False)))
-            else:
-                feats.append(p.point_encoder(p.pc[None], p.nrm[None])[0])
-        items = []
-        for p, f in zip(pipes, feats):
-            it = dict(encoder=p.encoder, pc=p.pc, pc_normal=p.nrm, feat=f, idxs=p.idx, u_tr=p.u_tr, vote_range=p.cfg.vote_range)
-            if self.full_first:
-                it["u_rot"] = p.u_rot
-            items.append(it)
+            point_encoder_forward_batch([dict(encoder=p.point_encoder, pc=p.pc, nrm=p.nrm, n_dev=p.shape, out=p._feat_out,
+                                              nbrs=p._nbrs, nbrs_ready=p.nbrs_ready) for p in enc_members])
+        feats = [p._feat_out if batched and p in enc_members else _point_features(p) for p in pipes]
         tables = []
-        outs = forward_decode_batch(items, p0.cfg.tr_num_bins, p0.cfg.rot_num_bins, tables_out=tables)          # :182-188
+        outs = forward_decode_batch(_decode_items(pipes, feats, self.full_first), p0.cfg.tr_num_bins, p0.cfg.rot_num_bins,
+                                    tables_out=tables)                                                           # :182-188
         outputs = [o for o, _ in outs]
         heads = [(h if self.full_first else p.ws.heads) for p, (_, h) in zip(pipes, outs)]
-        self.tensors = [dict(outputs=o, heads=h, feat=f) for o, h, f in zip(outputs, heads, feats)]
         vws = []
-        voting.vote_argmax_batch([dict(points=p.pc, outputs=o, point_idxs=p.idx, corner=p.corner, res=p.cfg.res, out_idx=p.out_idx,
-                                       out_val=p.out_val, **(dict(grid=p.grid_flat, shape=p.shape, many_tiles=p.many_tiles) if p.dynamic
-                                                             else dict(grid=p.grid))) for p, o in zip(pipes, outputs)],
-                                 p0.num_rots, p0.adaptive, accumulate=False, workgroups=self.vote_workgroups, workspaces_out=vws)   # :191-208
+        voting.vote_argmax_batch(_vote_items(pipes, outputs), p0.num_rots, p0.adaptive, accumulate=False,
+                                 workgroups=self.vote_workgroups, workspaces_out=vws)                            # :191-208
         arr = (_lib.PoseTailItem * len(pipes))()
         keep = []
         sph32, sph64, sorted_y = p0._sph
@@ -915,6 +915,7 @@ class PoseChain:
                                         p0.encoder.out_dim, p0.cfg.tr_num_bins, p0.cfg.rot_num_bins, p0.num_rots, sph32.data_ptr(),
                                         sph64.data_ptr(), sph32.shape[0], sorted_y, thr, p0.max_rot_pairs, stream_ptr(self.device))
         _lib.check(rc, "cppf_pose_tail_batch")                                                                  # :209-303,335
+        return [dict(outputs=o, heads=h, feat=f) for o, h, f in zip(outputs, heads, feats)]
 
     def _key(self):
         return (self.vote_workgroups,) + tuple((p.idx.data_ptr(), p.pc.data_ptr()) for p in self.pipes)
@@ -939,41 +940,13 @@ class PoseChain:
                         int(seeds[i]) & 0xFFFFFFFFFFFFFFFF, int(ids[i]))
         copy_words(self.desc, host, self.device)          # (kernels, not copy engines: see cppf_copy_words)
         ev.record(torch.cuda.current_stream(self.device))
-        self.run_async(None, check_weights, eager=not capture and self._graphs.get(self.full_first, (None, None))[0] is None)
+        self.run_async(None, check_weights, eager=not capture and self._graph is None)
         copy_words(rows_out, self.records[:rows_out.shape[0]], self.device)
 
     def run_async(self, records_out, check_weights=True, eager=False):
         """Replay the chain and copy every member's 21-double record into records_out[i] (device f64[21]) on the current stream
         (records_out None: no copies).  eager: launch instead of capturing / replaying."""
-        with torch.no_grad(), workspace_scope(id(self)):
-            if not self._use_graph or eager:
-                self._chain()
-            else:
-                form = self.full_first
-                graph, images = self._graphs.get(form, (None, None))
-                now = ((tuple(tuple(p._weight_images()) for p in self.pipes) if check_weights or graph is None else
-                        (tuple(tuple(p._image_ptrs()) for p in self.pipes) if check_weights is None else images[0])), self._key())
-                if graph is not None and now != images:
-                    graph = None
-                if graph is None:
-                    s = torch.cuda.Stream(device=self.device)
-                    s.wait_stream(torch.cuda.current_stream(self.device))
-                    with torch.cuda.stream(s):
-                        self._chain()
-                        self._chain()
-                    torch.cuda.current_stream(self.device).wait_stream(s)
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                        self._chain()
-                    # (a captured form owns the tensors its launches write: `tensors` = outputs / heads / feat per member of THIS form)
-                    self._graphs[form] = (graph, now)
-                    self._owned[form] = self.tensors
-                self.tensors = self._owned[form]
-                for p in self.pipes:
-                    p._await_images()
-                graph.replay()
-                for p in self.pipes:
-                    p._note_images_read()
+        self.tensors = self._cache.run(self._chain, self.pipes, check_weights, self._key(), self.full_first, eager)
         for p, r in zip(self.pipes, records_out or ()):
             r.copy_(p.ws.rec, non_blocking=True)
 
@@ -1001,14 +974,8 @@ class PoseChain:
             self.full_first = False
 
     def release(self):
-        self._graphs, self._owned, self.tensors = {}, {}, None
-        release_scope(id(self))
-
-    def __del__(self):
-        try:
-            release_scope(id(self))
-        except Exception:
-            pass
+        self.tensors = None
+        super().release()
 
 
 def assemble_batch(recs, cfgs, object_ids, n_cols):

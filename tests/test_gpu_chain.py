@@ -73,6 +73,41 @@ def test_chain_records_equal_member_pipelines_and_oracle(oracle, golden, dev, dy
         PoseChain([pipes[0], pipes[0]])
 
 
+def test_staged_chain_first_eager_run_is_ordered_against_weight_image_rebuilds(golden, dev):
+    """a staged chain whose combination has no graph yet, run with run_staged(capture=False), launches eagerly -- and like a replay
+    it waits for a weight image rebuilt on another stream and registers as its reader: _await_images / _note_images_read once per
+    member (the calls are counted; the race itself is not produced).  Its records equal the captured run's bit for bit."""
+    from cppf_amd import sharding
+    sph = golden("sphere.npz")["pts"]
+    enc = make_encoder(seeded_sd(0, 4.0), dev)
+    specs = [("bottle", 1500, 40, 1), ("mug", 1200, 50, 2), ("camera", 900, 64, 4)]
+    pipes, data = make_members(dev, sph, enc, specs, True)
+    chain = PoseChain(pipes, staged=True)
+    objs = [{k: torch.from_numpy(d["ob"][k]).to(dev) for k in ("pc", "normals", "feat")} for d in data]
+    calls = []
+
+    def counted(j, name, fn):
+        def wrapper():
+            calls.append((j, name))
+            return fn()
+        return wrapper
+    for j, p in enumerate(pipes):
+        p._await_images = counted(j, "await", p._await_images)
+        p._note_images_read = counted(j, "note", p._note_images_read)
+    once_each = sorted((j, name) for j in range(len(pipes)) for name in ("await", "note"))
+    rows = []
+    for capture in (False, True):
+        del calls[:]
+        out = torch.zeros((len(pipes), sharding.RECORD), dtype=torch.float64, device=dev)
+        chain.run_staged(objs, [7, 8, 9], [0, 1, 2], out, capture=capture)
+        torch.cuda.synchronize()
+        assert sorted(calls) == once_each, (capture, calls)
+        assert (chain._graph is not None) == capture
+        rows.append(out.cpu().numpy())
+    assert (rows[0][:, 12] >= 0).all() and (rows[0][:, 14] > 0).all() and rows[0][:, 15].tolist() == [0, 1, 2]
+    np.testing.assert_array_equal(rows[0], rows[1])
+
+
 @pytest.mark.parametrize("n_bins,gain", [(3600, 12.0), (37, 1.0), (480, 12.0)])
 def test_chain_sphere_count_equals_member_pipelines_on_other_spheres(dev, n_bins, gain):
     """the chain's orientation count (rot_sphere_band_even_body: a block owns a contiguous share of the survivors) against the
