@@ -182,6 +182,7 @@ class VoteItem(C.Structure):
 
 
 ABI_VERSION = 4     # include/cppf.h CPPF_ABI_VERSION: records assembled on the device (CppfPoseTailItem.record_out), cppf_stage_batch
+EUNSUPPORTED, ENONFINITE, ECAPACITY = -3, -4, -5    # include/cppf.h CPPF_E*: the return codes a caller reads before check()
 
 
 class CppfError(RuntimeError):

@@ -1,4 +1,5 @@
 """torch plumbing for the C ABI: pointer extraction, argument checks, stream, scratch cache."""
+import ctypes as C
 import threading
 
 import numpy as np
@@ -13,20 +14,68 @@ def stream_ptr(device=None):
     return torch.cuda.current_stream(device).cuda_stream
 
 
+class scratch:
+    """a scratch buffer (uint8 tensor) as ONE argument of call() / field of fill(): it expands to the ABI's (void* workspace,
+    size_t workspace_bytes) pair"""
+
+    def __init__(self, buf):
+        self.buf = buf
+
+
+def _arg(a):
+    """what ctypes is handed for one argument: the address of a tensor or of a C-contiguous numpy array, 0 / 1 for a bool; None
+    (NULL), Python numbers and ctypes arrays / pointers pass unchanged"""
+    if isinstance(a, torch.Tensor):
+        return a.data_ptr()
+    if isinstance(a, np.ndarray):
+        if not a.flags.c_contiguous:
+            raise ValueError("a numpy array passed to the C ABI must be C-contiguous")
+        return a.ctypes.data
+    return int(a) if isinstance(a, bool) else a
+
+
+def call(name, device, *args, ok=()):
+    """The one path into the C ABI: `name`(*args, stream) with `device` current, on its current stream (device None: a host-only
+    entry point, which takes no stream); raises CppfError naming `name` on a non-zero return unless the code is listed in `ok`.
+    Returns the code."""
+    fn, conv = getattr(_lib.lib(), name), []
+    for a in args:              # (`args` keeps every tensor / array referenced until the call has returned)
+        conv += [a.buf.data_ptr(), a.buf.nbytes] if isinstance(a, scratch) else [_arg(a)]
+    if device is None:
+        rc = fn(*conv)
+    else:
+        with torch.cuda.device(device):
+            rc = fn(*conv, stream_ptr(device))
+    if rc not in ok:
+        _lib.check(rc, name)
+    return rc
+
+
+def fill(item, **fields):
+    """set fields of a ctypes item struct (_lib.*Item) with the conversion of call(); field=scratch(buf) also sets field_bytes"""
+    known = dict(item._fields_)
+    for k, v in fields.items():
+        if isinstance(v, scratch):
+            fill(item, **{k: v.buf, k + "_bytes": v.buf.nbytes})
+            continue
+        if k not in known:
+            raise AttributeError(f"{type(item).__name__} has no field {k!r}")
+        setattr(item, k, _arg(v))
+    return item
+
+
 def copy_words(dst, src, device):
     """dst <- src (tensors of 8-byte elements, contiguous, the same number of elements; either may be PINNED host memory) by a kernel
     of the current stream of `device`, not by a copy engine (cppf_copy_words: small copies on the SDMA queues can wait behind another
     stream's transfers)"""
     n = dst.numel()
     assert src.numel() == n and dst.element_size() == 8 and src.element_size() == 8 and dst.is_contiguous() and src.is_contiguous()
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().cppf_copy_words(dst.data_ptr(), src.data_ptr(), n, stream_ptr(device)), "cppf_copy_words")
+    call("cppf_copy_words", device, dst, src, n)
 
 
 def gather_words(dst, srcs, device):
     """dst[r] <- srcs[r] (dst: [len(srcs), W] of 8-byte elements or an equivalent view; srcs: device tensors of at least W such words
     each, in different allocations) with ONE launch on the current stream (cppf_gather_words) instead of a small copy per row"""
-    import ctypes as C
     n = len(srcs)
     if n == 0:
         return
@@ -35,8 +84,7 @@ def gather_words(dst, srcs, device):
     for i in range(0, n, 32):
         part = srcs[i:i + 32]
         ptrs = (C.c_void_p * len(part))(*[t_.data_ptr() for t_ in part])
-        with torch.cuda.device(device):
-            _lib.check(_lib.lib().cppf_gather_words(len(part), ptrs, words, dst.data_ptr() + i * words * 8, stream_ptr(device)), "cppf_gather_words")
+        call("cppf_gather_words", device, len(part), ptrs, words, dst.data_ptr() + i * words * 8)
 
 
 _lane_cache = {}
@@ -167,10 +215,8 @@ def workspace(nbytes, device, tag="ws", zero=False):
     buf = _ws_cache.get(key)
     if buf is None or buf.numel() < nbytes:
         n = max(int(nbytes), 256)
+        buf = torch.empty(n, dtype=torch.uint8, device=device)
         if zero:
-            buf = torch.empty(n, dtype=torch.uint8, device=device)
             buf[:min(n, int(_lib.lib().cppf_vote_workspace_init_bytes()))].zero_()
-        else:
-            buf = torch.empty(n, dtype=torch.uint8, device=device)
         _ws_cache[key] = buf
     return buf

@@ -243,13 +243,9 @@ class BatchPoseRunner:
                     if obj.get(k) is not None:
                         o[k] = obj[k].to(device=self.device, dtype=torch.float32).contiguous()
                 if o.get("dims") is None:            # cppf_grid_setup: the arithmetic the chain's own grid set-up uses (a torch
-                    from . import _lib               # division by a scalar multiplies by its reciprocal: other dims at the edges)
-                    from ._torch_util import stream_ptr
-                    cd = torch.empty(8, dtype=torch.int32, device=self.device)
-                    with torch.cuda.device(self.device):
-                        _lib.check(_lib.lib().cppf_grid_setup(o["pc"].data_ptr(), o["pc"].shape[0], float(np.float32(obj["cfg"].res)),
-                                                              cd[:3].view(torch.float32).data_ptr(), cd[4:7].data_ptr(),
-                                                              stream_ptr(self.device)), "cppf_grid_setup")
+                    from ._torch_util import call    # division by a scalar multiplies by its reciprocal: other dims at the edges)
+                    cd = torch.empty(8, dtype=torch.int32, device=self.device)  # corner f32[3] (bits) | pad | dims i32[3] | pad
+                    call("cppf_grid_setup", self.device, o["pc"], o["pc"].shape[0], float(np.float32(obj["cfg"].res)), cd[:3], cd[4:7])
                     o["dims"] = tuple(int(v) for v in cd[4:7].tolist())
             else:
                 _, o["dims"] = grid_shape(obj["pc"], obj["cfg"].res)

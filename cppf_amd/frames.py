@@ -39,13 +39,10 @@ def draw_pairs(seed, i, n_pairs, dev, n_points, idx=None, u=None):
     torch.multinomial's draws, :186,250) of instance i of a frame, drawn on the device by cppf_sample_pairs: a function of
     (seed, i, pair index) alone, so the eager loop (N known on the host) and a captured chain (N in a device record, the seed in
     device memory) draw the same numbers."""
-    from . import _lib
-    from ._torch_util import stream_ptr
+    from ._torch_util import call
     idx = torch.empty((n_pairs, 2), dtype=torch.int64, device=dev) if idx is None else idx
     u = torch.empty((2, n_pairs, 2), dtype=torch.float32, device=dev) if u is None else u
-    with torch.cuda.device(dev):
-        _lib.check(_lib.lib().cppf_sample_pairs(idx.data_ptr(), u[0].data_ptr(), u[1].data_ptr(), n_pairs, int(n_points), None,
-                                                pair_seed(seed, i), None, stream_ptr(dev)), "cppf_sample_pairs")
+    call("cppf_sample_pairs", dev, idx, u[0], u[1], n_pairs, int(n_points), None, pair_seed(seed, i), None)
     return idx, u
 
 
@@ -152,7 +149,7 @@ class FrameRunner:
         tight mask) until an instance of the category came back with "shape beyond the launch's capacities" -- from then on the
         category's members are of the many-tile class (any grid of up to 64 tiles)."""
         from . import _lib
-        from ._torch_util import stream_ptr
+        from ._torch_util import call, scratch
         from .inference import PosePipeline
         cap = max(self.cap_bucket, 1 << int(np.ceil(np.log2(max(n_mask, 1)))))
         key = (cat, cap, cat in self._many_tile_cats)
@@ -174,8 +171,7 @@ class FrameRunner:
         cfg, H, W = self.cfgs[cat], self._hw[0], self._hw[1]
         pipe = PosePipeline(self.encoders[cat], cfg, cap, self.n_pairs, key[2], self.device, self.sphere, num_rots=self.num_rots,
                             angle_tol=self.angle_tol, point_encoder=self.point_encoders[cat], dynamic=True)
-        L = _lib.lib()
-        ws = torch.empty(int(L.cppf_frame_cloud_workspace_bytes(H, W, cap, cfg.knn)), dtype=torch.uint8, device=self.device)
+        ws = torch.empty(int(_lib.lib().cppf_frame_cloud_workspace_bytes(H, W, cap, cfg.knn)), dtype=torch.uint8, device=self.device)
         if not self._free_rows:                       # (more live members than rows: only when the bound yielded to a huge frame)
             raise RuntimeError("FrameRunner: no free member record; raise max_members")
         row = self._free_rows.pop()
@@ -185,18 +181,14 @@ class FrameRunner:
         # reuses them instead of searching again (the stage writes them straight into the pipeline's neighbour buffer)
         share = pipe.point_encoder is not None and pipe.point_encoder.k == cfg.knn
         pipe.nbrs_ready = share
-        nbrs_ptr = pipe._nbrs.data_ptr() if share else None
+        nbrs = pipe._nbrs if share else None
 
         def prestage():
-            with torch.cuda.device(dev):
-                _lib.check(L.cppf_frame_cloud_dyn_bit(depth.data_ptr(), 1, labels.data_ptr(), 4, slot.data_ptr(), H, W, kinv.ctypes.data,
-                                                      1000.0, float(cfg.res), cfg.knn, cfg.knn + 1, cap, pipe.pc.data_ptr(),
-                                                      pipe.nrm.data_ptr(), pipe.corner.data_ptr(), pipe.shape.data_ptr(), nbrs_ptr,
-                                                      ws.data_ptr(), ws.numel(), stream_ptr(dev)), "cppf_frame_cloud_dyn_bit")
-                # pairs and bin uniforms: N from the shape record the stage just wrote, the key from the member's record
-                _lib.check(L.cppf_sample_pairs(pipe.idx.data_ptr(), pipe.u_tr.data_ptr(), pipe.u_rot.data_ptr(), pipe.idx.shape[0], 1,
-                                               pipe.shape.data_ptr(), 0, slot.data_ptr() + 8, stream_ptr(dev)), "cppf_sample_pairs")
-        mem = dict(pipe=pipe, pre=prestage, slot=slot, row=row, ws=ws, key=key, cfg=cfg, cap=cap, nbrs_ptr=nbrs_ptr)
+            call("cppf_frame_cloud_dyn_bit", dev, depth, 1, labels, 4, slot, H, W, kinv, 1000.0, float(cfg.res), cfg.knn, cfg.knn + 1, cap,
+                 pipe.pc, pipe.nrm, pipe.corner, pipe.shape, nbrs, scratch(ws))
+            # pairs and bin uniforms: N from the shape record the stage just wrote, the key from the member's record
+            call("cppf_sample_pairs", dev, pipe.idx, pipe.u_tr, pipe.u_rot, pipe.idx.shape[0], 1, pipe.shape, 0, slot.data_ptr() + 8)
+        mem = dict(pipe=pipe, pre=prestage, slot=slot, row=row, ws=ws, key=key, cfg=cfg, cap=cap, nbrs=nbrs)
         self._members[id(pipe)] = mem
         self._pool.setdefault(key, []).append(mem)
         return mem
@@ -204,24 +196,20 @@ class FrameRunner:
     def _batch_prestage(self, mems):
         """the frame stage of a chain's members in eight launches (cppf_frame_cloud_dyn_batch) instead of sixteen each: a callable
         for the head of their captured chain"""
-        import ctypes as C
         from . import _lib
-        from ._torch_util import stream_ptr
-        L, dev, H, W = _lib.lib(), self.device, self._hw[0], self._hw[1]
+        from ._torch_util import call, fill, scratch
+        dev, H, W = self.device, self._hw[0], self._hw[1]
         depth, labels, kinv = self._depth, self._labels, self.kinv
         arr = (_lib.FrameCloudItem * len(mems))()
         for a, m in zip(arr, mems):
             pipe, cfg = m["pipe"], m["cfg"]
-            a.label_bit_dev, a.seed_dev = m["slot"].data_ptr(), m["slot"].data_ptr() + 8
-            a.pc_out, a.nrm_out, a.corner_out, a.shape_out = pipe.pc.data_ptr(), pipe.nrm.data_ptr(), pipe.corner.data_ptr(), pipe.shape.data_ptr()
-            a.nbrs_out, a.idx, a.u_tr, a.u_rot = m["nbrs_ptr"], pipe.idx.data_ptr(), pipe.u_tr.data_ptr(), pipe.u_rot.data_ptr()
-            a.workspace, a.workspace_bytes, a.res, a.n_pairs = m["ws"].data_ptr(), m["ws"].numel(), float(cfg.res), pipe.idx.shape[0]
-            a.knn_k, a.k_min, a.n_cap, a.idx_is_i64 = cfg.knn, cfg.knn + 1, m["cap"], 1 if pipe.idx.dtype == torch.int64 else 0
+            fill(a, label_bit_dev=m["slot"], seed_dev=m["slot"].data_ptr() + 8, pc_out=pipe.pc, nrm_out=pipe.nrm, corner_out=pipe.corner,
+                 shape_out=pipe.shape, nbrs_out=m["nbrs"], idx=pipe.idx, u_tr=pipe.u_tr, u_rot=pipe.u_rot, workspace=scratch(m["ws"]),
+                 res=float(cfg.res), n_pairs=pipe.idx.shape[0], knn_k=cfg.knn, k_min=cfg.knn + 1, n_cap=m["cap"],
+                 idx_is_i64=pipe.idx.dtype == torch.int64)
 
         def prestage():
-            with torch.cuda.device(dev):
-                _lib.check(L.cppf_frame_cloud_dyn_batch(len(mems), C.cast(arr, C.c_void_p), depth.data_ptr(), 1, labels.data_ptr(), 4, H, W,
-                                                        kinv.ctypes.data, 1000.0, stream_ptr(dev)), "cppf_frame_cloud_dyn_batch")
+            call("cppf_frame_cloud_dyn_batch", dev, len(mems), arr, depth, 1, labels, 4, H, W, kinv, 1000.0)
         return prestage
 
     def _chain_for(self, pipes, pres, busy):

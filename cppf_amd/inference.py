@@ -20,13 +20,14 @@ surviving pairs only, like the reference's, through cppf_pair_mlp_decode_sel), a
 10 000-pair subset of :277-280 is the first `max_rot_pairs` survivors in pair order (pairs are
 i.i.d. uniform, so a prefix is distributed exactly like a shuffled subset).
 """
+import ctypes as C
 import os
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._torch_util import copy_words, release_scope, require_cuda, stream_ptr, workspace, workspace_scope
+from ._torch_util import call, copy_words, fill, release_scope, require_cuda, scratch, workspace, workspace_scope
 from .models import voting
 
 F32, I32 = torch.float32, torch.int32
@@ -39,11 +40,10 @@ def grid_shape(pc_host, res):
     if a.dtype == np.float32 and a.ndim == 2 and a.shape[1] == 3 and a.shape[0] > 0 and a.flags.c_contiguous:
         corners = np.empty((2, 3), np.float32)
         dims = np.empty(3, np.int32)
-        rc = _lib.lib().cppf_host_grid_shape(a.ctypes.data, a.shape[0], float(np.float32(res)), corners.ctypes.data, dims.ctypes.data)
-        if rc == 0:
-            return corners, (int(dims[0]), int(dims[1]), int(dims[2]))
-        if rc == -4:      # CPPF_ENONFINITE; the reference fails at np.zeros(grid_res) with the dims such a cloud gives (:196)
+        rc = call("cppf_host_grid_shape", None, a, a.shape[0], float(np.float32(res)), corners, dims, ok=(_lib.ENONFINITE,))
+        if rc == _lib.ENONFINITE:      # the reference fails at np.zeros(grid_res) with the dims such a cloud gives (:196)
             raise ValueError("the cloud holds NaN / inf coordinates: no vote grid can be laid over it")
+        return corners, (int(dims[0]), int(dims[1]), int(dims[2]))
     t = np.ascontiguousarray(np.asarray(pc_host, dtype=np.float32).T)    # [3,N]: numpy reduces the long axis 20x faster than axis 0 of [N,3]
     corners = np.stack([t.min(1), t.max(1)])
     if not np.isfinite(corners).all():
@@ -451,8 +451,6 @@ def estimate_pose(encoder, pc, pc_normal, feat, point_idxs, u_tr, u_rot, cfg, sp
     argmax (flat grid index), peak, n_surv, counts_up/right (i32[S])."""
     require_cuda()
     dev = pc.device
-    L = _lib.lib()
-    st = stream_ptr(dev)
     P = point_idxs.shape[0]
     if pc_host is None:
         pc_host = pc.detach().cpu().numpy()
@@ -494,72 +492,52 @@ def _enqueue_tail(ws, pc, pc_normal, idx32, outputs, heads, corner, cfg, dims, n
     None = the first `max_rot_pairs` survivors."""
     dev = pc.device
     L = _lib.lib()
-    st = stream_ptr(dev)
     P, S = idx32.shape[0], sph32_d.shape[0]
-    with torch.cuda.device(dev):
-        # the vote's workspace (same scope, same tag as models/voting.py): its rotation table is reused by the back-vote
-        vws = workspace(256, dev, "vote_dyn" if shape is not None else "vote")
-        vws_ptr = vws.data_ptr() if vws.numel() >= 32768 else None
-        shape_ptr = None if shape is None else shape.data_ptr()
-        gx, gy, gz = (1, 1, 1) if shape is not None else dims
-        # T = corner + unravel(argmax) * res (:209-210); the same launch zeroes the record, the bin counts, the chunk counts
-        # and the ticket of the launches below
-        _lib.check(L.cppf_pose_tail_begin(ws.out_idx.data_ptr(), corner.data_ptr(), float(cfg.res), gy, gz, shape_ptr,
-                                          ws.T64.data_ptr(), ws.T32.data_ptr(), ws.out_val.data_ptr(),
-                                          ws.rec[19:21].data_ptr(), ws._tail0.data_ptr(), ws._tail0.numel(), st),
-                   "cppf_pose_tail_begin")
-        # back-vote filter (:216-231) --------------------------------------------------------------
-        # mask only: the offsets themselves (:220-228) are consumed nowhere else, so no buffer is zeroed or written
-        tol = float(np.float32(3 * cfg.res))
-        fused = 0 < P <= 8192 * 1024
-        if idx64 is not None and not fused:
-            idx32.copy_(idx64)
-        if fused:                    # survivors counted per chunk by the back-vote itself: the compaction is one launch
-            if idx64 is not None:
-                _lib.check(L.cppf_backvote_count64(pc.data_ptr(), outputs.data_ptr(), idx64.data_ptr(), idx32.data_ptr(),
-                                                   corner.data_ptr(), float(cfg.res), P, num_rots, gx, gy, gz, shape_ptr,
-                                                   ws.T32.data_ptr(), tol, ws.mask.data_ptr(), ws.chunk_counts.data_ptr(),
-                                                   vws_ptr, st), "cppf_backvote_count64")
-            else:
-                _lib.check(L.cppf_backvote_count(pc.data_ptr(), outputs.data_ptr(), idx32.data_ptr(), corner.data_ptr(),
-                                                 float(cfg.res), P, num_rots, gx, gy, gz, shape_ptr, ws.T32.data_ptr(), tol,
-                                                 ws.mask.data_ptr(), ws.chunk_counts.data_ptr(), vws_ptr, st),
-                           "cppf_backvote_count")
-            _lib.check(L.cppf_compact_scatter(ws.mask.data_ptr(), P, ws.chunk_counts.data_ptr(), ws.surv.data_ptr(),
-                                              ws.count.data_ptr(), st), "cppf_compact_scatter")
+    # the vote's workspace (same scope, same tag as models/voting.py): its rotation table is reused by the back-vote
+    vws = workspace(256, dev, "vote_dyn" if shape is not None else "vote")
+    vws = vws if vws.numel() >= 32768 else None
+    gx, gy, gz = (1, 1, 1) if shape is not None else dims
+    # T = corner + unravel(argmax) * res (:209-210); the same launch zeroes the record, the bin counts, the chunk counts
+    # and the ticket of the launches below
+    call("cppf_pose_tail_begin", dev, ws.out_idx, corner, float(cfg.res), gy, gz, shape, ws.T64, ws.T32, ws.out_val, ws.rec[19:21],
+         scratch(ws._tail0))
+    # back-vote filter (:216-231) --------------------------------------------------------------
+    # mask only: the offsets themselves (:220-228) are consumed nowhere else, so no buffer is zeroed or written
+    tol = float(np.float32(3 * cfg.res))
+    fused = 0 < P <= 8192 * 1024
+    if idx64 is not None and not fused:
+        idx32.copy_(idx64)
+    if fused:                    # survivors counted per chunk by the back-vote itself: the compaction is one launch
+        if idx64 is not None:
+            call("cppf_backvote_count64", dev, pc, outputs, idx64, idx32, corner, float(cfg.res), P, num_rots, gx, gy, gz, shape, ws.T32,
+                 tol, ws.mask, ws.chunk_counts, vws)
         else:
-            _lib.check(L.cppf_backvote_ws(pc.data_ptr(), outputs.data_ptr(), None, idx32.data_ptr(), corner.data_ptr(),
-                                          float(cfg.res), P, num_rots, gx, gy, gz, shape_ptr, ws.T32.data_ptr(), tol,
-                                          ws.mask.data_ptr(), vws_ptr, st), "cppf_backvote_ws")
-            cws = workspace(L.cppf_compact_workspace_bytes(P), dev, "compact")
-            _lib.check(L.cppf_compact_mask(ws.mask.data_ptr(), P, ws.surv.data_ptr(), ws.count.data_ptr(),
-                                           cws.data_ptr(), cws.numel(), st), "cppf_compact_mask")
-        if second_pass is not None:                                          # :236-256, survivors only
-            enc2, feat2, idxs2, u_rot2 = second_pass
-            enc2.forward_decode_sel(pc, pc_normal, feat2, idxs2, u_rot2, ws.surv, ws.count, heads, max_sel=P,
-                                    tr_num_bins=cfg.tr_num_bins, rot_num_bins=cfg.rot_num_bins)
-        # orientation (:259-303) and scale (:335) ---------------------------------------------------
-        # heads row = {theta_up, theta_right, aux_up, aux_right, sx, sy, sz, 0}: both directions' candidates are counted in
-        # one launch; np.argmax(counts), sphere_pts[...] (:283-284), the sign sums (:287-301) and the scale sums in another
-        thr = float(np.float32(np.cos(angle_tol / 180 * np.pi)))
-        n_dirs = 2 if cfg.regress_right else 1
-        if rot_order is None:
-            _lib.check(L.cppf_rot_sphere_count_dirs(pc.data_ptr(), heads.data_ptr(), 8, 1, n_dirs, idx32.data_ptr(),
-                                                    ws.surv.data_ptr(), ws.count.data_ptr(), P, max_rot_pairs, num_rots,
-                                                    sph32_d.data_ptr(), S, thr, sorted_y, ws.counts.data_ptr(), S, st),
-                       "cppf_rot_sphere_count_dirs")
-        else:
-            _lib.check(L.cppf_rot_sphere_count_dirs_order(pc.data_ptr(), heads.data_ptr(), 8, 1, n_dirs, idx32.data_ptr(),
-                                                          ws.surv.data_ptr(), ws.count.data_ptr(), P, rot_order.data_ptr(),
-                                                          rot_order.numel(), max_rot_pairs, num_rots, sph32_d.data_ptr(), S,
-                                                          thr, sorted_y, ws.counts.data_ptr(), S, st),
-                       "cppf_rot_sphere_count_dirs_order")
-        pws = workspace(L.cppf_pose_sums_workspace_bytes(), dev, "pose_sums")
-        _lib.check(L.cppf_pose_sums(pc.data_ptr(), pc_normal.data_ptr(), idx32.data_ptr(), ws.surv.data_ptr(),
-                                    ws.count.data_ptr(), P, heads.data_ptr() + 4 * 2, 8, n_dirs, ws.counts.data_ptr(), S, S,
-                                    sph64_d.data_ptr(), heads.data_ptr() + 4 * 4, 8, ws.best_idx.data_ptr(),
-                                    ws.best_dir.data_ptr(), ws.sign.data_ptr(), ws.scale.data_ptr(), pws.data_ptr(),
-                                    pws.numel(), ws.ticket.data_ptr(), st), "cppf_pose_sums")
+            call("cppf_backvote_count", dev, pc, outputs, idx32, corner, float(cfg.res), P, num_rots, gx, gy, gz, shape, ws.T32, tol,
+                 ws.mask, ws.chunk_counts, vws)
+        call("cppf_compact_scatter", dev, ws.mask, P, ws.chunk_counts, ws.surv, ws.count)
+    else:
+        call("cppf_backvote_ws", dev, pc, outputs, None, idx32, corner, float(cfg.res), P, num_rots, gx, gy, gz, shape, ws.T32, tol,
+             ws.mask, vws)
+        cws = workspace(L.cppf_compact_workspace_bytes(P), dev, "compact")
+        call("cppf_compact_mask", dev, ws.mask, P, ws.surv, ws.count, scratch(cws))
+    if second_pass is not None:                                          # :236-256, survivors only
+        enc2, feat2, idxs2, u_rot2 = second_pass
+        enc2.forward_decode_sel(pc, pc_normal, feat2, idxs2, u_rot2, ws.surv, ws.count, heads, max_sel=P,
+                                tr_num_bins=cfg.tr_num_bins, rot_num_bins=cfg.rot_num_bins)
+    # orientation (:259-303) and scale (:335) ---------------------------------------------------
+    # heads row = {theta_up, theta_right, aux_up, aux_right, sx, sy, sz, 0}: both directions' candidates are counted in
+    # one launch; np.argmax(counts), sphere_pts[...] (:283-284), the sign sums (:287-301) and the scale sums in another
+    thr = float(np.float32(np.cos(angle_tol / 180 * np.pi)))
+    n_dirs = 2 if cfg.regress_right else 1
+    if rot_order is None:
+        call("cppf_rot_sphere_count_dirs", dev, pc, heads, 8, 1, n_dirs, idx32, ws.surv, ws.count, P, max_rot_pairs, num_rots, sph32_d, S,
+             thr, sorted_y, ws.counts, S)
+    else:
+        call("cppf_rot_sphere_count_dirs_order", dev, pc, heads, 8, 1, n_dirs, idx32, ws.surv, ws.count, P, rot_order, rot_order.numel(),
+             max_rot_pairs, num_rots, sph32_d, S, thr, sorted_y, ws.counts, S)
+    pws = workspace(L.cppf_pose_sums_workspace_bytes(), dev, "pose_sums")
+    call("cppf_pose_sums", dev, pc, pc_normal, idx32, ws.surv, ws.count, P, heads.data_ptr() + 4 * 2, 8, n_dirs, ws.counts, S, S, sph64_d,
+         heads.data_ptr() + 4 * 4, 8, ws.best_idx, ws.best_dir, ws.sign, ws.scale, scratch(pws), ws.ticket)
     # (T64, best_dir, sign, scale, arg-max index and value were written into ws.rec by the kernels above)
 
 
@@ -776,9 +754,8 @@ class PosePipeline(CenterPipeline):
         n = int(n_points) if n_points is not None else n
         if isinstance(seed, torch.Generator):
             seed = seed.initial_seed()
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().cppf_sample_pairs(self.idx.data_ptr(), self.u_tr.data_ptr(), self.u_rot.data_ptr(), self.idx.shape[0], n,
-                                                    None, int(seed) & 0xFFFFFFFFFFFFFFFF, None, stream_ptr(self.device)), "cppf_sample_pairs")
+        call("cppf_sample_pairs", self.device, self.idx, self.u_tr, self.u_rot, self.idx.shape[0], n, None, int(seed) & 0xFFFFFFFFFFFFFFFF,
+             None)
 
 
 class PoseChain(_Captured):
@@ -843,19 +820,13 @@ class PoseChain(_Captured):
         pipes = self.pipes
         arr = (_lib.StageItem * len(pipes))()
         for i, p in enumerate(pipes):
-            a = arr[i]
-            a.desc, a.pc, a.nrm, a.corner = self.desc[i].data_ptr(), p.pc.data_ptr(), p.nrm.data_ptr(), p.corner.data_ptr()
-            a.feat = p.feat.data_ptr() if p.point_encoder is None else None
-            a.shape = p.shape.data_ptr() if p.dynamic else None
-            a.idx, a.u_tr, a.u_rot = p.idx.data_ptr(), p.u_tr.data_ptr(), p.u_rot.data_ptr()
-            a.n_pairs, a.n_cap, a.F, a.res = p.idx.shape[0], p.pc.shape[0], p.feat.shape[1], float(np.float32(p.cfg.res))
-            a.idx_is_i64 = 1 if p.idx.dtype == torch.int64 else 0
-        with torch.cuda.device(self.device):
-            _lib.check(_lib.lib().cppf_stage_batch(len(pipes), arr, stream_ptr(self.device)), "cppf_stage_batch")
+            fill(arr[i], desc=self.desc[i], pc=p.pc, nrm=p.nrm, corner=p.corner, feat=p.feat if p.point_encoder is None else None,
+                 shape=p.shape if p.dynamic else None, idx=p.idx, u_tr=p.u_tr, u_rot=p.u_rot, n_pairs=p.idx.shape[0], n_cap=p.pc.shape[0],
+                 F=p.feat.shape[1], res=float(np.float32(p.cfg.res)), idx_is_i64=p.idx.dtype == torch.int64)
+        call("cppf_stage_batch", self.device, len(pipes), arr)
 
     def _chain(self):
         from .models.model import forward_decode_batch
-        import ctypes as C
         pipes, p0 = self.pipes, self.pipes[0]
         L = _lib.lib()
         if self.staged:                                                          # nocs/inference.py:177,194-196 for resident objects
@@ -885,36 +856,28 @@ class PoseChain(_Captured):
         keep = []
         sph32, sph64, sorted_y = p0._sph
         for i, p in enumerate(pipes):
-            ws, a = p.ws, arr[i]
+            ws = p.ws
             pws = workspace(L.cppf_pose_sums_workspace_bytes(), self.device, f"pose_sums{i}")
             packed = p.encoder._packed_weights(self.device)
-            a.pc, a.nrm, a.feat, a.idx32 = p.pc.data_ptr(), p.nrm.data_ptr(), feats[i].data_ptr(), p.idx32.data_ptr()
-            a.idx64 = p.idx.data_ptr() if p.idx.dtype == torch.int64 else None          # (None: the list is int32, idx32 is the input)
-            a.outputs, a.u_rot, a.heads, a.corner = outputs[i].data_ptr(), p.u_rot.data_ptr(), heads[i].data_ptr(), p.corner.data_ptr()
-            a.shape_dev = p.shape.data_ptr() if p.dynamic else None
-            a.argmax_idx, a.peak = p.out_idx.data_ptr(), p.out_val.data_ptr()
-            a.packed, a.mlp_workspace, a.mlp_workspace_bytes = packed.data_ptr(), tables[i].data_ptr(), tables[i].numel()
-            a.vote_workspace = vws[i].data_ptr() if vws[i].numel() >= 32768 else None
-            a.rec, a.T32, a.tail0, a.tail0_bytes = ws.rec.data_ptr(), ws.T32.data_ptr(), ws._tail0.data_ptr(), ws._tail0.numel()
-            a.mask, a.chunk_counts, a.surv, a.count = ws.mask.data_ptr(), ws.chunk_counts.data_ptr(), ws.surv.data_ptr(), ws.count.data_ptr()
-            a.counts, a.best_idx, a.ticket = ws.counts.data_ptr(), ws.best_idx.data_ptr(), ws.ticket.data_ptr()
-            a.sums_workspace, a.sums_workspace_bytes = pws.data_ptr(), pws.numel()
-            a.n_points, a.n_pairs = p.pc.shape[0], p.idx.shape[0]
-            a.res64, a.res, a.tol = float(p.cfg.res), float(p.cfg.res), float(np.float32(3 * p.cfg.res))
-            a.gx, a.gy, a.gz = (1, 1, 1) if p.dynamic else p.dims
-            a.n_dirs, a.second_pass = (2 if p.cfg.regress_right else 1), (0 if self.full_first else 1)
+            gx, gy, gz = (1, 1, 1) if p.dynamic else p.dims
+            # (idx64 None: the list is int32, idx32 is the input)
+            fill(arr[i], pc=p.pc, nrm=p.nrm, feat=feats[i], idx32=p.idx32, idx64=p.idx if p.idx.dtype == torch.int64 else None,
+                 outputs=outputs[i], u_rot=p.u_rot, heads=heads[i], corner=p.corner, shape_dev=p.shape if p.dynamic else None,
+                 argmax_idx=p.out_idx, peak=p.out_val, packed=packed, mlp_workspace=scratch(tables[i]),
+                 vote_workspace=vws[i] if vws[i].numel() >= 32768 else None, rec=ws.rec, T32=ws.T32, tail0=scratch(ws._tail0),
+                 mask=ws.mask, chunk_counts=ws.chunk_counts, surv=ws.surv, count=ws.count, counts=ws.counts, best_idx=ws.best_idx,
+                 ticket=ws.ticket, sums_workspace=scratch(pws), n_points=p.pc.shape[0], n_pairs=p.idx.shape[0], res64=float(p.cfg.res),
+                 res=float(p.cfg.res), tol=float(np.float32(3 * p.cfg.res)), gx=gx, gy=gy, gz=gz, n_dirs=2 if p.cfg.regress_right else 1,
+                 second_pass=not self.full_first)
             if self.staged:                      # the finished record, assembled by the last launch (:299-339)
-                a.record_out, a.object_id_dev = self.records[i].data_ptr(), self.desc[i].data_ptr() + 40
-                a.scale_mean = (C.c_double * 3)(*[float(v) for v in p.cfg.scale_mean])
-                a.regress_right = 1 if p.cfg.regress_right else 0
+                fill(arr[i], record_out=self.records[i], object_id_dev=self.desc[i].data_ptr() + 40,
+                     scale_mean=(C.c_double * 3)(*[float(v) for v in p.cfg.scale_mean]), regress_right=bool(p.cfg.regress_right))
             keep.append((pws, packed))
         dims = (C.c_int * len(p0.encoder.ppffcs))(*p0.encoder.ppffcs)
         thr = float(np.float32(np.cos(p0.angle_tol / 180 * np.pi)))
-        with torch.cuda.device(self.device):
-            rc = L.cppf_pose_tail_batch(len(pipes), C.cast(arr, C.c_void_p), feats[0].shape[1], dims, len(p0.encoder.ppffcs) - 1,
-                                        p0.encoder.out_dim, p0.cfg.tr_num_bins, p0.cfg.rot_num_bins, p0.num_rots, sph32.data_ptr(),
-                                        sph64.data_ptr(), sph32.shape[0], sorted_y, thr, p0.max_rot_pairs, stream_ptr(self.device))
-        _lib.check(rc, "cppf_pose_tail_batch")                                                                  # :209-303,335
+        call("cppf_pose_tail_batch", self.device, len(pipes), arr, feats[0].shape[1], dims, len(p0.encoder.ppffcs) - 1, p0.encoder.out_dim,
+             p0.cfg.tr_num_bins, p0.cfg.rot_num_bins, p0.num_rots, sph32, sph64, sph32.shape[0], sorted_y, thr,
+             p0.max_rot_pairs)                                                                                   # :209-303,335
         return [dict(outputs=o, heads=h, feat=f) for o, h, f in zip(outputs, heads, feats)]
 
     def _key(self):

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._torch_util import require_cuda, stream_ptr, workspace
+from ._torch_util import call, require_cuda, scratch, workspace
 from .config import CategoryConfig
 from .synthetic import philox4x32_10
 
@@ -89,13 +89,9 @@ def sample_surface_packed(verts, faces, vert_off, face_off, n_points, seed=0, fi
     pts = torch.empty((M, int(n_points), 3), dtype=torch.float64, device=dev)
     fid = torch.empty((M, int(n_points)), dtype=torch.int32, device=dev)
     status = torch.empty(M, dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    ws = workspace(L.cppf_surface_sample_workspace_bytes(M, int(face_off[-1])), dev, "surface_sample")
-    with torch.cuda.device(dev):
-        _lib.check(L.cppf_surface_sample_batch(verts.data_ptr(), faces.data_ptr(), vert_off.ctypes.data, face_off.ctypes.data, M,
-                                               int(n_points), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_mesh), pts.data_ptr(),
-                                               fid.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev)),
-                   "cppf_surface_sample_batch")
+    ws = workspace(_lib.lib().cppf_surface_sample_workspace_bytes(M, int(face_off[-1])), dev, "surface_sample")
+    call("cppf_surface_sample_batch", dev, verts, faces, vert_off, face_off, M, int(n_points), int(seed) & 0xFFFFFFFFFFFFFFFF,
+         int(first_mesh), pts, fid, status, scratch(ws))
     return pts, fid, status
 
 
@@ -135,12 +131,9 @@ def vote_stats_batch(points, n_pairs=100000, seed=0, first_mesh=0):
     dev = points.device
     stats = torch.empty((M, 6), dtype=torch.float64, device=dev)
     status = torch.empty(M, dtype=torch.int32, device=dev)
-    L = _lib.lib()
-    ws = workspace(L.cppf_mesh_vote_stats_workspace_bytes(M, N, int(n_pairs)), dev, "mesh_vote_stats")
-    with torch.cuda.device(dev):
-        _lib.check(L.cppf_mesh_vote_stats_batch(points.data_ptr(), M, N, int(n_pairs), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_mesh),
-                                                stats.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev)),
-                   "cppf_mesh_vote_stats_batch")
+    ws = workspace(_lib.lib().cppf_mesh_vote_stats_workspace_bytes(M, N, int(n_pairs)), dev, "mesh_vote_stats")
+    call("cppf_mesh_vote_stats_batch", dev, points, M, N, int(n_pairs), int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_mesh), stats, status,
+         scratch(ws))
     return stats, status
 
 

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._torch_util import require_cuda, stream_ptr, workspace
+from ._torch_util import call, require_cuda, scratch, workspace
 from .config import CATEGORIES, NOCS_CATEGORIES
 
 DATASET_K = np.array([[591.0125, 0, 320], [0, 590.16775, 240], [0, 0, 1]])   # utils/dataset.py:96 (not the inference intrinsics)
@@ -99,28 +99,24 @@ def default_bin_entries(n_faces, W=WIDTH, H=HEIGHT):
     return int(min(4 * n_faces + 64 * ((W + 15) // 16) * ((H + 15) // 16), 0x7FFFFFFF))
 
 
-def _raster(mesh, model_view, out, cull, fx, fy, znear, sync):
-    L = _lib.lib()
+def _raster(mesh, model_view, out, cull, fx, fy, znear, sync, ok=()):
     H, W = out.shape
-    nbytes = L.cppf_raster_workspace_bytes(mesh.n_faces, W, H, mesh.bins)
+    nbytes = _lib.lib().cppf_raster_workspace_bytes(mesh.n_faces, W, H, mesh.bins)
     if nbytes == 0:
         raise ValueError(f"render of {mesh.n_faces} faces at {W}x{H}: outside the rasteriser's limits (include/cppf.h)")
     ws = workspace(nbytes, out.device, "raster")
     mv = np.ascontiguousarray(np.asarray(model_view, np.float64)[:3, :4])
-    with torch.cuda.device(out.device):
-        rc = L.cppf_raster_depth(mesh.v.data_ptr(), mesh.v.shape[0], mesh.f.data_ptr(), mesh.n_faces, mv.ctypes.data, fx, fy, W, H,
-                                 znear, 1 if cull else 0, out.data_ptr(), mesh.bins, 1 if sync else 0, ws.data_ptr(), ws.numel(),
-                                 stream_ptr(out.device))
+    rc = call("cppf_raster_depth", out.device, mesh.v, mesh.v.shape[0], mesh.f, mesh.n_faces, mv, fx, fy, W, H, znear, bool(cull), out,
+              mesh.bins, bool(sync), scratch(ws), ok=ok)
     return rc, ws
 
 
 def _render(mesh, model_view, out, cull=True, fx=FX, fy=FY, znear=ZNEAR, sync=True):
     """render into `out`; a bin list that was too small is grown to what the render needed and the render repeated once"""
-    rc, ws = _raster(mesh, model_view, out, cull, fx, fy, znear, sync)
-    if rc == -5:                                                     # CPPF_ECAPACITY: the status words hold the entries needed
+    rc, ws = _raster(mesh, model_view, out, cull, fx, fy, znear, sync, ok=(_lib.ECAPACITY,))
+    if rc == _lib.ECAPACITY:                                         # the status words hold the entries needed
         mesh.bins = int(min(int(ws[:8].view(torch.int32)[1].item()) * 5 // 4 + 1024, 0x7FFFFFFF))   # (headroom for the next pose)
-        rc, ws = _raster(mesh, model_view, out, cull, fx, fy, znear, True)
-    _lib.check(rc, "cppf_raster_depth")
+        _, ws = _raster(mesh, model_view, out, cull, fx, fy, znear, True)
     return ws
 
 
@@ -138,8 +134,7 @@ def render_depth(vertices, faces, pose, cull=True, fx=FX, fy=FY, width=WIDTH, he
     out = torch.empty((height, width), dtype=torch.float32, device=dev)
     if max_bin_entries is not None:
         mesh.bins = int(max_bin_entries)
-        rc, _ = _raster(mesh, pose, out, cull, fx, fy, znear, True)
-        _lib.check(rc, "cppf_raster_depth")
+        _raster(mesh, pose, out, cull, fx, fy, znear, True)
     else:
         _render(mesh, pose, out, cull, fx, fy, znear)
     return out
@@ -149,15 +144,12 @@ def depth_points(depth, intrinsics=DATASET_K):
     """The covered pixels of a rendered depth image as the dataset's cloud (utils/dataset.py:203-207): (pts f64[H*W,3], count
     i32[1]) device tensors, the first count rows valid, in row-major pixel order (include/cppf.h: cppf_depth_points)."""
     H, W = depth.shape
-    L = _lib.lib()
     pts = torch.empty((H * W, 3), dtype=torch.float64, device=depth.device)
     pix = torch.empty(H * W, dtype=torch.int32, device=depth.device)
     count = torch.zeros(1, dtype=torch.int32, device=depth.device)
-    ws = workspace(L.cppf_depth_points_workspace_bytes(H, W), depth.device, "depth_points")
+    ws = workspace(_lib.lib().cppf_depth_points_workspace_bytes(H, W), depth.device, "depth_points")
     kinv = np.ascontiguousarray(np.linalg.inv(np.asarray(intrinsics, np.float64)))
-    with torch.cuda.device(depth.device):
-        _lib.check(L.cppf_depth_points(depth.data_ptr(), H, W, kinv.ctypes.data, pts.data_ptr(), pix.data_ptr(), count.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), stream_ptr(depth.device)), "cppf_depth_points")
+    call("cppf_depth_points", depth.device, depth, H, W, kinv, pts, pix, count, scratch(ws))
     return pts, count
 
 
@@ -256,7 +248,7 @@ class MeshViewSampler:
             ws = _render(m, model, self._depth, sync=False)
             pts, count = depth_points(self._depth)
             n_px, code, _ = torch.cat([count, ws[:8].view(torch.int32)]).tolist()       # one host read: count + render status
-            if code == -5:                                                                  # the bin list grew: render again
+            if code == _lib.ECAPACITY:                                                                  # the bin list grew: render again
                 ws = _render(m, model, self._depth)
                 pts, count = depth_points(self._depth)
                 n_px = int(count.item())

@@ -31,7 +31,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
-from .._torch_util import require_cuda, stream_ptr, workspace
+from .._torch_util import call, fill, require_cuda, scratch, workspace
 from .sprin import GlobalInfoProp, SparseSO3Conv, pack_point_encoder
 
 __all__ = ["ResLayer", "PPFEncoder", "PointEncoder"]
@@ -170,12 +170,8 @@ class _PairMlpFunction(torch.autograd.Function):
         ws = workspace(max(int(need), 256), dev, "pair_mlp_bwd")
         pcc, nrmc, featc = (pc.detach().float().contiguous(), nrm.detach().float().contiguous(),
                             feat.detach().float().contiguous())
-        with torch.cuda.device(dev):
-            rc = L.cppf_pair_mlp_backward(pcc.data_ptr(), nrmc.data_ptr(), featc.data_ptr(), idxs.data_ptr(),
-                                          1 if idxs.dtype == torch.int64 else 0, flat.data_ptr(), offs_c, pc.shape[0], F_,
-                                          dims, len(enc.ppffcs) - 1, P, enc.out_dim, grad_out.data_ptr(), gp.data_ptr(),
-                                          gf.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev))
-        _lib.check(rc, "cppf_pair_mlp_backward")
+        call("cppf_pair_mlp_backward", dev, pcc, nrmc, featc, idxs, idxs.dtype == torch.int64, flat, offs_c, pc.shape[0], F_, dims,
+             len(enc.ppffcs) - 1, P, enc.out_dim, grad_out, gp, gf, scratch(ws))
         grads, pos = [], 0
         for p in params:
             grads.append(gp[pos:pos + p.numel()].reshape(p.shape))
@@ -214,12 +210,8 @@ class _PointEncoderFunction(torch.autograd.Function):
         n_nat = sum(p.numel() for p in enc._ordered_params())
         gp = torch.empty(n_nat, dtype=torch.float32, device=dev)
         ws = workspace(max(int(L.cppf_point_encoder_backward_workspace_bytes(N)), 256), dev, "point_encoder_bwd")
-        with torch.cuda.device(dev):
-            rc = L.cppf_point_encoder_backward(pc.data_ptr(), nrm.data_ptr(), nbrs.data_ptr(), N, k, packed.data_ptr(), hid,
-                                               len(desc["hidden"]), desc["rank"], desc["n_nbr_feats"], desc["n_out"],
-                                               desc["n_glob"], enc.num_layers, out.data_ptr(), mixed.data_ptr(), g.data_ptr(),
-                                               gp.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev))
-        _lib.check(rc, "cppf_point_encoder_backward")
+        call("cppf_point_encoder_backward", dev, pc, nrm, nbrs, N, k, packed, hid, len(desc["hidden"]), desc["rank"], desc["n_nbr_feats"],
+             desc["n_out"], desc["n_glob"], enc.num_layers, out, mixed, g, gp, scratch(ws))
         grads, pos = [], 0
         for p, transposed in zip(enc._ordered_params(), enc._ordered_transposed()):
             v = gp[pos:pos + p.numel()]
@@ -285,10 +277,7 @@ class PointEncoder(_DeviceWeights, nn.Module):
         if self.k > N:
             raise ValueError(f"k={self.k} neighbours requested from {N} points")
         nbrs = torch.empty((N, self.k), dtype=torch.int32, device=pc.device)
-        with torch.cuda.device(pc.device):
-            rc = _lib.lib().cppf_knn(pc.data_ptr(), 0 if dist is None else dist.data_ptr(), N, self.k, nbrs.data_ptr(),
-                                     stream_ptr(pc.device))
-        _lib.check(rc, "cppf_knn")
+        call("cppf_knn", pc.device, pc, dist, N, self.k, nbrs)
         return nbrs
 
     def _forward_device(self, pc, nrm, nbrs, keep_contraction=None):
@@ -300,22 +289,15 @@ class PointEncoder(_DeviceWeights, nn.Module):
         out = torch.empty((N, W), dtype=torch.float32, device=pc.device)
         ws = workspace(L.cppf_point_encoder_workspace_bytes(N, desc["n_out"], desc["n_glob"], self.num_layers), pc.device,
                        "point_encoder")
-        with torch.cuda.device(pc.device):
-            if keep_contraction is not None:   # training: the backward reuses the per-point contraction
-                rc = L.cppf_point_encoder_forward_train(pc.data_ptr(), nrm.data_ptr(), nbrs.data_ptr(), N, k, packed.data_ptr(),
-                                                        hid, len(desc["hidden"]), desc["rank"], desc["n_nbr_feats"],
-                                                        desc["n_out"], desc["n_glob"], self.num_layers, out.data_ptr(),
-                                                        keep_contraction.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                        stream_ptr(pc.device))
-            else:
-                rc = L.cppf_point_encoder_forward(pc.data_ptr(), nrm.data_ptr(), nbrs.data_ptr(), N, k, packed.data_ptr(), hid,
-                                                  len(desc["hidden"]), desc["rank"], desc["n_nbr_feats"], desc["n_out"],
-                                                  desc["n_glob"], self.num_layers, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                  stream_ptr(pc.device))
-        if rc == -3:
+        args = (pc, nrm, nbrs, N, k, packed, hid, len(desc["hidden"]), desc["rank"], desc["n_nbr_feats"], desc["n_out"], desc["n_glob"],
+                self.num_layers, out)
+        if keep_contraction is not None:   # training: the backward reuses the per-point contraction
+            rc = call("cppf_point_encoder_forward_train", pc.device, *args, keep_contraction, scratch(ws), ok=(_lib.EUNSUPPORTED,))
+        else:
+            rc = call("cppf_point_encoder_forward", pc.device, *args, scratch(ws), ok=(_lib.EUNSUPPORTED,))
+        if rc == _lib.EUNSUPPORTED:
             raise _lib.CppfError(f"no device kernel for PointEncoder(k={self.k}, spfcs={self.spfcs}, out_dim={self.out_dim}): "
                                  "csrc/sprin.hip covers spfcs=[32,64,32,32], out_dim=32, k<=64 (train.py:34)")
-        _lib.check(rc, "cppf_point_encoder_forward")
         return out
 
     # ------------------------------------------------------------------ internals
@@ -394,10 +376,7 @@ class PointEncoder(_DeviceWeights, nn.Module):
             packed = old if old is not None and old.numel() == n else torch.empty(n, dtype=torch.float32, device=dev)
             if packed is old:
                 self._image_rebuild_begins(dev)
-            with torch.cuda.device(dev):
-                rc = L.cppf_point_encoder_pack_device(nat.data_ptr(), hid, 4, 32, 2, 32, desc["n_glob"], 1, packed.data_ptr(),
-                                                      stream_ptr(dev))
-            _lib.check(rc, "cppf_point_encoder_pack_device")
+            call("cppf_point_encoder_pack_device", dev, nat, hid, 4, 32, 2, 32, desc["n_glob"], 1, packed)
         else:
             sd = {k: v.detach().float().cpu().numpy() for k, v in self.state_dict().items()}
             natural, desc = pack_point_encoder(sd, self.num_layers)
@@ -405,9 +384,8 @@ class PointEncoder(_DeviceWeights, nn.Module):
             n = L.cppf_point_encoder_packed_floats(hid, len(desc["hidden"]), desc["rank"], desc["n_nbr_feats"], desc["n_out"],
                                                    desc["n_glob"], self.num_layers)
             image = np.zeros(max(int(n), natural.size), np.float32)
-            _lib.check(L.cppf_point_encoder_pack(natural.ctypes.data, hid, len(desc["hidden"]), desc["rank"],
-                                                 desc["n_nbr_feats"], desc["n_out"], desc["n_glob"], self.num_layers,
-                                                 image.ctypes.data), "cppf_point_encoder_pack")
+            call("cppf_point_encoder_pack", None, natural, hid, len(desc["hidden"]), desc["rank"], desc["n_nbr_feats"], desc["n_out"],
+                 desc["n_glob"], self.num_layers, image)
             if old is not None and old.numel() == image.size:
                 packed = old
                 self._image_rebuild_begins(dev)
@@ -438,17 +416,13 @@ class PointEncoder(_DeviceWeights, nn.Module):
             nbrs = torch.zeros((n_cap, self.k), dtype=torch.int32, device=pc.device)
         ws = workspace(L.cppf_point_encoder_workspace_bytes(n_cap, desc["n_out"], desc["n_glob"], self.num_layers), pc.device,
                        "point_encoder")
-        with torch.cuda.device(pc.device):
-            if not nbrs_ready:
-                _lib.check(L.cppf_knn_dyn(pc.data_ptr(), n_cap, n_dev.data_ptr(), self.k, nbrs.data_ptr(), stream_ptr(pc.device)),
-                           "cppf_knn_dyn")
-            rc = L.cppf_point_encoder_forward_dyn(pc.data_ptr(), pc_normal.data_ptr(), nbrs.data_ptr(), n_cap, n_dev.data_ptr(),
-                                                  self.k, packed.data_ptr(), hid, len(desc["hidden"]), desc["rank"],
-                                                  desc["n_nbr_feats"], desc["n_out"], desc["n_glob"], self.num_layers,
-                                                  out.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(pc.device))
-        if rc == -3:
+        if not nbrs_ready:
+            call("cppf_knn_dyn", pc.device, pc, n_cap, n_dev, self.k, nbrs)
+        rc = call("cppf_point_encoder_forward_dyn", pc.device, pc, pc_normal, nbrs, n_cap, n_dev, self.k, packed, hid, len(desc["hidden"]),
+                  desc["rank"], desc["n_nbr_feats"], desc["n_out"], desc["n_glob"], self.num_layers, out, scratch(ws),
+                  ok=(_lib.EUNSUPPORTED,))
+        if rc == _lib.EUNSUPPORTED:
             raise _lib.CppfError(f"no device kernel for PointEncoder(k={self.k}, spfcs={self.spfcs}, out_dim={self.out_dim})")
-        _lib.check(rc, "cppf_point_encoder_forward_dyn")
         return out
 
 
@@ -472,20 +446,13 @@ def point_encoder_forward_batch(members):
         packed, desc = m["encoder"]._packed_weights(dev)
         n_cap = m["pc"].shape[0]
         ws = workspace(L.cppf_point_encoder_workspace_bytes(n_cap, desc["n_out"], desc["n_glob"], 1), dev, f"point_encoder{i}")
-        a = arr[i]
-        a.pc, a.nrm, a.nbrs, a.out = m["pc"].data_ptr(), m["nrm"].data_ptr(), m["nbrs"].data_ptr(), m["out"].data_ptr()
-        a.n_dev = None if m.get("n_dev") is None else m["n_dev"].data_ptr()
-        a.packed, a.workspace, a.workspace_bytes = packed.data_ptr(), ws.data_ptr(), ws.numel()
-        a.n_cap, a.nbrs_ready = n_cap, 1 if m.get("nbrs_ready") else 0
+        fill(arr[i], pc=m["pc"], nrm=m["nrm"], nbrs=m["nbrs"], out=m["out"], n_dev=m.get("n_dev"), packed=packed, workspace=scratch(ws),
+             n_cap=n_cap, nbrs_ready=bool(m.get("nbrs_ready")))
         keep.append((packed, ws))
     hid = (C.c_int * len(desc["hidden"]))(*desc["hidden"])
-    with torch.cuda.device(dev):
-        rc = L.cppf_point_encoder_forward_batch(len(members), C.cast(arr, C.c_void_p), e0.k, hid, len(desc["hidden"]), desc["rank"],
-                                                desc["n_nbr_feats"], desc["n_out"], desc["n_glob"], 1, stream_ptr(dev))
-    if rc == -3:
-        return None
-    _lib.check(rc, "cppf_point_encoder_forward_batch")
-    return [m["out"] for m in members]
+    rc = call("cppf_point_encoder_forward_batch", dev, len(members), arr, e0.k, hid, len(desc["hidden"]), desc["rank"],
+              desc["n_nbr_feats"], desc["n_out"], desc["n_glob"], 1, ok=(_lib.EUNSUPPORTED,))
+    return None if rc == _lib.EUNSUPPORTED else [m["out"] for m in members]
 
 
 class PPFEncoder(_DeviceWeights, nn.Module):
@@ -529,13 +496,8 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         out = torch.empty((P, self.out_dim), dtype=torch.float32, device=pc.device)
         dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
         ws = self._scratch(pc, feat, dims)
-        with torch.cuda.device(pc.device):
-            rc = _lib.lib().cppf_pair_mlp_forward(
-                pc.data_ptr(), pc_normal.data_ptr(), feat.data_ptr(), idxs.data_ptr(),
-                1 if idxs.dtype == torch.int64 else 0, self._packed_weights(pc.device).data_ptr(), pc.shape[0],
-                feat.shape[1], dims, len(self.ppffcs) - 1, P, self.out_dim, out.data_ptr(), ws.data_ptr(), ws.numel(),
-                stream_ptr(pc.device))
-        _lib.check(rc, "cppf_pair_mlp_forward")
+        call("cppf_pair_mlp_forward", pc.device, pc, pc_normal, feat, idxs, idxs.dtype == torch.int64, self._packed_weights(pc.device),
+             pc.shape[0], feat.shape[1], dims, len(self.ppffcs) - 1, P, self.out_dim, out, scratch(ws))
         return out
 
     # ------------------------------------------------------------------ fused decode (this package)
@@ -555,26 +517,16 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         outputs = torch.empty((P, 2), dtype=torch.float32, device=pc.device)
         heads = torch.empty((P, 8), dtype=torch.float32, device=pc.device) if u_rot is not None else None
         dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
-        L = _lib.lib()
         ws = self._scratch(pc, feat, dims)
-        with torch.cuda.device(pc.device):
-            rc = L.cppf_pair_mlp_decode(
-                pc.data_ptr(), pc_normal.data_ptr(), feat.data_ptr(), idxs.data_ptr(),
-                1 if idxs.dtype == torch.int64 else 0, self._packed_weights(pc.device).data_ptr(), pc.shape[0],
-                feat.shape[1], dims, len(self.ppffcs) - 1, P, self.out_dim, tr_num_bins, rot_num_bins,
-                float(vote_range[0]), float(vote_range[1]), u_tr.data_ptr(),
-                u_rot.data_ptr() if u_rot is not None else None, outputs.data_ptr(),
-                heads.data_ptr() if heads is not None else None, ws.data_ptr(), ws.numel(), stream_ptr(pc.device))
-            if rc == -3:  # architecture / bin counts outside the fused kernel: logits + decode kernels
-                logits = self.forward_with_idx(pc, pc_normal, feat, idxs)
-                rc = L.cppf_decode_center(logits.data_ptr(), P, self.out_dim, tr_num_bins, float(vote_range[0]),
-                                          float(vote_range[1]), u_tr.data_ptr(), outputs.data_ptr(),
-                                          stream_ptr(pc.device))
-                _lib.check(rc, "cppf_decode_center")
-                if heads is not None:
-                    rc = L.cppf_decode_rot(logits.data_ptr(), P, self.out_dim, self.out_dim, tr_num_bins, rot_num_bins,
-                                           u_rot.data_ptr(), heads.data_ptr(), stream_ptr(pc.device))
-        _lib.check(rc, "cppf_pair_mlp_decode")
+        rc = call("cppf_pair_mlp_decode", pc.device, pc, pc_normal, feat, idxs, idxs.dtype == torch.int64, self._packed_weights(pc.device),
+                  pc.shape[0], feat.shape[1], dims, len(self.ppffcs) - 1, P, self.out_dim, tr_num_bins, rot_num_bins,
+                  float(vote_range[0]), float(vote_range[1]), u_tr, u_rot, outputs, heads, scratch(ws), ok=(_lib.EUNSUPPORTED,))
+        if rc == _lib.EUNSUPPORTED:  # architecture / bin counts outside the fused kernel: logits + decode kernels
+            logits = self.forward_with_idx(pc, pc_normal, feat, idxs)
+            call("cppf_decode_center", pc.device, logits, P, self.out_dim, tr_num_bins, float(vote_range[0]), float(vote_range[1]), u_tr,
+                 outputs)
+            if heads is not None:
+                call("cppf_decode_rot", pc.device, logits, P, self.out_dim, self.out_dim, tr_num_bins, rot_num_bins, u_rot, heads)
         return outputs, heads
 
     def fused_decode_supported(self, tr_num_bins=32, rot_num_bins=36):
@@ -597,27 +549,21 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         max_sel = P if max_sel is None else min(int(max_sel), P)
         dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
         ws = self._scratch(pc, feat, dims)
-        with torch.cuda.device(pc.device):
-            rc = _lib.lib().cppf_pair_mlp_decode_sel(
-                pc.data_ptr(), pc_normal.data_ptr(), feat.data_ptr(), idxs.data_ptr(), 1 if idxs.dtype == torch.int64 else 0,
-                self._packed_weights(pc.device).data_ptr(), pc.shape[0], feat.shape[1], dims, len(self.ppffcs) - 1, P,
-                self.out_dim, tr_num_bins, rot_num_bins, u_rot.data_ptr(), sel.data_ptr(), n_sel.data_ptr(), max_sel,
-                heads.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(pc.device))
-            if rc == -3:
-                # architecture / bin counts outside the fused kernel: the logits of the selected pairs + cppf_decode_rot, rows
-                # scattered back.  The count is read on the host (one sync; not capturable -- the pose pipelines run such
-                # configurations in their full-first form instead, see inference.PosePipeline).
-                n = min(int(n_sel.item()), max_sel)
-                if n > 0:
-                    rows = sel[:n].long()
-                    logits = self._forward_device(pc, pc_normal, feat, idxs[rows].contiguous())
-                    sub = torch.empty((n, 8), dtype=torch.float32, device=pc.device)
-                    rc = _lib.lib().cppf_decode_rot(logits.data_ptr(), n, self.out_dim, self.out_dim, tr_num_bins, rot_num_bins,
-                                                    u_rot[rows].contiguous().data_ptr(), sub.data_ptr(), stream_ptr(pc.device))
-                    _lib.check(rc, "cppf_decode_rot")
-                    heads[rows] = sub
-                rc = 0
-        _lib.check(rc, "cppf_pair_mlp_decode_sel")
+        rc = call("cppf_pair_mlp_decode_sel", pc.device, pc, pc_normal, feat, idxs, idxs.dtype == torch.int64,
+                  self._packed_weights(pc.device), pc.shape[0], feat.shape[1], dims, len(self.ppffcs) - 1, P, self.out_dim, tr_num_bins,
+                  rot_num_bins, u_rot, sel, n_sel, max_sel, heads, scratch(ws), ok=(_lib.EUNSUPPORTED,))
+        if rc == _lib.EUNSUPPORTED:
+            # architecture / bin counts outside the fused kernel: the logits of the selected pairs + cppf_decode_rot, rows
+            # scattered back.  The count is read on the host (one sync; not capturable -- the pose pipelines run such
+            # configurations in their full-first form instead, see inference.PosePipeline).
+            n = min(int(n_sel.item()), max_sel)
+            if n > 0:
+                rows = sel[:n].long()
+                logits = self._forward_device(pc, pc_normal, feat, idxs[rows].contiguous())
+                sub = torch.empty((n, 8), dtype=torch.float32, device=pc.device)
+                call("cppf_decode_rot", pc.device, logits, n, self.out_dim, self.out_dim, tr_num_bins, rot_num_bins,
+                     u_rot[rows].contiguous(), sub)
+                heads[rows] = sub
         return heads
 
     # ------------------------------------------------------------------ internals
@@ -743,18 +689,13 @@ class PPFEncoder(_DeviceWeights, nn.Module):
             packed = old if old is not None else torch.empty(n, dtype=torch.float32, device=dev)
             if old is not None:
                 self._image_rebuild_begins(dev)
-            with torch.cuda.device(dev):
-                rc = L.cppf_pair_mlp_pack_device(flat.data_ptr(), offs_c, F_, dims, n_res, self.out_dim, packed.data_ptr(),
-                                                 stream_ptr(dev))
-            _lib.check(rc, "cppf_pair_mlp_pack_device")
+            call("cppf_pair_mlp_pack_device", dev, flat, offs_c, F_, dims, n_res, self.out_dim, packed)
             self._packed = packed
         else:
             sd = {k: v.detach().float().cpu().numpy() for k, v in self.state_dict().items()}
             params, offs = flatten_state_dict(sd, self.ppffcs)
             packed = np.zeros(n, np.float32)
-            rc = L.cppf_pair_mlp_pack(params.ctypes.data, offs.ctypes.data, F_, dims, n_res, self.out_dim,
-                                      packed.ctypes.data)
-            _lib.check(rc, "cppf_pair_mlp_pack")
+            call("cppf_pair_mlp_pack", None, params, offs, F_, dims, n_res, self.out_dim, packed)
             if old is not None:
                 if dev.type == "cuda":
                     self._image_rebuild_begins(dev)
@@ -794,7 +735,7 @@ def batch_plan(n_pairs):
     n = len(n_pairs)
     arr = (C.c_int64 * n)(*[int(v) for v in n_pairs])
     per_xcd, grid, wb = C.c_int(0), C.c_int(0), (C.c_int * (n + 1))()
-    _lib.check(_lib.lib().cppf_pair_mlp_batch_plan(n, arr, C.byref(per_xcd), C.byref(grid), wb), "cppf_pair_mlp_batch_plan")
+    call("cppf_pair_mlp_batch_plan", None, n, arr, C.byref(per_xcd), C.byref(grid), wb)
     return dict(per_xcd=per_xcd.value, grid=grid.value, wg_begin=list(wb))
 
 
@@ -827,20 +768,13 @@ def forward_decode_batch(items, tr_num_bins=32, rot_num_bins=36, tables_out=None
         need = _lib.lib().cppf_pair_mlp_workspace_bytes(pc.shape[0], feat.shape[1], dims, len(enc.ppffcs) - 1, enc.out_dim)
         ws = workspace(max(int(need), 256), dev, f"pair_mlp_batch{i}")       # (each list its own per-point table)
         packed = enc._packed_weights(dev)
-        a = arr[i]
-        a.pc, a.nrm, a.feat, a.idxs, a.packed = pc.data_ptr(), nrm.data_ptr(), feat.data_ptr(), idxs.data_ptr(), packed.data_ptr()
-        a.u_tr, a.u_rot = u_tr.data_ptr(), (u_rot.data_ptr() if u_rot is not None else None)
-        a.outputs, a.heads = outputs.data_ptr(), (heads.data_ptr() if heads is not None else None)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        a.n_points, a.n_pairs = pc.shape[0], P
-        a.vr0, a.vr1 = float(it["vote_range"][0]), float(it["vote_range"][1])
-        a.idx_is_i64 = 1 if idxs.dtype == torch.int64 else 0
+        fill(arr[i], pc=pc, nrm=nrm, feat=feat, idxs=idxs, packed=packed, u_tr=u_tr, u_rot=u_rot, outputs=outputs, heads=heads,
+             workspace=scratch(ws), n_points=pc.shape[0], n_pairs=P, vr0=float(it["vote_range"][0]), vr1=float(it["vote_range"][1]),
+             idx_is_i64=idxs.dtype == torch.int64)
         keep.append((idxs, pc, nrm, feat, ws, packed))
         outs.append((outputs, heads))
-    with torch.cuda.device(dev):
-        rc = _lib.lib().cppf_pair_mlp_decode_batch(len(items), C.cast(arr, C.c_void_p), items[0]["feat"].shape[1], dims,
-                                                   len(enc0.ppffcs) - 1, enc0.out_dim, tr_num_bins, rot_num_bins, stream_ptr(dev))
-    _lib.check(rc, "cppf_pair_mlp_decode_batch")
+    call("cppf_pair_mlp_decode_batch", dev, len(items), arr, items[0]["feat"].shape[1], dims, len(enc0.ppffcs) - 1, enc0.out_dim,
+         tr_num_bins, rot_num_bins)
     if tables_out is not None:      # the per-point tables this pass left (a batched second pass reuses them: cppf_pose_tail_batch)
         tables_out[:] = [k[4] for k in keep]
     return outs

@@ -17,7 +17,7 @@ includes a file that does not exist).
 import torch
 
 from .. import _lib
-from .._torch_util import dev_tensor, require_cuda, scalar, stream_ptr, workspace
+from .._torch_util import call, dev_tensor, fill, require_cuda, scalar, scratch, workspace
 
 __all__ = ["ppf_kernel", "backvote_kernel", "rot_voting_kernel", "vote_argmax", "vote_argmax_dyn", "grid_argmax",
            "vote_grid_raw", "grid_from_raw", "vote_fixed_point_bits"]
@@ -82,17 +82,12 @@ def _ppf_voting(points, outputs, probs, point_idxs, grid_obj, corner, res, n_ppf
         raise ValueError("probs must have one entry per point")
     if outputs.shape[0] < n_ppfs or point_idxs.shape[0] < n_ppfs or n_ppfs < 0:
         raise ValueError("n_ppfs exceeds the outputs/point_idxs arrays")
-    L = _lib.lib()
-    need = L.cppf_vote_workspace_bytes(n_ppfs, n_rots, gx, gy, gz)
+    need = _lib.lib().cppf_vote_workspace_bytes(n_ppfs, n_rots, gx, gy, gz)
     if need == 0:
         raise ValueError(f"n_rots must be in 1..360, got {n_rots}")
     ws = workspace(need, dev, "vote", zero=True)
-    with torch.cuda.device(dev):
-        rc = L.cppf_ppf_voting(points.data_ptr(), outputs.data_ptr(), probs.data_ptr(), point_idxs.data_ptr(),
-                               grid_obj.data_ptr(), corner.data_ptr(), float(scalar(res)), points.shape[0], n_ppfs,
-                               n_rots, gx, gy, gz, 1 if bool(scalar(adaptive)) else 0, ws.data_ptr(), ws.numel(),
-                               stream_ptr(dev))
-    _lib.check(rc, "cppf_ppf_voting")
+    call("cppf_ppf_voting", dev, points, outputs, probs, point_idxs, grid_obj, corner, float(scalar(res)), points.shape[0], n_ppfs, n_rots,
+         gx, gy, gz, bool(scalar(adaptive)), scratch(ws))
 
 
 def _vote_flags(accumulate, workgroups):
@@ -130,17 +125,12 @@ def vote_argmax(points, outputs, probs, point_idxs, grid_obj, corner, res, n_rot
         out_idx = torch.empty(1, dtype=torch.int64, device=dev)
     if out_val is None:
         out_val = torch.empty(1, dtype=F32, device=dev)
-    L = _lib.lib()
-    need = L.cppf_vote_workspace_bytes(n_ppfs, int(n_rots), gx, gy, gz)
+    need = _lib.lib().cppf_vote_workspace_bytes(n_ppfs, int(n_rots), gx, gy, gz)
     if need == 0:
         raise ValueError(f"n_rots must be in 1..360, got {n_rots}")
     ws = workspace(need, dev, "vote", zero=True)
-    with torch.cuda.device(dev):
-        rc = L.cppf_vote_argmax(points.data_ptr(), outputs.data_ptr(), None if probs is None else probs.data_ptr(), point_idxs.data_ptr(),
-                                1 if i64 else 0, grid_obj.data_ptr(), corner.data_ptr(), float(scalar(res)), points.shape[0], n_ppfs,
-                                int(n_rots), gx, gy, gz, 1 if adaptive else 0, _vote_flags(accumulate, workgroups),
-                                out_idx.data_ptr(), out_val.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev))
-    _lib.check(rc, "cppf_vote_argmax")
+    call("cppf_vote_argmax", dev, points, outputs, probs, point_idxs, i64, grid_obj, corner, float(scalar(res)), points.shape[0], n_ppfs,
+         int(n_rots), gx, gy, gz, bool(adaptive), _vote_flags(accumulate, workgroups), out_idx, out_val, scratch(ws))
     return out_idx, out_val
 
 
@@ -161,16 +151,11 @@ def vote_argmax_dyn(points, outputs, probs, point_idxs, grid_flat, shape, corner
     dev_tensor(corner, F32, "corner", None, dev)
     if shape.numel() < 4 or (probs is not None and probs.numel() != points.shape[0]):
         raise ValueError("shape must be i32[4]; probs must have one entry per (capacity) point")
-    L = _lib.lib()
     many_tiles = _lib.tile_class(many_tiles)
-    ws = workspace(L.cppf_vote_workspace_bytes_dyn_pairs(many_tiles, int(point_idxs.shape[0])), dev, "vote_dyn", zero=True)
-    with torch.cuda.device(dev):
-        rc = L.cppf_vote_argmax_dyn(points.data_ptr(), outputs.data_ptr(), None if probs is None else probs.data_ptr(), point_idxs.data_ptr(),
-                                    1 if i64 else 0, grid_flat.data_ptr(), grid_flat.numel(), corner.data_ptr(),
-                                    float(scalar(res)), points.shape[0], point_idxs.shape[0], int(n_rots), shape.data_ptr(),
-                                    many_tiles, 1 if adaptive else 0, _vote_flags(accumulate, workgroups),
-                                    out_idx.data_ptr(), out_val.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev))
-    _lib.check(rc, "cppf_vote_argmax_dyn")
+    ws = workspace(_lib.lib().cppf_vote_workspace_bytes_dyn_pairs(many_tiles, int(point_idxs.shape[0])), dev, "vote_dyn", zero=True)
+    call("cppf_vote_argmax_dyn", dev, points, outputs, probs, point_idxs, i64, grid_flat, grid_flat.numel(), corner, float(scalar(res)),
+         points.shape[0], point_idxs.shape[0], int(n_rots), shape, many_tiles, bool(adaptive), _vote_flags(accumulate, workgroups),
+         out_idx, out_val, scratch(ws))
     return out_idx, out_val
 
 
@@ -222,8 +207,7 @@ def vote_argmax_batch(items, n_rots, adaptive, accumulate=False, workgroups=0, w
             dev_tensor(shape, I32, "shape", None, dev)
             many = _lib.tile_class(it.get("many_tiles") or 0)
             ws = workspace(L.cppf_vote_workspace_bytes_dyn_pairs(many, int(n_ppfs)), dev, f"{ws_tag}dyn{i}", zero=True)
-            a.shape_dev, a.grid_capacity, a.many_tiles = shape.data_ptr(), grid.numel(), many
-            a.gx = a.gy = a.gz = 1
+            fill(a, shape_dev=shape, grid_capacity=grid.numel(), many_tiles=many, gx=1, gy=1, gz=1)
         else:
             if grid.dim() != 3:
                 raise ValueError("grid must be [gx,gy,gz] (or pass `shape` for a capacity buffer)")
@@ -232,17 +216,11 @@ def vote_argmax_batch(items, n_rots, adaptive, accumulate=False, workgroups=0, w
             if need == 0:
                 raise ValueError(f"n_rots must be in 1..360, got {n_rots}")
             ws = workspace(need, dev, f"{ws_tag}{i}", zero=True)
-            a.shape_dev, a.grid_capacity, a.many_tiles = None, 0, 0
-            a.gx, a.gy, a.gz = gx, gy, gz
-        a.points, a.outputs, a.probs = points.data_ptr(), outputs.data_ptr(), (None if probs is None else probs.data_ptr())
-        a.point_idxs, a.idx_is_i64, a.grid, a.corner = idx.data_ptr(), (1 if i64 else 0), grid.data_ptr(), corner.data_ptr()
-        a.out_idx, a.out_val, a.workspace, a.workspace_bytes = out_idx.data_ptr(), out_val.data_ptr(), ws.data_ptr(), ws.numel()
-        a.n_points, a.n_ppfs, a.res = points.shape[0], n_ppfs, float(scalar(it["res"]))
+            fill(a, shape_dev=None, grid_capacity=0, many_tiles=0, gx=gx, gy=gy, gz=gz)
+        fill(a, points=points, outputs=outputs, probs=probs, point_idxs=idx, idx_is_i64=i64, grid=grid, corner=corner, out_idx=out_idx,
+             out_val=out_val, workspace=scratch(ws), n_points=points.shape[0], n_ppfs=n_ppfs, res=float(scalar(it["res"])))
         keep.append(ws)
-    import ctypes as C
-    with torch.cuda.device(dev):
-        rc = L.cppf_vote_argmax_batch(len(items), C.cast(arr, C.c_void_p), int(n_rots), 1 if adaptive else 0, flags, stream_ptr(dev))
-    _lib.check(rc, "cppf_vote_argmax_batch")
+    call("cppf_vote_argmax_batch", dev, len(items), arr, int(n_rots), bool(adaptive), flags)
     if workspaces_out is not None:  # (the back-vote loads the rotation table a vote left in its workspace)
         workspaces_out[:] = keep
     return [(it["out_idx"], it["out_val"]) for it in items]
@@ -272,17 +250,12 @@ def vote_grid_raw(points, outputs, probs, point_idxs, grid_raw, quantum, corner,
         raise ValueError("grid_raw must be [gx,gy,gz]")
     gx, gy, gz = grid_raw.shape
     n_ppfs = point_idxs.shape[0]
-    L = _lib.lib()
-    need = L.cppf_vote_workspace_bytes(n_ppfs, int(n_rots), gx, gy, gz)
+    need = _lib.lib().cppf_vote_workspace_bytes(n_ppfs, int(n_rots), gx, gy, gz)
     if need == 0:
         raise ValueError(f"n_rots must be in 1..360, got {n_rots}")
     ws = workspace(need, dev, "vote", zero=True)
-    with torch.cuda.device(dev):
-        rc = L.cppf_vote_grid_raw(points.data_ptr(), outputs.data_ptr(), None if probs is None else probs.data_ptr(),
-                                  point_idxs.data_ptr(), 1 if i64 else 0, grid_raw.data_ptr(), quantum.data_ptr(), corner.data_ptr(),
-                                  float(scalar(res)), points.shape[0], n_ppfs, int(n_rots), gx, gy, gz, 1 if adaptive else 0,
-                                  1 if accumulate else 0, int(fixed_bits), ws.data_ptr(), ws.numel(), stream_ptr(dev))
-    _lib.check(rc, "cppf_vote_grid_raw")
+    call("cppf_vote_grid_raw", dev, points, outputs, probs, point_idxs, i64, grid_raw, quantum, corner, float(scalar(res)), points.shape[0],
+         n_ppfs, int(n_rots), gx, gy, gz, bool(adaptive), bool(accumulate), int(fixed_bits), scratch(ws))
 
 
 def grid_from_raw(grid_raw, quantum, grid=None, out_idx=None, out_val=None):
@@ -299,10 +272,7 @@ def grid_from_raw(grid_raw, quantum, grid=None, out_idx=None, out_val=None):
     if out_val is None:
         out_val = torch.empty(1, dtype=F32, device=dev)
     ws = workspace(256, dev, "argmax")
-    with torch.cuda.device(dev):
-        rc = _lib.lib().cppf_grid_from_raw(grid_raw.data_ptr(), grid_raw.numel(), quantum.data_ptr(), grid.data_ptr(),
-                                           out_idx.data_ptr(), out_val.data_ptr(), ws.data_ptr(), ws.numel(), stream_ptr(dev))
-    _lib.check(rc, "cppf_grid_from_raw")
+    call("cppf_grid_from_raw", dev, grid_raw, grid_raw.numel(), quantum, grid, out_idx, out_val, scratch(ws))
     return grid, out_idx, out_val
 
 
@@ -314,10 +284,7 @@ def grid_argmax(grid, out_idx=None, out_val=None):
     if out_val is None:
         out_val = torch.empty(1, dtype=F32, device=dev)
     ws = workspace(256, dev, "argmax")
-    with torch.cuda.device(dev):
-        rc = _lib.lib().cppf_grid_argmax(grid.data_ptr(), grid.numel(), out_idx.data_ptr(), out_val.data_ptr(),
-                                         ws.data_ptr(), ws.numel(), stream_ptr(dev))
-    _lib.check(rc, "cppf_grid_argmax")
+    call("cppf_grid_argmax", dev, grid, grid.numel(), out_idx, out_val, scratch(ws))
     return out_idx, out_val
 
 
@@ -333,11 +300,8 @@ def _backvote(points, outputs, out_offsets, point_idxs, corner, res, n_ppfs, n_r
     gx, gy, gz = _dims(gx, gy, gz)
     if min(outputs.shape[0], point_idxs.shape[0], out_offsets.shape[0]) < n_ppfs or n_ppfs < 0:
         raise ValueError("n_ppfs exceeds the outputs/point_idxs/out_offsets arrays")
-    with torch.cuda.device(dev):
-        rc = _lib.lib().cppf_backvote(points.data_ptr(), outputs.data_ptr(), out_offsets.data_ptr(),
-                                      point_idxs.data_ptr(), corner.data_ptr(), float(scalar(res)), n_ppfs, n_rots, gx,
-                                      gy, gz, gt_center.data_ptr(), float(scalar(tol)), None, stream_ptr(dev))
-    _lib.check(rc, "cppf_backvote")
+    call("cppf_backvote", dev, points, outputs, out_offsets, point_idxs, corner, float(scalar(res)), n_ppfs, n_rots, gx, gy, gz, gt_center,
+         float(scalar(tol)), None)
 
 
 def _rot_voting(points, not_used, preds_rot, outputs_up, point_idxs, corner, res, n_ppfs, n_rots, gx, gy, gz):
@@ -352,10 +316,7 @@ def _rot_voting(points, not_used, preds_rot, outputs_up, point_idxs, corner, res
         raise ValueError("n_ppfs exceeds the preds_rot/point_idxs arrays")
     if outputs_up.numel() < n_ppfs * n_rots * 3:
         raise ValueError("outputs_up must hold n_ppfs*n_rots*3 floats")
-    with torch.cuda.device(dev):
-        rc = _lib.lib().cppf_rot_voting(points.data_ptr(), preds_rot.data_ptr(), outputs_up.data_ptr(),
-                                        point_idxs.data_ptr(), n_ppfs, n_rots, stream_ptr(dev))
-    _lib.check(rc, "cppf_rot_voting")
+    call("cppf_rot_voting", dev, points, preds_rot, outputs_up, point_idxs, n_ppfs, n_rots)
 
 
 ppf_kernel = _Kernel("ppf_voting", 13, _ppf_voting)

@@ -44,7 +44,7 @@ def backproject(depth, intrinsics, instance_mask, return_device=False):
     all of its instances (pass the device tensor)."""
     import torch
     from .. import _lib
-    from .._torch_util import require_cuda, stream_ptr, workspace
+    from .._torch_util import call, require_cuda, scratch, workspace
     require_cuda()
 
     def dev(x, kinds):
@@ -67,12 +67,8 @@ def backproject(depth, intrinsics, instance_mask, return_device=False):
     pts = torch.empty((H * W, 3), dtype=torch.float64, device=d.device)
     pix = torch.empty(H * W, dtype=torch.int32, device=d.device)
     count = torch.zeros(1, dtype=torch.int32, device=d.device)
-    L = _lib.lib()
-    ws = workspace(L.cppf_backproject_workspace_bytes(H, W), d.device, "backproject")
-    with torch.cuda.device(d.device):
-        _lib.check(L.cppf_backproject(d.data_ptr(), 1 if d.dtype == torch.int16 else 0, m.data_ptr(), H, W, kinv.ctypes.data,
-                                      pts.data_ptr(), pix.data_ptr(), count.data_ptr(), ws.data_ptr(), ws.numel(),
-                                      stream_ptr(d.device)), "cppf_backproject")
+    ws = workspace(_lib.lib().cppf_backproject_workspace_bytes(H, W), d.device, "backproject")
+    call("cppf_backproject", d.device, d, d.dtype == torch.int16, m, H, W, kinv, pts, pix, count, scratch(ws))
     n = int(count.item())
     if return_device:
         return pts[:n], pix[:n]
@@ -86,17 +82,13 @@ def estimate_normals(pc, knn):
     numpy in -> numpy f32[N,3] out, torch in -> torch out.  open3d leaves the sign of a normal unspecified; here the
     component of largest magnitude is positive (parity with open3d is unpinned, see oracle/preproc_oracle.c)."""
     import torch
-    from .. import _lib
-    from .._torch_util import stream_ptr
+    from .._torch_util import call
     t, was_np = _device_cloud(pc)
     N, k = t.shape[0], min(int(knn), t.shape[0])
     nbrs = torch.empty((N, k), dtype=torch.int32, device=t.device)
     out = torch.empty((N, 3), dtype=torch.float32, device=t.device)
-    L = _lib.lib()
-    with torch.cuda.device(t.device):
-        _lib.check(L.cppf_knn(t.data_ptr(), None, N, k, nbrs.data_ptr(), stream_ptr(t.device)), "cppf_knn")
-        _lib.check(L.cppf_estimate_normals(t.data_ptr(), nbrs.data_ptr(), N, k, out.data_ptr(), stream_ptr(t.device)),
-                   "cppf_estimate_normals")
+    call("cppf_knn", t.device, t, None, N, k, nbrs)
+    call("cppf_estimate_normals", t.device, t, nbrs, N, k, out)
     return out.cpu().numpy() if was_np else out
 
 
@@ -107,16 +99,13 @@ def sparse_quantize(pc, return_index=True, quantization_size=1.0):
     output is in index order (MinkowskiEngine's choice is hash-order dependent: parity unpinned)."""
     import torch
     from .. import _lib
-    from .._torch_util import stream_ptr, workspace
+    from .._torch_util import call, scratch, workspace
     t, was_np = _device_cloud(pc)
     N = t.shape[0]
     keep = torch.empty(N, dtype=torch.int32, device=t.device)
     count = torch.zeros(1, dtype=torch.int32, device=t.device)
-    L = _lib.lib()
-    ws = workspace(L.cppf_voxel_dedupe_workspace_bytes(N), t.device, "voxel")
-    with torch.cuda.device(t.device):
-        _lib.check(L.cppf_voxel_dedupe(t.data_ptr(), N, float(quantization_size), keep.data_ptr(), count.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), stream_ptr(t.device)), "cppf_voxel_dedupe")
+    ws = workspace(_lib.lib().cppf_voxel_dedupe_workspace_bytes(N), t.device, "voxel")
+    call("cppf_voxel_dedupe", t.device, t, N, float(quantization_size), keep, count, scratch(ws))
     idx = keep[:int(count.item())].long()
     coords = torch.floor(t[idx].double() / float(quantization_size)).to(torch.int32)
     if was_np:

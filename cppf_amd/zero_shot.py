@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._torch_util import require_cuda, stream_ptr, workspace
+from ._torch_util import call, require_cuda, scratch, workspace
 from .models import voting
 from .utils.util import fibonacci_sphere, num_sphere_bins
 
@@ -60,11 +60,8 @@ def smooth_grid(grid, sigma=1.0, truncate=4.0):
     w = gaussian_weights(sigma, truncate)
     gx, gy, gz = g.shape
     out = torch.empty_like(g)
-    L = _lib.lib()
-    ws = workspace(L.cppf_gaussian_filter3d_workspace_bytes(gx, gy, gz), g.device, "gauss")
-    with torch.cuda.device(g.device):
-        _lib.check(L.cppf_gaussian_filter3d(g.data_ptr(), out.data_ptr(), gx, gy, gz, w.ctypes.data, (w.shape[0] - 1) // 2,
-                                            ws.data_ptr(), ws.numel(), stream_ptr(g.device)), "cppf_gaussian_filter3d")
+    ws = workspace(_lib.lib().cppf_gaussian_filter3d_workspace_bytes(gx, gy, gz), g.device, "gauss")
+    call("cppf_gaussian_filter3d", g.device, g, out, gx, gy, gz, w, (w.shape[0] - 1) // 2, scratch(ws))
     return out.cpu().numpy() if was_np else out
 
 
@@ -107,13 +104,8 @@ def scene_proposals_device(grid, sigma=1.0, thresh=50, margin=10, max_proposals=
         raise ValueError("smoothed_out must be a contiguous float32 tensor shaped like the grid")
     if ws is None:
         ws = proposals_workspace(g.shape, dev)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        _lib.check(L.cppf_scene_proposals(g.data_ptr(), gx, gy, gz, w.ctypes.data, (w.shape[0] - 1) // 2,
-                                          float(np.float32(thresh)), int(margin), K, max_iters, loc.data_ptr(), val.data_ptr(),
-                                          diff.data_ptr(), count.data_ptr(),
-                                          None if smoothed_out is None else smoothed_out.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          stream_ptr(dev)), "cppf_scene_proposals")
+    call("cppf_scene_proposals", dev, g, gx, gy, gz, w, (w.shape[0] - 1) // 2, float(np.float32(thresh)), int(margin), K, max_iters,
+         loc, val, diff, count, smoothed_out, scratch(ws))
     return loc, val, diff, count
 
 
@@ -138,14 +130,12 @@ def _pairs_tensor(idx, dev):
 
 def _compact(mask, dev):
     """positions of the non-zero bytes of a device u8 mask, in order (cppf_compact_mask) -> (i32[n] device, n)"""
-    L = _lib.lib()
     P = mask.numel()
     surv = torch.empty(max(P, 1), dtype=I32, device=dev)
     count = torch.zeros(1, dtype=I32, device=dev)
     if P:
-        cws = workspace(L.cppf_compact_workspace_bytes(P), dev, "compact")
-        _lib.check(L.cppf_compact_mask(mask.data_ptr(), P, surv.data_ptr(), count.data_ptr(), cws.data_ptr(), cws.numel(),
-                                       stream_ptr(dev)), "cppf_compact_mask")
+        cws = workspace(_lib.lib().cppf_compact_workspace_bytes(P), dev, "compact")
+        call("cppf_compact_mask", dev, mask, P, surv, count, scratch(cws))
     n = int(count.item())
     return surv[:n], n
 
@@ -158,20 +148,15 @@ def distinct_pairs(pc, nrm, idx):
     idx = _pairs_tensor(idx, dev)
     P = idx.shape[0]
     keep = torch.empty(max(P, 1), dtype=U8, device=dev)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        if P:
-            _lib.check(L.cppf_pair_filter_distinct(pc.data_ptr(), nrm.data_ptr(), idx.data_ptr(), 1 if idx.dtype == torch.int64 else 0,
-                                                   pc.shape[0], P, keep.data_ptr(), stream_ptr(dev)), "cppf_pair_filter_distinct")
-        pos, _ = _compact(keep[:P], dev)
+    if P:
+        call("cppf_pair_filter_distinct", dev, pc, nrm, idx, idx.dtype == torch.int64, pc.shape[0], P, keep)
+    pos, _ = _compact(keep[:P], dev)
     return idx[pos.long()]
 
 
 def _segment_enqueue(pc, outputs, idx32, T32, corner, res, dims, num_rots, tol, min_contrib):
     """back-vote at T32 + segmentation, all enqueued: (point_mask u8[N], positions i32[P], count i32[1]) device tensors"""
     dev = pc.device
-    L = _lib.lib()
-    st = stream_ptr(dev)
     N, P = pc.shape[0], idx32.shape[0]
     surv = torch.empty(max(P, 1), dtype=U8, device=dev)
     point_mask = torch.empty(N, dtype=U8, device=dev)
@@ -179,12 +164,10 @@ def _segment_enqueue(pc, outputs, idx32, T32, corner, res, dims, num_rots, tol, 
     count = torch.zeros(1, dtype=I32, device=dev)
     gx, gy, gz = (int(d) for d in dims)
     if P:
-        _lib.check(L.cppf_backvote_ws(pc.data_ptr(), outputs.data_ptr(), None, idx32.data_ptr(), corner.data_ptr(), float(res), P,
-                                      int(num_rots), gx, gy, gz, None, T32.data_ptr(), float(tol), surv.data_ptr(), None, st),
-                   "cppf_backvote_ws")
-    sws = workspace(L.cppf_segment_instance_workspace_bytes(N, P), dev, "segment")
-    _lib.check(L.cppf_segment_instance(idx32.data_ptr(), surv.data_ptr(), P, N, int(min_contrib), point_mask.data_ptr(),
-                                       pairs.data_ptr(), count.data_ptr(), sws.data_ptr(), sws.numel(), st), "cppf_segment_instance")
+        call("cppf_backvote_ws", dev, pc, outputs, None, idx32, corner, float(res), P, int(num_rots), gx, gy, gz, None, T32, float(tol),
+             surv, None)
+    sws = workspace(_lib.lib().cppf_segment_instance_workspace_bytes(N, P), dev, "segment")
+    call("cppf_segment_instance", dev, idx32, surv, P, N, int(min_contrib), point_mask, pairs, count, scratch(sws))
     return point_mask, pairs, count
 
 
@@ -207,8 +190,7 @@ def segment_instance(pc, outputs, idx, center, corner, res, dims, num_rots=72, t
     dev, pc, outputs, idx32, corner = _prep(pc, outputs, idx, corner)
     tol = float(np.float32(3 * res)) if tol is None else float(np.float32(tol))
     T32 = torch.as_tensor(np.asarray(center, np.float64).astype(np.float32)).to(dev)
-    with torch.cuda.device(dev):
-        pm, pairs, count = _segment_enqueue(pc, outputs, idx32, T32, corner, res, dims, num_rots, tol, min_contrib)
+    pm, pairs, count = _segment_enqueue(pc, outputs, idx32, T32, corner, res, dims, num_rots, tol, min_contrib)
     n = int(count.item())
     return dict(point_mask=pm.bool(), pairs=pairs[:n].long(), n_pairs=n)
 
@@ -263,42 +245,32 @@ def zero_shot_scene(encoder9, pc, nrm, feat, idx, cfg, angle_tol=2, max_rot_pair
     worlds = [corners[0].astype(np.float64) + loc[k].astype(np.int64) * float(cfg.res) for k in range(n)]
 
     # cell 11, every proposal enqueued before the one read-back
-    L = _lib.lib()
-    st = stream_ptr(dev)
     sph64, sph32_d, sph64_d = _sphere(angle_tol, dev)
     S = sph64.shape[0]
     thr = float(np.float32(np.cos(angle_tol / 180 * np.pi)))
     tol = float(np.float32(3 * cfg.res))
     if rot_order is not None:
         rot_order = torch.as_tensor(rot_order).to(device=dev, dtype=I32).contiguous()
-    rws = workspace(L.cppf_reduce_workspace_bytes(), dev, "zs_reduce")
+    rws = workspace(_lib.lib().cppf_reduce_workspace_bytes(), dev, "zs_reduce")
     recs, masks, counts_d = [], [], []
-    with torch.cuda.device(dev):
-        for k in range(n):
-            T32 = torch.as_tensor(worlds[k].astype(np.float32)).to(dev)
-            pm, sel, cnt = _segment_enqueue(pc, outputs, idx32, T32, corner, cfg.res, dims, num_rots, tol, min_contrib)
-            counts = torch.zeros(S, dtype=I32, device=dev)
-            rec = torch.zeros(10, dtype=torch.float64, device=dev)          # best_dir[3] | sign sums[3] | exp-scale sums[4]
-            best_idx = torch.empty(1, dtype=torch.int64, device=dev)
-            rot = preds.data_ptr() + 4 * 2
-            if rot_order is None:
-                _lib.check(L.cppf_rot_sphere_count(pc.data_ptr(), rot, 9, idx32.data_ptr(), sel.data_ptr(), cnt.data_ptr(), P,
-                                                   int(max_rot_pairs), int(num_rots), sph32_d.data_ptr(), S, thr, 1,
-                                                   counts.data_ptr(), st), "cppf_rot_sphere_count")
-            else:
-                _lib.check(L.cppf_rot_sphere_count_dirs_order(pc.data_ptr(), rot, 9, 1, 1, idx32.data_ptr(), sel.data_ptr(),
-                                                              cnt.data_ptr(), P, rot_order.data_ptr(), rot_order.numel(),
-                                                              int(max_rot_pairs), int(num_rots), sph32_d.data_ptr(), S, thr, 1,
-                                                              counts.data_ptr(), S, st), "cppf_rot_sphere_count_dirs_order")
-            _lib.check(L.cppf_counts_argmax_select(counts.data_ptr(), S, sph64_d.data_ptr(), best_idx.data_ptr(),
-                                                   rec[0:3].data_ptr(), st), "cppf_counts_argmax_select")
-            _lib.check(L.cppf_axis_sign(pc.data_ptr(), nrm.data_ptr(), idx32.data_ptr(), sel.data_ptr(), cnt.data_ptr(), P,
-                                        preds.data_ptr() + 4 * 4, 9, rec[0:3].data_ptr(), rec[3:6].data_ptr(), rws.data_ptr(),
-                                        rws.numel(), st), "cppf_axis_sign")
-            _lib.check(L.cppf_scale_exp_sum(preds.data_ptr() + 4 * 6, 9, sel.data_ptr(), cnt.data_ptr(), P, rec[6:10].data_ptr(),
-                                            rws.data_ptr(), rws.numel(), st), "cppf_scale_exp_sum")
-            recs.append(rec)
-            masks.append(pm)
+    for k in range(n):
+        T32 = torch.as_tensor(worlds[k].astype(np.float32)).to(dev)
+        pm, sel, cnt = _segment_enqueue(pc, outputs, idx32, T32, corner, cfg.res, dims, num_rots, tol, min_contrib)
+        counts = torch.zeros(S, dtype=I32, device=dev)
+        rec = torch.zeros(10, dtype=torch.float64, device=dev)          # best_dir[3] | sign sums[3] | exp-scale sums[4]
+        best_idx = torch.empty(1, dtype=torch.int64, device=dev)
+        rot = preds.data_ptr() + 4 * 2
+        if rot_order is None:
+            call("cppf_rot_sphere_count", dev, pc, rot, 9, idx32, sel, cnt, P, int(max_rot_pairs), int(num_rots), sph32_d, S, thr, 1,
+                 counts)
+        else:
+            call("cppf_rot_sphere_count_dirs_order", dev, pc, rot, 9, 1, 1, idx32, sel, cnt, P, rot_order, rot_order.numel(),
+                 int(max_rot_pairs), int(num_rots), sph32_d, S, thr, 1, counts, S)
+        call("cppf_counts_argmax_select", dev, counts, S, sph64_d, best_idx, rec[0:3])
+        call("cppf_axis_sign", dev, pc, nrm, idx32, sel, cnt, P, preds.data_ptr() + 4 * 4, 9, rec[0:3], rec[3:6], scratch(rws))
+        call("cppf_scale_exp_sum", dev, preds.data_ptr() + 4 * 6, 9, sel, cnt, P, rec[6:10], scratch(rws))
+        recs.append(rec)
+        masks.append(pm)
     poses = []
     for k in range(n):
         poses.append(_assemble(recs[k].cpu().numpy(), worlds[k], cfg, val[k], diff[k], masks[k].cpu().numpy().astype(bool)))

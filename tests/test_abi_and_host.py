@@ -26,6 +26,137 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert b"workspace" in L.cppf_error_string(-2)
 
 
+def _header():
+    """include/cppf.h without comments and without the CPPF_DEBUG_ENTRY block"""
+    hdr = open(os.path.join(ROOT, "include", "cppf.h")).read()
+    hdr = re.sub(r"#ifdef CPPF_DEBUG_ENTRY.*?#endif", "", hdr, flags=re.S)
+    return re.sub(r"/\*.*?\*/|//[^\n]*", " ", hdr, flags=re.S)
+
+
+_C_CLASS = {"int": "i4", "int32_t": "i4", "unsigned": "i4", "unsigned int": "i4", "uint32_t": "i4", "int64_t": "i8", "size_t": "i8",
+            "uint64_t": "i8", "long long": "i8", "unsigned long long": "i8", "float": "f4", "double": "f8"}
+
+
+def _c_class(decl, named):
+    """type class of a C parameter (`named`: the declarator carries a name) or return type: ptr / i4 / i8 / f4 / f8"""
+    if "*" in decl:
+        return "ptr"
+    words = [w for w in decl.split() if w != "const"]
+    return _C_CLASS[" ".join(words[:-1] if named else words)]          # KeyError: a type this test cannot classify -- it fails
+
+
+def _ctypes_class(t):
+    if t is None:
+        return "void"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "ptr"
+    return {"f": "f4", "d": "f8"}.get(t._type_, f"i{C.sizeof(t)}")
+
+
+def test_sigs_match_the_header_argument_by_argument():
+    """_lib._SIGS is a hand-written mirror of include/cppf.h: every prototype's return type and every argument's type class
+    (pointer / 4-byte integer / 8-byte integer / float / double) must agree, for all of them"""
+    from cppf_amd import _lib
+    protos = re.findall(r"([\w \*]+?)\b(cppf_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", _header())
+    assert len(protos) == len({p[1] for p in protos}) == len(re.findall(r"\bcppf_[a-z0-9_]+\s*\(", _header()))   # nothing the regex missed
+    assert {p[1] for p in protos} == set(_lib._SIGS) and len(protos) >= 97
+    for ret, name, args in protos:
+        res, argtypes = _lib._SIGS[name]
+        params = [a.strip() for a in args.split(",")]
+        want = [] if params == ["void"] else [_c_class(a, True) for a in params]
+        assert _ctypes_class(res) == _c_class(ret, False), f"{name}: return type"
+        assert [_ctypes_class(t) for t in argtypes] == want, f"{name}: {args}"
+
+
+_ITEMS = {"CppfPairMlpItem": "PairMlpItem", "CppfPoseTailItem": "PoseTailItem", "CppfStageItem": "StageItem",
+          "CppfFrameCloudItem": "FrameCloudItem", "CppfPointEncItem": "PointEncItem", "CppfVoteItem": "VoteItem"}
+
+
+def test_item_structs_match_the_header(tmp_path):
+    """the six ctypes item structs against the C compiler's view of include/cppf.h: field names in order, every offset, the size"""
+    import subprocess
+    from cppf_amd import _lib
+    hdr = _header()
+    lines = []
+    for cname, pyname in _ITEMS.items():
+        (body,) = re.findall(r"typedef struct(?: \w+)? \{([^{}]*)\}\s*%s;" % cname, hdr)
+        names = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            names += [re.findall(r"\w+", part.split("[")[0])[-1] for part in decl.split(",")]
+        fields = getattr(_lib, pyname)._fields_
+        assert [f[0] for f in fields] == names, cname
+        lines += [f'P("{cname}", sizeof({cname}));'] + [f'P("{cname}.{n}", offsetof({cname}, {n}));' for n in names]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include "cppf.h"\n#define P(what, n) printf("%s %lu\\n", what, (unsigned long)(n))\n'
+                   "int main(void)\n{\n    " + "\n    ".join(lines) + "\n    return 0;\n}\n")
+    exe = str(tmp_path / "layout")
+    p = subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I" + os.path.join(ROOT, "include"), str(src), "-o", exe],
+                       capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr
+    got = dict(line.split() for line in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines())
+    for cname, pyname in _ITEMS.items():
+        T = getattr(_lib, pyname)
+        assert C.sizeof(T) == int(got[cname]), cname
+        for n, _ in T._fields_:
+            assert getattr(T, n).offset == int(got[f"{cname}.{n}"]), f"{cname}.{n}"
+    assert len(got) == sum(1 + len(getattr(_lib, v)._fields_) for v in _ITEMS.values())
+
+
+class _FakeLib:
+    """stands in for libcppf_hip.so under _torch_util.call: records what ctypes would be handed"""
+
+    def __init__(self, rc=0):
+        self.rc, self.calls = rc, []
+
+    def __getattr__(self, name):
+        if not name.startswith("cppf_"):
+            raise AttributeError(name)
+        return lambda *args: (self.calls.append((name, args)), self.rc)[1]
+
+    def cppf_error_string(self, rc):
+        return b"fake error"
+
+
+def test_call_helper_converts_arguments_and_reports_errors(monkeypatch):
+    """_torch_util.call / fill on a fake library and the host-only form (no device): one conversion for every call site"""
+    from cppf_amd import _lib, _torch_util as tu
+    fake = _FakeLib()
+    monkeypatch.setattr(_lib, "_lib", fake)
+    t = torch.arange(6, dtype=torch.float32)
+    a = np.arange(6, dtype=np.int64).reshape(2, 3)
+    ws = torch.empty(320, dtype=torch.uint8)
+    ptrs = (C.c_void_p * 2)(1, 2)
+    assert tu.call("cppf_x", None, t, t[2:], a, None, True, False, 7, 0.5, ptrs, tu.scratch(ws), 3) == 0
+    assert fake.calls == [("cppf_x", (t.data_ptr(), t.data_ptr() + 8, a.ctypes.data, None, 1, 0, 7, 0.5, ptrs, ws.data_ptr(), 320, 3))]
+    assert all(type(v) is int for v in fake.calls[0][1][4:6])
+    with pytest.raises(ValueError, match="C-contiguous"):
+        tu.call("cppf_x", None, a.T)
+    with pytest.raises(ValueError, match="C-contiguous"):
+        tu.call("cppf_x", None, a[:, ::2])
+    assert len(fake.calls) == 1                                   # a refused argument: no call was made
+    # a non-zero return raises CppfError naming the function that was called, unless the code is allowed
+    fake.rc = _lib.ECAPACITY
+    with pytest.raises(_lib.CppfError, match=r"cppf_raster_depth failed \(-5\): fake error"):
+        tu.call("cppf_raster_depth", None, t)
+    assert tu.call("cppf_raster_depth", None, t, ok=(_lib.ECAPACITY,)) == -5
+    with pytest.raises(_lib.CppfError, match="cppf_other failed"):
+        tu.call("cppf_other", None, t, ok=(_lib.ENONFINITE,))
+    assert (_lib.EUNSUPPORTED, _lib.ENONFINITE, _lib.ECAPACITY) == (-3, -4, -5)
+    with pytest.raises(AttributeError):
+        tu.call("no_such_function", None)
+    # the struct filler: the same conversion, a scratch buffer fills field and field_bytes, unknown names raise
+    item = tu.fill(_lib.PoseTailItem(), pc=t, idx64=None, mlp_workspace=tu.scratch(ws), n_pairs=5, res=0.25, second_pass=True,
+                   feat=a, scale_mean=(C.c_double * 3)(1.0, 2.0, 3.0))
+    assert (item.pc, item.idx64, item.mlp_workspace, item.mlp_workspace_bytes) == (t.data_ptr(), None, ws.data_ptr(), 320)
+    assert (item.n_pairs, item.res, item.second_pass, item.feat, list(item.scale_mean)) == (5, 0.25, 1, a.ctypes.data, [1.0, 2.0, 3.0])
+    with pytest.raises(AttributeError, match="no field 'n_pair'"):
+        tu.fill(item, n_pair=5)
+    with pytest.raises(AttributeError, match="no field 'pc_bytes'"):
+        tu.fill(item, pc=tu.scratch(ws))
+    with pytest.raises(ValueError, match="C-contiguous"):
+        tu.fill(item, feat=a.T)
+
+
 def test_workspace_queries_and_argument_errors_without_a_device():
     from cppf_amd import _lib
     L = _lib.lib()
