@@ -608,46 +608,54 @@ extern "C" int cppf_rot_voting(const float* points, const float* preds_rot, floa
     return 0;
 }
 
-// Fused rot_voting + sphere count (nocs/inference.py:265-284): candidates of SPH_PPB pairs go to
-// LDS, then every lane owns sphere bins and sweeps the block's candidates (broadcast LDS reads),
-// cos = fma(c.z,s.z, fma(c.y,s.y, c.x*s.x)) > thr.  Integer atomics: deterministic counts.
+// Fused rot_voting + sphere count (nocs/inference.py:265-284).  One argument block, by value, for every kernel of the count: the
+// single calls fill it from the C ABI, the batched tail from a TailItem and the TailBatch's shared fields.
+struct SphereCountArgs {
+    const float *points, *preds_rot, *sphere;
+    const int32_t *point_idxs, *sel, *n_sel_dev, *order;   // sel null: the pairs themselves; order null: the survivors in their order
+    int32_t* counts;
+    int64_t n_sel_host, max_pairs, n_order;
+    int rot_stride, rot_dir_step, n_rots, n_sphere, counts_dir_step, descending;
+    float thr;
+};
+// Slot k of a count -> the frame of its pair.  A slot is position k of the survivor list (n_avail entries of sel, or pairs when sel
+// is null), with an `order` position order[k] of it; an entry of the order outside the list is a pad slot and contributes nothing.
+__device__ __forceinline__ RotFrame sphere_slot_frame(const SphereCountArgs& A, const float* __restrict__ preds_rot,
+                                                      const int32_t* __restrict__ order, int64_t k, int64_t n_avail)
+{
+    const int64_t sl = order ? (int64_t)order[k] : k;
+    if (sl < 0 || sl >= n_avail) {
+        RotFrame fr;
+        fr.ok = 0;
+        fr.pad = 1;
+        return fr;
+    }
+    const int p = A.sel ? A.sel[sl] : (int)sl;
+    const int2 ij = reinterpret_cast<const int2*>(A.point_idxs)[p];
+    return rot_frame(A.points, ij.x, ij.y, preds_rot[(int64_t)p * A.rot_stride]);
+}
+
+// Candidates of SPH_PPB pairs go to LDS, then every lane owns sphere bins and sweeps the block's candidates (broadcast LDS
+// reads), cos = fma(c.z,s.z, fma(c.y,s.y, c.x*s.x)) > thr.  Integer atomics: deterministic counts.
 #define SPH_PPB 16
 #define SPH_THREADS 512
-__global__ __launch_bounds__(SPH_THREADS) void rot_sphere_kernel(const float* __restrict__ points,
-                                                                 const float* __restrict__ preds_rot, int rot_stride,
-                                                                 const int32_t* __restrict__ point_idxs,
-                                                                 const int32_t* __restrict__ sel,
-                                                                 const int32_t* __restrict__ n_sel_dev,
-                                                                 int64_t n_sel_host, int64_t max_pairs, int n_rots,
-                                                                 const float* __restrict__ sphere, int n_sphere,
-                                                                 float thr, int32_t* __restrict__ counts,
-                                                                 int rot_dir_step, int counts_dir_step,
-                                                                 const int32_t* __restrict__ order, int64_t n_order)
+__global__ __launch_bounds__(SPH_THREADS) void rot_sphere_kernel(SphereCountArgs A)
 {
-    preds_rot += (int64_t)blockIdx.y * rot_dir_step;
-    counts += (int64_t)blockIdx.y * counts_dir_step;
+    const float* preds_rot = A.preds_rot + (int64_t)blockIdx.y * A.rot_dir_step;   // direction blockIdx.y of the launch
+    int32_t* counts = A.counts + (int64_t)blockIdx.y * A.counts_dir_step;
+    const int n_rots = A.n_rots;
     __shared__ RotFrame frames[SPH_PPB];
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float4* cand = reinterpret_cast<float4*>(lds);                       // [SPH_PPB*n_rots]
     float2* row = reinterpret_cast<float2*>(lds + 4 * SPH_PPB * n_rots);  // [n_rots]
-    const int64_t n_avail = n_sel_dev ? (int64_t)*n_sel_dev : n_sel_host;   // entries of sel (or pairs, sel == null)
-    int64_t n_sel = order ? n_order : n_avail;                               // slots of this count
-    if (n_sel > max_pairs) n_sel = max_pairs;
+    const int64_t n_avail = A.n_sel_dev ? (int64_t)*A.n_sel_dev : A.n_sel_host;   // entries of sel (or pairs, sel == null)
+    int64_t n_sel = A.order ? A.n_order : n_avail;                                 // slots of this count
+    if (n_sel > A.max_pairs) n_sel = A.max_pairs;
     const int64_t k0 = (int64_t)blockIdx.x * SPH_PPB;
     if (k0 >= n_sel) return;
     const int np = (int)min((int64_t)SPH_PPB, n_sel - k0);
     for (int i = threadIdx.x; i < n_rots; i += SPH_THREADS) row[i] = rot_cs(i, n_rots);
-    if ((int)threadIdx.x < np) {
-        const int64_t sl = order ? (int64_t)order[k0 + threadIdx.x] : k0 + threadIdx.x;   // position in the survivor list
-        if (sl >= 0 && sl < n_avail) {
-            const int p = sel ? sel[sl] : (int)sl;
-            const int2 ij = reinterpret_cast<const int2*>(point_idxs)[p];
-            frames[threadIdx.x] = rot_frame(points, ij.x, ij.y, preds_rot[(int64_t)p * rot_stride]);
-        } else {
-            frames[threadIdx.x].ok = 0;
-            frames[threadIdx.x].pad = 1;
-        }
-    }
+    if ((int)threadIdx.x < np) frames[threadIdx.x] = sphere_slot_frame(A, preds_rot, A.order, k0 + threadIdx.x, n_avail);
     __syncthreads();
     const int items = np * n_rots;
     for (int k = threadIdx.x; k < items; k += SPH_THREADS) {
@@ -657,13 +665,13 @@ __global__ __launch_bounds__(SPH_THREADS) void rot_sphere_kernel(const float* __
         cand[k] = make_float4(up.x, up.y, up.z, frames[pl].pad ? 1.f : 0.f);
     }
     __syncthreads();
-    for (int j = threadIdx.x; j < n_sphere; j += SPH_THREADS) {
-        const float sx = sphere[3 * j], sy = sphere[3 * j + 1], sz = sphere[3 * j + 2];
+    for (int j = threadIdx.x; j < A.n_sphere; j += SPH_THREADS) {
+        const float sx = A.sphere[3 * j], sy = A.sphere[3 * j + 1], sz = A.sphere[3 * j + 2];
         int cnt = 0;
         for (int k = 0; k < items; ++k) {
             const float4 c = cand[k];
             const float d = fmaf(c.z, sz, fmaf(c.y, sy, c.x * sx));
-            cnt += (d > thr) && c.w == 0.f;
+            cnt += (d > A.thr) && c.w == 0.f;
         }
         if (cnt) atomicAdd(&counts[j], cnt);
     }
@@ -673,144 +681,111 @@ __global__ __launch_bounds__(SPH_THREADS) void rot_sphere_kernel(const float* __
 // utils/util.py:102-118 is): a candidate c can only match bins with |s.y - c.y| < sqrt(2 - 2 thr), so
 // each lane takes candidates and tests only that band of bins (~14 of 480 at 1.5 deg) instead of every
 // lane sweeping every candidate.  Same dot product, same threshold test -> identical counts.
-#define SPHB_PPB 8   // most pairs per group; few survivors are taken 2 at a time, see the kernel
-__device__ __forceinline__ void rot_sphere_band_body(const float* __restrict__ points,
-                                                              const float* __restrict__ preds_rot, int rot_stride,
-                                                              const int32_t* __restrict__ point_idxs,
-                                                              const int32_t* __restrict__ sel,
-                                                              const int32_t* __restrict__ n_sel_dev, int64_t n_sel_host,
-                                                              int64_t max_pairs, int n_rots,
-                                                              const float* __restrict__ sphere, int n_sphere, float thr,
-                                                              int32_t* __restrict__ counts, int descending,
-                                                              int rot_dir_step, int counts_dir_step,
-                                                              const int32_t* __restrict__ order, int64_t n_order)
+__device__ __forceinline__ float sphere_band_halfwidth(float thr)
 {
-    preds_rot += (int64_t)blockIdx.y * rot_dir_step;   // cppf_rot_sphere_count_dirs: direction blockIdx.y of the launch
-    counts += (int64_t)blockIdx.y * counts_dir_step;
-    __shared__ RotFrame frames[SPHB_PPB];
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* sph = lds;                                             // [n_sphere][3]
-    int* cnt = reinterpret_cast<int*>(lds + 3 * n_sphere);        // [n_sphere]
-    float2* row = reinterpret_cast<float2*>(cnt + n_sphere);      // [n_rots]
-    const int64_t n_avail = n_sel_dev ? (int64_t)*n_sel_dev : n_sel_host;   // entries of sel (or pairs, sel == null)
-    int64_t n_sel = order ? n_order : n_avail;                               // slots of this count
-    if (n_sel > max_pairs) n_sel = max_pairs;
-    const int ppb = n_sel > 4096 ? SPHB_PPB : 2;   // (uniform over the launch)
-    if ((int64_t)blockIdx.x * ppb >= n_sel) return;
-    for (int i = threadIdx.x; i < 3 * n_sphere; i += 256) sph[i] = sphere[i];
-    for (int i = threadIdx.x; i < n_sphere; i += 256) cnt[i] = 0;
-    for (int i = threadIdx.x; i < n_rots; i += 256) row[i] = rot_cs(i, n_rots);
-    float band = 2.f - 2.f * thr;
-    band = sqrtf(fminf(fmaxf(band, 0.f), 4.f) + 1e-5f) + 1e-4f;
-    // A block takes groups of ppb pairs, blockIdx, + gridDim, ...  A group's time is a chain (frame with an fp64 tangent ->
-    // candidate -> binary search -> ~14 dependent band steps) that only more groups in flight hide, so few survivors go 2 to a
-    // group (the ~2 000 of the benchmark object: 15.7 -> 12.2 us; 500: 13.4 -> 8.5), many go 8 to a group for throughput, and the
-    // grid is bounded so that the block's set-up (bins, rotation row) is paid once when it has several groups.
-    for (int64_t k0 = (int64_t)blockIdx.x * ppb; k0 < n_sel; k0 += (int64_t)gridDim.x * ppb) {
-    const int np = (int)min((int64_t)ppb, n_sel - k0);
-    __syncthreads();   // (previous group's frames are no longer read; first trip: the tables above are complete)
-    if ((int)threadIdx.x < np) {
-        const int64_t sl = order ? (int64_t)order[k0 + threadIdx.x] : k0 + threadIdx.x;   // position in the survivor list
-        if (sl >= 0 && sl < n_avail) {
-            const int p = sel ? sel[sl] : (int)sl;
-            const int2 ij = reinterpret_cast<const int2*>(point_idxs)[p];
-            frames[threadIdx.x] = rot_frame(points, ij.x, ij.y, preds_rot[(int64_t)p * rot_stride]);
-        } else {
-            frames[threadIdx.x].ok = 0;
-            frames[threadIdx.x].pad = 1;
-        }
+    const float band = 2.f - 2.f * thr;
+    return sqrtf(fminf(fmaxf(band, 0.f), 4.f) + 1e-5f) + 1e-4f;
+}
+// One candidate against the bins with y in [up.y - band, up.y + band]: a binary search on the sorted y column for the first of
+// them, then the walk to the band's other end.  sph: the bins in LDS as {x, y, z, -} (one LDS read per band step), cnt: their counts.
+__device__ __forceinline__ void sphere_band_count(const f3 up, const float4* sph, int n_sphere, int descending, float band, float thr,
+                                                  int* cnt)
+{
+    const float ylo = up.y - band, yhi = up.y + band;
+    int lo = 0, hi = n_sphere;  // first bin inside the band
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        const float y = sph[mid].y;
+        const bool before = descending ? (y > yhi) : (y < ylo);
+        if (before) lo = mid + 1; else hi = mid;
     }
-    __syncthreads();
-    const int items = np * n_rots;
-    for (int k = threadIdx.x; k < items; k += 256) {
-        const int pl = k / n_rots, i = k - pl * n_rots;
-        if (frames[pl].pad) continue;
-        f3 up = {0.f, 0.f, 0.f};
-        if (frames[pl].ok) up = rot_candidate(frames[pl], row[i]);
-        // bins with y in [up.y - band, up.y + band]: binary searches on the sorted y column
-        const float ylo = up.y - band, yhi = up.y + band;
-        int lo = 0, hi = n_sphere;  // first bin inside the band
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            const float y = sph[3 * mid + 1];
-            const bool before = descending ? (y > yhi) : (y < ylo);
-            if (before) lo = mid + 1; else hi = mid;
-        }
-        for (int j = lo; j < n_sphere; ++j) {
-            const float sy = sph[3 * j + 1];
-            if (descending ? (sy < ylo) : (sy > yhi)) break;
-            const float d = fmaf(up.z, sph[3 * j + 2], fmaf(up.y, sy, up.x * sph[3 * j]));
-            if (d > thr) atomicAdd(&cnt[j], 1);
-        }
+    for (int j = lo; j < n_sphere; ++j) {
+        const float4 sb = sph[j];
+        if (descending ? (sb.y < ylo) : (sb.y > yhi)) break;
+        const float d = fmaf(up.z, sb.z, fmaf(up.y, sb.y, up.x * sb.x));
+        if (d > thr) atomicAdd(&cnt[j], 1);
     }
-    }
-    __syncthreads();
-    for (int j = threadIdx.x; j < n_sphere; j += 256)
-        if (cnt[j]) atomicAdd(&counts[j], cnt[j]);
+}
+// Dynamic LDS of the banded kernels: float4 bins | float2 (cos, sin) row | int counts, every region aligned for any n_sphere.
+static size_t sphere_band_lds(int n_sphere, int n_rots)
+{
+    return (size_t)n_sphere * (sizeof(float4) + sizeof(int)) + (size_t)n_rots * sizeof(float2);
+}
+// 4 096 bins x 20 B + the rotation row is above the 64 KB a launch gets unasked: raised once per kernel, before its first such launch.
+template <auto Kernel>
+static void sphere_band_allow_lds(size_t lds)
+{
+    static bool raised = false;
+    if (lds <= 64 * 1024 || raised) return;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+    raised = true;
 }
 
-// The same count for launches that serve several instances at once (cppf_pose_tail_batch).  rot_sphere_band_body's blocks take groups
-// of 2 or 8 pairs -- tuned for ONE instance on an idle chip, where a group is a latency chain and only more groups in flight hide
-// it -- and every block pays the set-up (the 480 bins, the rotation row in fp64, the flush) for 144 or 576 candidates: as much
-// work as the candidates themselves.  In a chain of 4-8 instances beside other lanes the chip is full anyway and total work is what
-// counts: here a block owns a CONTIGUOUS share of the survivors (<= 256 blocks per instance and direction), computes the frames of up
-// to 64 pairs in one step and sweeps their candidates with full lanes; bins as float4 (one LDS read per band step instead of three).
+// The banded count of a workgroup; the two schedules differ in which slots a workgroup takes and how many per step, nothing else.
+//
+// EVEN = false, the single calls: a block takes groups of ppb pairs, blockIdx, + gridDim, ...  A group's time is a chain (frame with
+// an fp64 tangent -> candidate -> binary search -> ~14 dependent band steps) that only more groups in flight hide, so few survivors
+// go 2 to a group (the ~2 000 of the benchmark object: 15.7 -> 12.2 us; 500: 13.4 -> 8.5), many go 8 to a group for throughput, and
+// the grid is bounded (2 048 blocks) so that the block's set-up (bins, rotation row) is paid once when it has several groups.
+//
+// EVEN = true, launches that serve several instances at once (cppf_pose_tail_batch).  The groups of 2 or 8 are tuned for ONE instance
+// on an idle chip, and every block pays the set-up (the 480 bins, the rotation row in fp64, the flush) for 144 or 576 candidates: as
+// much work as the candidates themselves.  In a chain of 4-8 instances beside other lanes the chip is full anyway and total work is
+// what counts: here a block owns a CONTIGUOUS share of the survivors (<= SPHE_BLOCKS blocks per instance and direction), computes the
+// frames of up to SPHE_PAIRS pairs in one step and sweeps their candidates with full lanes.  It ignores `order`: the chain has none.
 // Same candidates, same dot products, same threshold test, integer counts: identical results.
+#define SPHB_PPB 8   // most pairs per group of the single calls; few survivors are taken 2 at a time
 #define SPHE_PAIRS 64
 #define SPHE_BLOCKS 256
-__device__ __forceinline__ void rot_sphere_band_even_body(const float* __restrict__ points, const float* __restrict__ preds_rot,
-                                                          int rot_stride, const int32_t* __restrict__ point_idxs,
-                                                          const int32_t* __restrict__ sel, const int32_t* __restrict__ n_sel_dev,
-                                                          int64_t n_sel_host, int64_t max_pairs, int n_rots,
-                                                          const float* __restrict__ sphere, int n_sphere, float thr,
-                                                          int32_t* __restrict__ counts, int descending, int rot_dir_step,
-                                                          int counts_dir_step)
+template <bool EVEN>
+__device__ __forceinline__ void rot_sphere_band_body(const SphereCountArgs& A)
 {
-    preds_rot += (int64_t)blockIdx.y * rot_dir_step;
-    counts += (int64_t)blockIdx.y * counts_dir_step;
-    __shared__ RotFrame frames[SPHE_PAIRS];
+    const float* preds_rot = A.preds_rot + (int64_t)blockIdx.y * A.rot_dir_step;   // cppf_rot_sphere_count_dirs: direction blockIdx.y of the launch
+    int32_t* counts = A.counts + (int64_t)blockIdx.y * A.counts_dir_step;
+    const int32_t* order = EVEN ? nullptr : A.order;
+    const int n_rots = A.n_rots, n_sphere = A.n_sphere;
+    __shared__ RotFrame frames[EVEN ? SPHE_PAIRS : SPHB_PPB];
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    float4* sph4 = reinterpret_cast<float4*>(lds);                // [n_sphere] {x, y, z, -}
-    int* cnt = reinterpret_cast<int*>(lds + 4 * n_sphere);        // [n_sphere]
-    float2* row = reinterpret_cast<float2*>(cnt + n_sphere);      // [n_rots]
-    const int64_t n_avail = n_sel_dev ? (int64_t)*n_sel_dev : n_sel_host;
-    const int64_t n_sel = n_avail < max_pairs ? n_avail : max_pairs;
-    const int64_t per = (n_sel + gridDim.x - 1) / gridDim.x;
-    const int64_t k_begin = (int64_t)blockIdx.x * per, k_end = k_begin + per < n_sel ? k_begin + per : n_sel;
+    float4* sph = reinterpret_cast<float4*>(lds);                 // [n_sphere] {x, y, z, -}     (sphere_band_lds)
+    float2* row = reinterpret_cast<float2*>(sph + n_sphere);      // [n_rots]
+    int* cnt = reinterpret_cast<int*>(row + n_rots);              // [n_sphere]
+    const int64_t n_avail = A.n_sel_dev ? (int64_t)*A.n_sel_dev : A.n_sel_host;   // entries of sel (or pairs, sel == null)
+    int64_t n_sel = order ? A.n_order : n_avail;                                   // slots of this count
+    if (n_sel > A.max_pairs) n_sel = A.max_pairs;
+    // this block's slots: `step` at a time from k_begin, + stride, ... below k_end
+    int64_t k_begin, k_end, stride;
+    int step;
+    if (EVEN) {
+        const int64_t per = (n_sel + gridDim.x - 1) / gridDim.x;
+        k_begin = (int64_t)blockIdx.x * per;
+        k_end = k_begin + per < n_sel ? k_begin + per : n_sel;
+        step = SPHE_PAIRS;
+        stride = SPHE_PAIRS;
+    } else {
+        step = n_sel > 4096 ? SPHB_PPB : 2;   // (uniform over the launch)
+        k_begin = (int64_t)blockIdx.x * step;
+        k_end = n_sel;
+        stride = (int64_t)gridDim.x * step;
+    }
     if (k_begin >= k_end) return;
-    for (int i = threadIdx.x; i < n_sphere; i += 256) { sph4[i] = make_float4(sphere[3 * i], sphere[3 * i + 1], sphere[3 * i + 2], 0.f); cnt[i] = 0; }
+    for (int i = threadIdx.x; i < n_sphere; i += 256) {
+        sph[i] = make_float4(A.sphere[3 * i], A.sphere[3 * i + 1], A.sphere[3 * i + 2], 0.f);
+        cnt[i] = 0;
+    }
     for (int i = threadIdx.x; i < n_rots; i += 256) row[i] = rot_cs(i, n_rots);
-    float band = 2.f - 2.f * thr;
-    band = sqrtf(fminf(fmaxf(band, 0.f), 4.f) + 1e-5f) + 1e-4f;
-    for (int64_t k0 = k_begin; k0 < k_end; k0 += SPHE_PAIRS) {
-        const int np = (int)min((int64_t)SPHE_PAIRS, k_end - k0);
-        __syncthreads();   // (previous round's frames are no longer read; first trip: the tables above are complete)
-        if ((int)threadIdx.x < np) {
-            const int64_t sl = k0 + threadIdx.x;
-            const int p = sel ? sel[sl] : (int)sl;
-            const int2 ij = reinterpret_cast<const int2*>(point_idxs)[p];
-            frames[threadIdx.x] = rot_frame(points, ij.x, ij.y, preds_rot[(int64_t)p * rot_stride]);
-        }
+    const float band = sphere_band_halfwidth(A.thr);
+    for (int64_t k0 = k_begin; k0 < k_end; k0 += stride) {
+        const int np = (int)min((int64_t)step, k_end - k0);
+        __syncthreads();   // (previous step's frames are no longer read; first trip: the tables above are complete)
+        if ((int)threadIdx.x < np) frames[threadIdx.x] = sphere_slot_frame(A, preds_rot, order, k0 + threadIdx.x, n_avail);
         __syncthreads();
         const int items = np * n_rots;
         for (int k = threadIdx.x; k < items; k += 256) {
             const int pl = k / n_rots, i = k - pl * n_rots;
-            f3 up = {0.f, 0.f, 0.f};
+            if (frames[pl].pad) continue;
+            f3 up = {0.f, 0.f, 0.f};  // degenerate pair, as in rot_sphere_kernel
             if (frames[pl].ok) up = rot_candidate(frames[pl], row[i]);
-            const float ylo = up.y - band, yhi = up.y + band;
-            int lo = 0, hi = n_sphere;
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                const float y = sph4[mid].y;
-                const bool before = descending ? (y > yhi) : (y < ylo);
-                if (before) lo = mid + 1; else hi = mid;
-            }
-            for (int j = lo; j < n_sphere; ++j) {
-                const float4 sb = sph4[j];
-                if (descending ? (sb.y < ylo) : (sb.y > yhi)) break;
-                const float d = fmaf(up.z, sb.z, fmaf(up.y, sb.y, up.x * sb.x));
-                if (d > thr) atomicAdd(&cnt[j], 1);
-            }
+            sphere_band_count(up, sph, n_sphere, A.descending, band, A.thr, cnt);
         }
     }
     __syncthreads();
@@ -818,48 +793,37 @@ __device__ __forceinline__ void rot_sphere_band_even_body(const float* __restric
         if (cnt[j]) atomicAdd(&counts[j], cnt[j]);
 }
 
-__global__ __launch_bounds__(256) void rot_sphere_band_kernel(const float* __restrict__ points, const float* __restrict__ preds_rot,
-                                                              int rot_stride, const int32_t* __restrict__ point_idxs,
-                                                              const int32_t* __restrict__ sel, const int32_t* __restrict__ n_sel_dev,
-                                                              int64_t n_sel_host, int64_t max_pairs, int n_rots,
-                                                              const float* __restrict__ sphere, int n_sphere, float thr,
-                                                              int32_t* __restrict__ counts, int descending, int rot_dir_step,
-                                                              int counts_dir_step, const int32_t* __restrict__ order, int64_t n_order)
+__global__ __launch_bounds__(256) void rot_sphere_band_kernel(SphereCountArgs A)
 {
-    rot_sphere_band_body(points, preds_rot, rot_stride, point_idxs, sel, n_sel_dev, n_sel_host, max_pairs, n_rots, sphere, n_sphere, thr,
-                         counts, descending, rot_dir_step, counts_dir_step, order, n_order);
+    rot_sphere_band_body<false>(A);
 }
 
-static int rot_sphere_impl(const float* points, const float* preds_rot, int rot_stride, int rot_dir_step, int n_dirs,
-                           const int32_t* point_idxs, const int32_t* sel, const int32_t* n_sel_dev,
-                           int64_t n_sel_host, int64_t max_pairs, int n_rots, const float* sphere,
-                           int n_sphere, float thr, int sphere_sorted_by_y, int32_t* counts, int counts_dir_step, void* stream,
-                           const int32_t* order = nullptr, int64_t n_order = 0)
+// sorted: 0 = bins in any order (full sweep), > 0 / < 0 = unit bins sorted by y, descending / ascending (banded search)
+static int rot_sphere_impl(const SphereCountArgs& args, int n_dirs, int sorted, void* stream)
 {
-    if (!points || !preds_rot || !point_idxs || !sphere || !counts) return CPPF_EINVAL;
-    if (n_order < 0) return CPPF_EINVAL;
-    if (!order) n_order = 0;
-    if (n_rots < 1 || n_rots > 512 || n_sphere < 1 || max_pairs < 0 || n_sel_host < 0 || rot_stride < 1 || n_dirs < 1 ||
+    SphereCountArgs A = args;
+    if (!A.points || !A.preds_rot || !A.point_idxs || !A.sphere || !A.counts) return CPPF_EINVAL;
+    if (A.n_order < 0) return CPPF_EINVAL;
+    if (!A.order) A.n_order = 0;
+    if (A.n_rots < 1 || A.n_rots > 512 || A.n_sphere < 1 || A.max_pairs < 0 || A.n_sel_host < 0 || A.rot_stride < 1 || n_dirs < 1 ||
         n_dirs > 16)
         return CPPF_EINVAL;
-    const int64_t slots = order ? n_order : n_sel_host;      // (with an order the slots are the order's)
-    int64_t bound = slots < max_pairs ? slots : max_pairs;
+    const int64_t slots = A.order ? A.n_order : A.n_sel_host;      // (with an order the slots are the order's)
+    const int64_t bound = slots < A.max_pairs ? slots : A.max_pairs;
     if (bound == 0) return 0;
-    if (sphere_sorted_by_y != 0 && n_sphere <= 4096) {
+    A.descending = sorted > 0 ? 1 : 0;
+    if (sorted != 0 && A.n_sphere <= 4096) {
         int64_t nb = (bound + 1) / 2;
         if (nb > 2048) nb = 2048;
-        const size_t lds = (size_t)(4 * n_sphere + 2 * n_rots) * sizeof(float);
-        hipLaunchKernelGGL(rot_sphere_band_kernel, dim3((unsigned)nb, (unsigned)n_dirs), dim3(256), lds, (hipStream_t)stream, points,
-                           preds_rot, rot_stride, point_idxs, sel, n_sel_dev, n_sel_host, max_pairs, n_rots, sphere,
-                           n_sphere, thr, counts, sphere_sorted_by_y > 0 ? 1 : 0, rot_dir_step, counts_dir_step, order, n_order);
+        const size_t lds = sphere_band_lds(A.n_sphere, A.n_rots);
+        sphere_band_allow_lds<&rot_sphere_band_kernel>(lds);
+        hipLaunchKernelGGL(rot_sphere_band_kernel, dim3((unsigned)nb, (unsigned)n_dirs), dim3(256), lds, (hipStream_t)stream, A);
         CPPF_CHECK_LAUNCH();
         return 0;
     }
     const int64_t nb = (bound + SPH_PPB - 1) / SPH_PPB;
-    const size_t lds = (size_t)(4 * SPH_PPB * n_rots + 2 * n_rots) * sizeof(float);
-    hipLaunchKernelGGL(rot_sphere_kernel, dim3((unsigned)nb, (unsigned)n_dirs), dim3(SPH_THREADS), lds, (hipStream_t)stream, points,
-                       preds_rot, rot_stride, point_idxs, sel, n_sel_dev, n_sel_host, max_pairs, n_rots, sphere,
-                       n_sphere, thr, counts, rot_dir_step, counts_dir_step, order, n_order);
+    const size_t lds = (size_t)(4 * SPH_PPB * A.n_rots + 2 * A.n_rots) * sizeof(float);
+    hipLaunchKernelGGL(rot_sphere_kernel, dim3((unsigned)nb, (unsigned)n_dirs), dim3(SPH_THREADS), lds, (hipStream_t)stream, A);
     CPPF_CHECK_LAUNCH();
     return 0;
 }
@@ -869,8 +833,11 @@ extern "C" int cppf_rot_sphere_count(const float* points, const float* preds_rot
                                      int64_t n_sel_host, int64_t max_pairs, int n_rots, const float* sphere,
                                      int n_sphere, float thr, int sphere_sorted_by_y, int32_t* counts, void* stream)
 {
-    return rot_sphere_impl(points, preds_rot, rot_stride, 0, 1, point_idxs, sel, n_sel_dev, n_sel_host, max_pairs, n_rots,
-                           sphere, n_sphere, thr, sphere_sorted_by_y, counts, 0, stream);
+    SphereCountArgs A = {};
+    A.points = points; A.preds_rot = preds_rot; A.rot_stride = rot_stride; A.point_idxs = point_idxs; A.sel = sel;
+    A.n_sel_dev = n_sel_dev; A.n_sel_host = n_sel_host; A.max_pairs = max_pairs; A.n_rots = n_rots; A.sphere = sphere;
+    A.n_sphere = n_sphere; A.thr = thr; A.counts = counts;
+    return rot_sphere_impl(A, 1, sphere_sorted_by_y, stream);
 }
 
 extern "C" int cppf_rot_sphere_count_dirs(const float* points, const float* preds_rot, int rot_stride, int rot_dir_step,
@@ -880,8 +847,11 @@ extern "C" int cppf_rot_sphere_count_dirs(const float* points, const float* pred
                                           int32_t* counts, int counts_dir_step, void* stream)
 {
     if (n_dirs > 1 && (rot_dir_step < 1 || counts_dir_step < n_sphere)) return CPPF_EINVAL;
-    return rot_sphere_impl(points, preds_rot, rot_stride, rot_dir_step, n_dirs, point_idxs, sel, n_sel_dev, n_sel_host,
-                           max_pairs, n_rots, sphere, n_sphere, thr, sphere_sorted_by_y, counts, counts_dir_step, stream);
+    SphereCountArgs A = {};
+    A.points = points; A.preds_rot = preds_rot; A.rot_stride = rot_stride; A.rot_dir_step = rot_dir_step; A.point_idxs = point_idxs;
+    A.sel = sel; A.n_sel_dev = n_sel_dev; A.n_sel_host = n_sel_host; A.max_pairs = max_pairs; A.n_rots = n_rots; A.sphere = sphere;
+    A.n_sphere = n_sphere; A.thr = thr; A.counts = counts; A.counts_dir_step = counts_dir_step;
+    return rot_sphere_impl(A, n_dirs, sphere_sorted_by_y, stream);
 }
 
 extern "C" int cppf_rot_sphere_count_dirs_order(const float* points, const float* preds_rot, int rot_stride, int rot_dir_step,
@@ -893,9 +863,11 @@ extern "C" int cppf_rot_sphere_count_dirs_order(const float* points, const float
 {
     if (n_dirs > 1 && (rot_dir_step < 1 || counts_dir_step < n_sphere)) return CPPF_EINVAL;
     if (!order) return CPPF_EINVAL;
-    return rot_sphere_impl(points, preds_rot, rot_stride, rot_dir_step, n_dirs, point_idxs, sel, n_sel_dev, n_sel_host,
-                           max_pairs, n_rots, sphere, n_sphere, thr, sphere_sorted_by_y, counts, counts_dir_step, stream,
-                           order, n_order);
+    SphereCountArgs A = {};
+    A.points = points; A.preds_rot = preds_rot; A.rot_stride = rot_stride; A.rot_dir_step = rot_dir_step; A.point_idxs = point_idxs;
+    A.sel = sel; A.n_sel_dev = n_sel_dev; A.n_sel_host = n_sel_host; A.order = order; A.n_order = n_order; A.max_pairs = max_pairs;
+    A.n_rots = n_rots; A.sphere = sphere; A.n_sphere = n_sphere; A.thr = thr; A.counts = counts; A.counts_dir_step = counts_dir_step;
+    return rot_sphere_impl(A, n_dirs, sphere_sorted_by_y, stream);
 }
 
 // ----------------------------------------------------------------------------- pose-tail reductions
@@ -1269,7 +1241,7 @@ struct TailItem {
 };
 struct TailBatch {
     TailItem item[TAIL_BATCH_MAX];
-    int n, n_rots, n_sphere, descending, sphere_legacy;
+    int n, n_rots, n_sphere, descending;
     int64_t max_rot_pairs;
     const float* sphere32;
     float thr;
@@ -1296,12 +1268,11 @@ __global__ __launch_bounds__(256) void rot_sphere_band_batch_kernel(TailBatch B)
 {
     const TailItem& I = B.item[blockIdx.z];
     if ((int)blockIdx.y >= I.n_dirs) return;
-    if (B.sphere_legacy)
-        rot_sphere_band_body(I.points, I.heads, 8, I.idx32, I.surv, I.count, I.n_ppfs, B.max_rot_pairs, B.n_rots, B.sphere32, B.n_sphere, B.thr,
-                             I.counts, B.descending, 1, B.n_sphere, nullptr, 0);
-    else
-        rot_sphere_band_even_body(I.points, I.heads, 8, I.idx32, I.surv, I.count, I.n_ppfs, B.max_rot_pairs, B.n_rots, B.sphere32, B.n_sphere,
-                                  B.thr, I.counts, B.descending, 1, B.n_sphere);
+    SphereCountArgs A = {};      // (heads rows of 8 floats: the directions' rotations in columns 0 and 1)
+    A.points = I.points; A.preds_rot = I.heads; A.rot_stride = 8; A.rot_dir_step = 1; A.point_idxs = I.idx32; A.sel = I.surv;
+    A.n_sel_dev = I.count; A.n_sel_host = I.n_ppfs; A.max_pairs = B.max_rot_pairs; A.n_rots = B.n_rots; A.sphere = B.sphere32;
+    A.n_sphere = B.n_sphere; A.thr = B.thr; A.counts = I.counts; A.counts_dir_step = B.n_sphere; A.descending = B.descending;
+    rot_sphere_band_body<true>(A);
 }
 __global__ __launch_bounds__(RED_THREADS) void pose_sums_batch_kernel(TailBatch B)
 {
@@ -1317,11 +1288,6 @@ extern "C" int cppf_pose_tail_batch(int n_items, const CppfPoseTailItem* items, 
     hipStream_t st = (hipStream_t)stream;
     TailBatch B = {};
     B.n = n_items; B.n_rots = n_rots; B.n_sphere = n_sphere; B.descending = sphere_sorted_by_y > 0 ? 1 : 0;
-    {   // development knob (A/B measurements): the single-instance grouping of the sphere count in the batched launch
-        static int legacy = -1;
-        if (legacy < 0) legacy = getenv("CPPF_SPHERE_LEGACY") ? 1 : 0;
-        B.sphere_legacy = legacy;
-    }
     B.max_rot_pairs = max_rot_pairs; B.sphere32 = sphere32; B.thr = thr;
     CppfPairMlpItem sel_items[TAIL_BATCH_MAX];
     int n_second = 0, max_dirs = 1;
@@ -1359,9 +1325,8 @@ extern "C" int cppf_pose_tail_batch(int n_items, const CppfPoseTailItem* items, 
         nb = (it.n_pairs + CMP_BLOCK - 1) / CMP_BLOCK;
         cmp_blocks = nb > cmp_blocks ? nb : cmp_blocks;
         const int64_t bound = it.n_pairs < max_rot_pairs ? it.n_pairs : max_rot_pairs;
-        nb = (bound + 7) / 8;                          // (rot_sphere_band_even_body: a block owns a contiguous share of the survivors)
+        nb = (bound + 7) / 8;                          // (rot_sphere_band_body<true>: a block owns a contiguous share of the survivors)
         nb = nb > SPHE_BLOCKS ? SPHE_BLOCKS : nb;
-        if (B.sphere_legacy) { nb = (bound + 1) / 2; nb = nb > 2048 ? 2048 : nb; }
         rot_blocks = nb > rot_blocks ? nb : rot_blocks;
         max_dirs = it.n_dirs > max_dirs ? it.n_dirs : max_dirs;
         if (it.second_pass) {
@@ -1392,12 +1357,8 @@ extern "C" int cppf_pose_tail_batch(int n_items, const CppfPoseTailItem* items, 
     }
     // 5. orientation vote + sphere-bin count (:259-284), both directions
     if (max_rot_pairs > 0) {
-        const size_t lds_rot = (size_t)(5 * n_sphere + 2 * n_rots) * sizeof(float);
-        static bool lds_attr = false;      // (4 096 bins x 20 B + the rotation row: above the 64 KB a launch gets unasked)
-        if (!lds_attr) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rot_sphere_band_batch_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            lds_attr = true;
-        }
+        const size_t lds_rot = sphere_band_lds(n_sphere, n_rots);
+        sphere_band_allow_lds<&rot_sphere_band_batch_kernel>(lds_rot);
         hipLaunchKernelGGL(rot_sphere_band_batch_kernel, dim3((unsigned)rot_blocks, (unsigned)max_dirs, (unsigned)n_items), dim3(256), lds_rot, st, B);
         CPPF_CHECK_LAUNCH();
     }

@@ -108,12 +108,13 @@ def test_staged_chain_first_eager_run_is_ordered_against_weight_image_rebuilds(g
     np.testing.assert_array_equal(rows[0], rows[1])
 
 
-@pytest.mark.parametrize("n_bins,gain", [(3600, 12.0), (37, 1.0), (480, 12.0)])
+@pytest.mark.parametrize("n_bins,gain", [(3600, 12.0), (37, 1.0), (480, 12.0), (423, 12.0), (4096, 12.0)])
 def test_chain_sphere_count_equals_member_pipelines_on_other_spheres(dev, n_bins, gain):
-    """the chain's orientation count (rot_sphere_band_even_body: a block owns a contiguous share of the survivors) against the
+    """the chain's orientation count (rot_sphere_band_body<true>: a block owns a contiguous share of the survivors) against the
     members' own launches (groups of 2 or 8 pairs) on a fine sphere (0.2 degrees: 3 600 bins, above the default 64 KB of LDS), a
-    coarse one and the default, with few survivors and with the cap on the voting pairs reached (nocs/inference.py:277; set to 1 000
-    here): records bit for bit, both forms"""
+    coarse one, the default, an odd bin count (num_sphere_bins(1.7) = 423) and the most bins the banded kernels take (4 096), with
+    few survivors and with the cap on the voting pairs reached (nocs/inference.py:277; set to 1 000 here): records bit for bit,
+    both forms"""
     from cppf_amd.utils.util import fibonacci_sphere
     sph = np.array(fibonacci_sphere(n_bins))
     enc = make_encoder(seeded_sd(3, gain), dev)

@@ -537,6 +537,87 @@ def test_rot_voting_and_sphere_count_bit_exact(oracle, golden, dev):
     assert counts_o.sum() > 0
 
 
+@pytest.fixture(scope="module")
+def sphere_case(oracle, dev):
+    """one 512-point object, 5 120 pairs with two rotation columns, the oracle's candidates of both and a survivor list: computed once,
+    read-only on the host, with the kernels' inputs on the device ("d")"""
+    ob = syn.make_object("camera", 512, 17)
+    idx32 = syn.make_pairs(512, 10, 17).astype(np.int32)
+    P = idx32.shape[0]
+    rng = np.random.default_rng(17)
+    theta = (rng.integers(0, 36, (P, 2)) / 35 * np.pi).astype(np.float32)     # both sides of pi/2, incl. 0 and pi
+    cands = np.stack([oracle.rot_voting(ob["pc"], np.ascontiguousarray(theta[:, j]), idx32, 72) for j in range(2)])
+    sel = np.sort(rng.choice(P, 4600, replace=False)).astype(np.int32)
+    case = dict(pc=ob["pc"], idx32=idx32, theta=theta, cands=cands, sel=sel)
+    on_device = {k: t(case[k], dev) for k in ("pc", "idx32", "theta", "sel")}
+    for a in case.values():
+        a.setflags(write=False)
+    return dict(case, P=P, d=on_device)
+
+
+@pytest.mark.parametrize("n_bins,n", [(480, 1), (480, 2), (480, 3), (480, 63), (480, 64), (480, 65), (480, 4097), (423, 500), (4096, 500)])
+def test_sphere_count_band_schedule_edges_match_oracle(oracle, golden, dev, sphere_case, n_bins, n):
+    """cppf_rot_sphere_count on bins sorted by y (the banded kernel) over the first n survivors, n reached through the device count and
+    through max_pairs: one block with one pair, the ends of a group of 2, around 64, past the 4 096 slots where groups become 8 pairs;
+    an odd bin count (num_sphere_bins(1.7) = 423) and the most bins the banded kernel takes (4 096: above 64 KB of LDS)"""
+    from cppf_amd.utils.util import fibonacci_sphere
+    c = sphere_case
+    sph = golden("sphere.npz")["pts"] if n_bins == 480 else np.array(fibonacci_sphere(n_bins))
+    assert sph.shape == (n_bins, 3)
+    sph32 = sph.astype(np.float32)
+    counts_o = oracle.sphere_count(c["cands"][0][c["sel"][:n]], sph32, 1.5)
+    assert counts_o.sum() > 0
+    L = _lib.lib()
+    thr = float(np.float32(np.cos(1.5 / 180 * np.pi)))
+    pc_d, th_d, idx_d, sel_d, sph_d = c["d"]["pc"], c["d"]["theta"], c["d"]["idx32"], c["d"]["sel"], t(sph32, dev)
+    counts = torch.zeros(n_bins, dtype=torch.int32, device=dev)
+    for n_dev, max_pairs in ((n, c["P"]), (c["sel"].size, n)):
+        nsel = torch.tensor([n_dev], dtype=torch.int32, device=dev)
+        counts.zero_()
+        _lib.check(L.cppf_rot_sphere_count(pc_d.data_ptr(), th_d.data_ptr(), 2, idx_d.data_ptr(), sel_d.data_ptr(), nsel.data_ptr(),
+                                           c["P"], max_pairs, 72, sph_d.data_ptr(), n_bins, thr, 1, counts.data_ptr(),
+                                           stream_ptr(dev)), "rot_sphere_count")
+        torch.cuda.synchronize()
+        np.testing.assert_array_equal(counts.cpu().numpy().astype(np.int64), counts_o, err_msg=str((n_dev, max_pairs)))
+
+
+@pytest.mark.parametrize("angle_tol", [1.5, 25.0])
+@pytest.mark.parametrize("n_dirs", [1, 2])
+def test_sphere_count_order_with_padding_matches_oracle(oracle, golden, dev, sphere_case, n_dirs, angle_tol):
+    """cppf_rot_sphere_count_dirs_order: 700 survivors, an order of 300 slots -- a shuffled subsample with repeats, about 20 entries
+    past the survivor list and a few negative ones (pad slots).  The counts are the oracle's over exactly the in-range entries,
+    repeats counted as often as they occur."""
+    c = sphere_case
+    n_surv = 700
+    rng = np.random.default_rng(29)
+    order = rng.integers(0, n_surv, 300).astype(np.int32)
+    pads = rng.choice(300, 26, replace=False)
+    order[pads[:20]] = rng.integers(n_surv, c["sel"].size + 50, 20)      # (some of them valid positions of sel, none a survivor)
+    order[pads[20]] = n_surv                                              # the first position past the list
+    order[pads[21:]] = [-1, -2, -700, -2 ** 31, -5]
+    inside = order[(order >= 0) & (order < n_surv)]
+    assert inside.size == 300 - 26 and np.unique(inside).size < inside.size
+    sph = golden("sphere.npz")["pts"]
+    want = [oracle.sphere_count(c["cands"][j][c["sel"][inside]], sph, angle_tol) for j in range(n_dirs)]
+    assert all(w.sum() > 0 for w in want)                                  # (a kernel that skips every slot cannot pass)
+    L = _lib.lib()
+    thr = float(np.float32(np.cos(angle_tol / 180 * np.pi)))
+    pc_d, th_d, idx_d, sel_d, ord_d = c["d"]["pc"], c["d"]["theta"], c["d"]["idx32"], c["d"]["sel"], t(order, dev)
+    sph_d = t(sph.astype(np.float32), dev)
+    nsel = torch.tensor([n_surv], dtype=torch.int32, device=dev)
+    for sorted_y in (1, 0):          # the banded kernel and the full sweep
+        counts = torch.zeros((2, 480), dtype=torch.int32, device=dev)
+        _lib.check(L.cppf_rot_sphere_count_dirs_order(pc_d.data_ptr(), th_d.data_ptr(), 2, 1, n_dirs, idx_d.data_ptr(), sel_d.data_ptr(),
+                                                      nsel.data_ptr(), c["P"], ord_d.data_ptr(), 300, 10000, 72, sph_d.data_ptr(), 480,
+                                                      thr, sorted_y, counts.data_ptr(), 480, stream_ptr(dev)),
+                   "rot_sphere_count_dirs_order")
+        torch.cuda.synchronize()
+        cn = counts.cpu().numpy().astype(np.int64)
+        for j in range(n_dirs):
+            np.testing.assert_array_equal(cn[j], want[j], err_msg=str((sorted_y, j)))
+        assert not cn[n_dirs:].any()                                       # a direction that was not asked for is not touched
+
+
 def test_axis_sign_and_scale_sums(oracle, dev):
     ob = syn.make_object("mug", 600, 21)
     idx = syn.make_pairs(600, 10, 21)
