@@ -118,8 +118,10 @@ __device__ void smallest_eigvec(double a00, double a01, double a02, double a11, 
     for (int c = 0; c < 3; ++c) out[c] = sg * (v[c] / n);
 }
 
-__global__ __launch_bounds__(256) void normals_kernel(const float* __restrict__ pc, const int32_t* __restrict__ nbrs, int64_t N, int k,
-                                                      float* __restrict__ normals)
+// normal of point n = blockIdx.x * 256 + threadIdx.x of a cloud of N points over its k neighbours (N by value: cppf_estimate_normals;
+// from the shape record: the frame stage)
+__device__ __forceinline__ void fc_normals_body(const float* __restrict__ pc, const int32_t* __restrict__ nbrs, int64_t N, int k,
+                                                float* __restrict__ normals)
 {
     const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
@@ -138,20 +140,14 @@ __global__ __launch_bounds__(256) void normals_kernel(const float* __restrict__ 
 #pragma unroll
     for (int i = 0; i < 3; ++i) normals[3 * n + i] = (float)v[i];
 }
-
-// ---- the whole per-instance pre-processing as ONE count-driven stage (cppf_frame_cloud_dyn): no size ever visits the host.
-// valid pixel = bit `bit` of the frame's label image set and depth > 0 (utils/util.py:609-610 with instance_mask = that bit)
-template <typename T, typename LT>
-__global__ __launch_bounds__(256) void fc_valid_kernel(const T* __restrict__ depth, const LT* __restrict__ labels, unsigned bit, int64_t n,
-                                                       uint8_t* __restrict__ valid, const int32_t* __restrict__ bit_dev)
+__global__ __launch_bounds__(256) void normals_kernel(const float* __restrict__ pc, const int32_t* __restrict__ nbrs, int64_t N, int k,
+                                                      float* __restrict__ normals)
 {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (bit_dev) bit = (unsigned)*bit_dev & (8u * (unsigned)sizeof(LT) - 1u);      // (a captured launch: this replay's bit is in memory)
-    if (i < n) valid[i] = ((labels[i] >> bit) & 1) && (depth[i] > (T)0);
+    fc_normals_body(pc, nbrs, N, k, normals);
 }
-// back-projection of the compacted pixels (bp_points_kernel's arithmetic), nocs/inference.py:132 `pc = pts / 1000.0` (fp64), the axis
-// flips of :136-137 (negations of utils/util.py:629-630's negations: exact), `.float()` of :140 -- and the voxel key of every slot:
-// slots beyond the count get the all-ones key, which sorts behind every real one
+
+// ---- the whole per-instance pre-processing as ONE count-driven stage (cppf_frame_cloud_dyn, _bit, _batch): no size ever visits the
+// host.  The device functions of its steps; the kernels (fcb_*) are behind cppf_stage_batch's.
 // Voxel de-duplication without a sort (rocprim's radix sort inside a captured graph gave different results from the second
 // replay on: ROCm 7.2): an open-addressing table of M = 2^m >= 2 n_cap slots {voxel key, lowest point index}.  Every point inserts
 // its key (atomicCAS on the key word, linear probing) and atomicMin's its index into the slot; a point represents its voxel iff it
@@ -161,11 +157,6 @@ __device__ __forceinline__ unsigned fc_hash(unsigned long long k, unsigned mask)
 {
     k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
     return (unsigned)k & mask;
-}
-__global__ __launch_bounds__(256) void fc_clear_kernel(unsigned long long* __restrict__ tkeys, int32_t* __restrict__ tidx, int M)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i < M) { tkeys[i] = FC_EMPTY; tidx[i] = 0x7fffffff; }
 }
 // back-projection of the compacted pixels (bp_points_kernel's arithmetic), nocs/inference.py:132 `pc = pts / 1000.0` (fp64), the axis
 // flips of :136-137 (negations of utils/util.py:629-630's negations: exact), `.float()` of :140, the voxel key (vox_keys_kernel) and
@@ -198,14 +189,6 @@ __device__ __forceinline__ void fc_points_body(const T* __restrict__ depth, cons
         if (prev == FC_EMPTY || prev == k) { atomicMin(&tidx[h], i); break; }
     }
 }
-template <typename T>
-__global__ __launch_bounds__(256) void fc_points_kernel(const T* __restrict__ depth, const int32_t* __restrict__ pix,
-                                                        const int32_t* __restrict__ count, int W, Kinv K, double divisor, double res,
-                                                        int n_cap, float* __restrict__ pcf, unsigned long long* __restrict__ keys,
-                                                        unsigned long long* __restrict__ tkeys, int32_t* __restrict__ tidx, unsigned tmask)
-{
-    fc_points_body<T>(depth, pix, count, W, K, divisor, res, n_cap, pcf, keys, tkeys, tidx, tmask);
-}
 // does point i represent its voxel (the lowest index among the points of its key)?
 __device__ __forceinline__ bool fc_is_representative(const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ tkeys,
                                                      const int32_t* __restrict__ tidx, unsigned tmask, int i)
@@ -215,62 +198,14 @@ __device__ __forceinline__ bool fc_is_representative(const unsigned long long* _
     while (tkeys[h] != k) h = (h + 1) & tmask;      // (the key is in the table: this point put it there or found it there)
     return tidx[h] == i;
 }
-__global__ __launch_bounds__(256) void fc_mark_kernel(const unsigned long long* __restrict__ keys, const unsigned long long* __restrict__ tkeys,
-                                                      const int32_t* __restrict__ tidx, unsigned tmask, const int32_t* __restrict__ count,
-                                                      int n_cap, uint8_t* __restrict__ mask)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_cap) return;
-    uint8_t m = 0;
-    if (i < min(*count, n_cap)) m = fc_is_representative(keys, tkeys, tidx, tmask, i);
-    mask[i] = m;
-}
-// pc = pc[keep] (:141) into the pipeline's cloud buffer; the instance's point count N (0 when it is below k_min: the reference
-// skips such instances, :121-123) goes to shape[0], where the kernels behind this stage read it
-__global__ __launch_bounds__(256) void fc_gather_kernel(const float* __restrict__ pcf, const int32_t* __restrict__ keep,
-                                                        const int32_t* __restrict__ count, int k_min, int n_cap, float* __restrict__ pc_out,
-                                                        int32_t* __restrict__ shape)
-{
-    const int n = min(*count, n_cap);
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i == 0) shape[0] = n >= k_min ? n : 0;
-    if (i >= n) return;
-    const int s = keep[i];
-    pc_out[3 * i] = pcf[3 * s]; pc_out[3 * i + 1] = pcf[3 * s + 1]; pc_out[3 * i + 2] = pcf[3 * s + 2];
-}
-__device__ __forceinline__ void fc_normals_body(const float* __restrict__ pc, const int32_t* __restrict__ nbrs,
-                                                const int32_t* __restrict__ n_dev, int k, float* __restrict__ normals)
-{
-    const int64_t n = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (n >= *n_dev) return;
-    double c[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-    for (int j = 0; j < k; ++j) {
-        const float* p = pc + 3 * (int64_t)nbrs[n * k + j];
-        const double x = p[0], y = p[1], z = p[2];
-        c[0] += x; c[1] += y; c[2] += z;
-        c[3] += x * x; c[4] += x * y; c[5] += x * z; c[6] += y * y; c[7] += y * z; c[8] += z * z;
-    }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) c[i] /= (double)k;
-    double v[3];
-    smallest_eigvec(c[3] - c[0] * c[0], c[4] - c[0] * c[1], c[5] - c[0] * c[2], c[6] - c[1] * c[1], c[7] - c[1] * c[2],
-                    c[8] - c[2] * c[2], v);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) normals[3 * n + i] = (float)v[i];
-}
-__global__ __launch_bounds__(256) void fc_normals_kernel(const float* __restrict__ pc, const int32_t* __restrict__ nbrs,
-                                                         const int32_t* __restrict__ n_dev, int k, float* __restrict__ normals)
-{
-    fc_normals_body(pc, nbrs, n_dev, k, normals);
-}
-// nocs/inference.py:194-195 from the device count: corner = min(pc), dims = int32((max - min) / res) + 1 -> shape[1..3]
-// (minima and maxima: exact in any order, whatever the block size)
-__device__ __forceinline__ void fc_grid_body(const float* __restrict__ pc, float res, float* __restrict__ corner, int32_t* __restrict__ shape)
+// nocs/inference.py:194-195 for the first N points of pc, by one block of any multiple of 64 threads: corner = min(pc), dims =
+// int32((max - min) / res) + 1 -> shape[1..3] (shape may be NULL); N = 0: corner 0, dims 1.  Minima and maxima are exact in any order.
+__device__ __forceinline__ void fc_grid_body(const float* __restrict__ pc, int64_t N, float res, float* __restrict__ corner,
+                                             int32_t* __restrict__ shape)
 {
     __shared__ float slo[16][3], shi[16][3];
-    const int N = shape[0];
     float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = threadIdx.x; i < N; i += (int)blockDim.x)
+    for (int64_t i = threadIdx.x; i < N; i += blockDim.x)
         for (int j = 0; j < 3; ++j) {
             const float v = pc[3 * i + j];
             lo[j] = fminf(lo[j], v);
@@ -289,13 +224,8 @@ __device__ __forceinline__ void fc_grid_body(const float* __restrict__ pc, float
         float l = slo[0][j], h = shi[0][j];
         for (int w = 1; w < (int)(blockDim.x >> 6); ++w) { l = fminf(l, slo[w][j]); h = fmaxf(h, shi[w][j]); }
         corner[j] = N > 0 ? l : 0.f;
-        shape[1 + j] = N > 0 ? (int32_t)((h - l) / res) + 1 : 1;
+        if (shape) shape[1 + j] = N > 0 ? (int32_t)((h - l) / res) + 1 : 1;
     }
-}
-__global__ __launch_bounds__(1024) void fc_grid_kernel(const float* __restrict__ pc, float res, float* __restrict__ corner,
-                                                       int32_t* __restrict__ shape)
-{
-    fc_grid_body(pc, res, corner, shape);
 }
 // idx = idx mod N (both columns): pairs drawn as full-range integers on the device before the instance's N is known anywhere but here
 __global__ __launch_bounds__(256) void mod_pairs_kernel(long long* __restrict__ idx, int64_t n2, const int32_t* __restrict__ n_dev)
@@ -333,28 +263,35 @@ FcLayout fc_layout(int H, int W, int n_cap, int k)
 
 // ---- pair list + bin uniforms drawn on the device (cppf_sample_pairs): Philox-4x32-10 (cppf_math.h), counter = pair index,
 // key = the caller's 64-bit seed; stateless, so a pair's draw depends on (seed, pair index) only -- whichever rank or stream draws it.
+// Pairs first, first + step, ... < n_pairs of a list over N points: idx i64[n_pairs,2] or i32[n_pairs,2], u_tr / u_rot (may be NULL)
+__device__ __forceinline__ void draw_pairs_body(void* __restrict__ idx, int idx_is_i64, float* __restrict__ u_tr, float* __restrict__ u_rot,
+                                                int64_t n_pairs, unsigned long long N, uint2 key, int64_t first, int64_t step)
+{
+    for (int64_t p = first; p < n_pairs; p += step) {
+        const uint4 a = philox4x32_10(make_uint4((unsigned)p, (unsigned)(p >> 32), 0u, 0u), key);
+        const uint4 b = philox4x32_10(make_uint4((unsigned)p, (unsigned)(p >> 32), 1u, 0u), key);
+        // index = floor(r N / 2^32): uniform over [0, N) up to a bias of N / 2^32 (np.random.randint(0, N, (P, 2)), nocs/inference.py:177)
+        const unsigned long long i0 = ((unsigned long long)a.x * N) >> 32, i1 = ((unsigned long long)a.y * N) >> 32;
+        if (idx_is_i64) reinterpret_cast<longlong2*>(idx)[p] = make_longlong2((long long)i0, (long long)i1);
+        else reinterpret_cast<int2*>(idx)[p] = make_int2((int)i0, (int)i1);
+        // uniforms in [0, 1): the top 24 bits (stand-ins for torch.multinomial's draws, :186,250,254)
+        if (u_tr) reinterpret_cast<float2*>(u_tr)[p] = make_float2((float)(a.z >> 8) * 0x1p-24f, (float)(a.w >> 8) * 0x1p-24f);
+        if (u_rot) reinterpret_cast<float2*>(u_rot)[p] = make_float2((float)(b.x >> 8) * 0x1p-24f, (float)(b.y >> 8) * 0x1p-24f);
+    }
+}
 __global__ __launch_bounds__(256) void sample_pairs_kernel(long long* __restrict__ idx, float* __restrict__ u_tr, float* __restrict__ u_rot,
                                                            int64_t P, int64_t n_points, const int32_t* __restrict__ n_dev,
                                                            unsigned long long seed, const unsigned long long* __restrict__ seed_dev)
 {
     const unsigned long long N = (unsigned long long)(n_dev ? (int64_t)*n_dev : n_points);
     if (seed_dev) seed = *seed_dev;      // (a captured launch: the seed of this replay is in memory)
-    const uint2 key = make_uint2((unsigned)seed, (unsigned)(seed >> 32));
-    for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < P; p += (int64_t)gridDim.x * 256) {
-        const uint4 a = philox4x32_10(make_uint4((unsigned)p, (unsigned)(p >> 32), 0u, 0u), key);
-        const uint4 b = philox4x32_10(make_uint4((unsigned)p, (unsigned)(p >> 32), 1u, 0u), key);
-        // index = floor(r N / 2^32): uniform over [0, N) up to a bias of N / 2^32 (np.random.randint(0, N, (P, 2)), nocs/inference.py:177)
-        reinterpret_cast<longlong2*>(idx)[p] = make_longlong2((long long)(((unsigned long long)a.x * N) >> 32),
-                                                              (long long)(((unsigned long long)a.y * N) >> 32));
-        // uniforms in [0, 1): the top 24 bits (stand-ins for torch.multinomial's draws, :186,250,254)
-        if (u_tr) reinterpret_cast<float2*>(u_tr)[p] = make_float2((float)(a.z >> 8) * 0x1p-24f, (float)(a.w >> 8) * 0x1p-24f);
-        if (u_rot) reinterpret_cast<float2*>(u_rot)[p] = make_float2((float)(b.x >> 8) * 0x1p-24f, (float)(b.y >> 8) * 0x1p-24f);
-    }
+    draw_pairs_body(idx, 1, u_tr, u_rot, P, N, make_uint2((unsigned)seed, (unsigned)(seed >> 32)), (int64_t)blockIdx.x * 256 + threadIdx.x,
+                    (int64_t)gridDim.x * 256);
 }
 
 // ---- cppf_stage_batch: the head of a captured chain for objects already on the device.  Workgroup roles by blockIdx.x, object =
 // blockIdx.y: 0 = grid set-up (nocs/inference.py:194-195, the arithmetic of grid_setup_kernel), 1 .. STAGE_COPY_BLOCKS = copies of cloud,
-// normals and features into the chain's buffers, the rest = the pair / uniform draws (sample_pairs_kernel's, bit for bit).
+// normals and features into the chain's buffers, the rest = the pair / uniform draws (draw_pairs_body: cppf_sample_pairs' numbers).
 #define STAGE_MAX 8
 #define STAGE_COPY_BLOCKS 16
 struct StageBatch { CppfStageItem item[STAGE_MAX]; int n_sample_blocks; };
@@ -365,28 +302,7 @@ __global__ __launch_bounds__(256) void stage_batch_kernel(StageBatch B)
     const int64_t N = D.n_points < 0 ? 0 : (D.n_points > I.n_cap ? I.n_cap : D.n_points);
     const int tid = threadIdx.x;
     if (blockIdx.x == 0) {
-        __shared__ float slo[4][3], shi[4][3];
-        float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-        for (int64_t i = tid; i < N; i += 256)
-            for (int j = 0; j < 3; ++j) {
-                const float v = D.pc_src[3 * i + j];
-                lo[j] = fminf(lo[j], v);
-                hi[j] = fmaxf(hi[j], v);
-            }
-        for (int j = 0; j < 3; ++j)
-            for (int off = 32; off > 0; off >>= 1) {
-                lo[j] = fminf(lo[j], __shfl_xor(lo[j], off, 64));
-                hi[j] = fmaxf(hi[j], __shfl_xor(hi[j], off, 64));
-            }
-        if ((tid & 63) == 0)
-            for (int j = 0; j < 3; ++j) { slo[tid >> 6][j] = lo[j]; shi[tid >> 6][j] = hi[j]; }
-        __syncthreads();
-        if (tid < 3) {
-            float l = slo[0][tid], h = shi[0][tid];
-            for (int w = 1; w < 4; ++w) { l = fminf(l, slo[w][tid]); h = fmaxf(h, shi[w][tid]); }
-            I.corner[tid] = N > 0 ? l : 0.f;
-            if (I.shape) I.shape[1 + tid] = N > 0 ? (int32_t)((h - l) / I.res) + 1 : 1;
-        }
+        fc_grid_body(D.pc_src, N, I.res, I.corner, I.shape);
         if (tid == 3 && I.shape) I.shape[0] = (int32_t)N;
         return;
     }
@@ -400,26 +316,16 @@ __global__ __launch_bounds__(256) void stage_batch_kernel(StageBatch B)
         return;
     }
     if (!I.idx) return;
-    const unsigned long long Nu = (unsigned long long)N;
-    const uint2 key = make_uint2((unsigned)D.seed, (unsigned)(D.seed >> 32));
-    const int64_t first = (int64_t)(blockIdx.x - 1 - STAGE_COPY_BLOCKS) * 256 + tid, step = (int64_t)B.n_sample_blocks * 256;
-    for (int64_t p = first; p < I.n_pairs; p += step) {
-        const uint4 a = philox4x32_10(make_uint4((unsigned)p, (unsigned)(p >> 32), 0u, 0u), key);
-        const uint4 b = philox4x32_10(make_uint4((unsigned)p, (unsigned)(p >> 32), 1u, 0u), key);
-        const unsigned long long i0 = ((unsigned long long)a.x * Nu) >> 32, i1 = ((unsigned long long)a.y * Nu) >> 32;
-        if (I.idx_is_i64) reinterpret_cast<longlong2*>(I.idx)[p] = make_longlong2((long long)i0, (long long)i1);
-        else reinterpret_cast<int2*>(I.idx)[p] = make_int2((int)i0, (int)i1);
-        if (I.u_tr) reinterpret_cast<float2*>(I.u_tr)[p] = make_float2((float)(a.z >> 8) * 0x1p-24f, (float)(a.w >> 8) * 0x1p-24f);
-        if (I.u_rot) reinterpret_cast<float2*>(I.u_rot)[p] = make_float2((float)(b.x >> 8) * 0x1p-24f, (float)(b.y >> 8) * 0x1p-24f);
-    }
+    draw_pairs_body(I.idx, I.idx_is_i64, I.u_tr, I.u_rot, I.n_pairs, (unsigned long long)N, make_uint2((unsigned)D.seed, (unsigned)(D.seed >> 32)),
+                    (int64_t)(blockIdx.x - 1 - STAGE_COPY_BLOCKS) * 256 + tid, (int64_t)B.n_sample_blocks * 256);
 }
 
-// ---- cppf_frame_cloud_dyn_batch: the frame stage of up to 8 instances of ONE frame in eight launches instead of sixteen each.
-// A frame's chain is launch-bound on the host (a hipGraph launch costs the host per kernel node: three chains of two instances, 52
-// nodes each, took 1.2 of a frame's 1.6 ms to enqueue) and its ~15 pre-processing kernels per instance run for ~5 us each.  Here a
-// launch serves every member (blockIdx.y) and neighbouring steps share launches: the mask kernels count their own 1 024-byte chunks
-// (no count + scan launches: compact.h), the first one clears the voxel table on the way, the normals launch also sets up the grid
-// and draws the pairs.  Per member the arithmetic is that of cppf_frame_cloud_dyn + cppf_sample_pairs (the same device functions).
+// ---- cppf_frame_cloud_dyn / _bit / _batch: the frame stage of up to 8 instances of ONE frame in eight launches (the single entry
+// points are a batch of one without draws).  A frame's chain is launch-bound on the host (a hipGraph launch costs the host per kernel
+// node: three chains of two instances, 52 nodes each, took 1.2 of a frame's 1.6 ms to enqueue) and a step per kernel runs for ~5 us.
+// Here a launch serves every member (blockIdx.y) and neighbouring steps share launches: the mask kernels count their own 1 024-byte
+// chunks (no count + scan launches: compact.h), the first one clears the voxel table on the way, the normals launch also sets up the
+// grid and draws the pairs (draw_pairs_body: cppf_sample_pairs' numbers).
 #define FCB_MAX 8
 struct FcbItem {
     const int32_t* bit_dev; const unsigned long long* seed_dev;
@@ -430,7 +336,7 @@ struct FcbItem {
     void* idx;
     double res;
     long long n_pairs;
-    int knn_k, k_min, n_cap, M, idx_is_i64;
+    int knn_k, k_min, n_cap, M, idx_is_i64, bit;      // bit: the label bit when bit_dev is NULL
 };
 struct FcbBatch { FcbItem item[FCB_MAX]; const void* depth; const void* labels; long long n_pix; Kinv K; double divisor; int W, label_bytes, n_sample_blocks; };
 static_assert(sizeof(FcbBatch) <= 4096, "FcbBatch travels by value: kernel arguments are limited to 4 KB");
@@ -449,7 +355,8 @@ __global__ __launch_bounds__(CMP_BLOCK) void fcb_valid_kernel(FcbBatch B)
         if (B.label_bytes == 1) lab = static_cast<const uint8_t*>(B.labels)[i];
         else if (B.label_bytes == 2) lab = static_cast<const uint16_t*>(B.labels)[i];
         else lab = static_cast<const uint32_t*>(B.labels)[i];
-        const unsigned bit = (unsigned)*I.bit_dev & (8u * (unsigned)B.label_bytes - 1u);
+        // valid pixel = its label's bit set and depth > 0 (utils/util.py:609-610 with instance_mask = that bit)
+        const unsigned bit = (unsigned)(I.bit_dev ? *I.bit_dev : I.bit) & (8u * (unsigned)B.label_bytes - 1u);
         f = ((lab >> bit) & 1u) && (d > (T)0);
         I.valid[i] = f;
     }
@@ -500,21 +407,13 @@ __global__ __launch_bounds__(256) void fcb_gather_kernel(FcbBatch B)
 __global__ __launch_bounds__(256) void fcb_finish_kernel(FcbBatch B, int nbc)
 {
     const FcbItem& I = B.item[blockIdx.y];
-    if ((int)blockIdx.x < nbc) { fc_normals_body(I.pc_out, I.nbrs, I.shape_out, I.knn_k, I.nrm_out); return; }
-    if ((int)blockIdx.x == nbc) { fc_grid_body(I.pc_out, (float)I.res, I.corner_out, I.shape_out); return; }
+    const int N = I.shape_out[0];
+    if ((int)blockIdx.x < nbc) { fc_normals_body(I.pc_out, I.nbrs, N, I.knn_k, I.nrm_out); return; }
+    if ((int)blockIdx.x == nbc) { fc_grid_body(I.pc_out, N, (float)I.res, I.corner_out, I.shape_out); return; }
     if (!I.idx) return;
-    const unsigned long long N = (unsigned long long)(long long)I.shape_out[0], seed = *I.seed_dev;
-    const uint2 key = make_uint2((unsigned)seed, (unsigned)(seed >> 32));
-    const long long first = (long long)((int)blockIdx.x - nbc - 1) * 256 + threadIdx.x, step = (long long)B.n_sample_blocks * 256;
-    for (long long p = first; p < I.n_pairs; p += step) {
-        const uint4 a = philox4x32_10(make_uint4((unsigned)p, (unsigned)(p >> 32), 0u, 0u), key);
-        const uint4 b = philox4x32_10(make_uint4((unsigned)p, (unsigned)(p >> 32), 1u, 0u), key);
-        const unsigned long long i0 = ((unsigned long long)a.x * N) >> 32, i1 = ((unsigned long long)a.y * N) >> 32;
-        if (I.idx_is_i64) reinterpret_cast<longlong2*>(I.idx)[p] = make_longlong2((long long)i0, (long long)i1);
-        else reinterpret_cast<int2*>(I.idx)[p] = make_int2((int)i0, (int)i1);
-        if (I.u_tr) reinterpret_cast<float2*>(I.u_tr)[p] = make_float2((float)(a.z >> 8) * 0x1p-24f, (float)(a.w >> 8) * 0x1p-24f);
-        if (I.u_rot) reinterpret_cast<float2*>(I.u_rot)[p] = make_float2((float)(b.x >> 8) * 0x1p-24f, (float)(b.y >> 8) * 0x1p-24f);
-    }
+    const unsigned long long seed = *I.seed_dev;
+    draw_pairs_body(I.idx, I.idx_is_i64, I.u_tr, I.u_rot, I.n_pairs, (unsigned long long)N, make_uint2((unsigned)seed, (unsigned)(seed >> 32)),
+                    (int64_t)((int)blockIdx.x - nbc - 1) * 256 + threadIdx.x, (int64_t)B.n_sample_blocks * 256);
 }
 
 // cppf_copy_words: a few 64-bit words moved by a kernel of the stream instead of by a copy engine.  hipMemcpyAsync hands small copies to
@@ -620,116 +519,56 @@ size_t cppf_frame_cloud_workspace_bytes(int H, int W, int n_cap, int knn_k)
     return fc_layout(H, W, n_cap, knn_k).total;
 }
 
-static int frame_cloud_impl(const void* depth, int depth_is_u16, const void* labels, int label_bytes, int label_bit, const int32_t* bit_dev,
-                            int H, int W, const double* kinv_host, double divisor, double res, int knn_k, int k_min, int n_cap, float* pc_out,
-                            float* nrm_out, float* corner_out, int32_t* shape_out, int32_t* nbrs_out, void* workspace, size_t workspace_bytes,
-                            void* stream)
+// the frame's arguments -> B
+static int fcb_frame(FcbBatch& B, const void* depth, const void* labels, int label_bytes, int H, int W, const double* kinv_host, double divisor)
 {
-    if (H < 1 || W < 1 || (int64_t)H * W > 0x7fffffffll || !depth || !labels || !kinv_host || !pc_out || !nrm_out || !corner_out || !shape_out)
-        return CPPF_EINVAL;
-    if ((label_bytes != 1 && label_bytes != 2 && label_bytes != 4) || label_bit < 0 || label_bit >= 8 * label_bytes) return CPPF_EINVAL;
-    if (n_cap < 1 || knn_k < 1 || knn_k > 64 || knn_k > n_cap || k_min < knn_k || !(res > 0.0) || !(divisor > 0.0)) return CPPF_EINVAL;
-    const FcLayout L = fc_layout(H, W, n_cap, knn_k);
-    if (!workspace || workspace_bytes < L.total) return CPPF_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = static_cast<char*>(workspace);
-    const int64_t n = (int64_t)H * W;
-    uint8_t* valid = (uint8_t*)(ws + L.valid);
-    int32_t* pix = (int32_t*)(ws + L.pix);
-    int32_t *count1 = (int32_t*)(ws + L.count), *count2 = (int32_t*)(ws + L.count + 64);
-    float* pcf = (float*)(ws + L.pcf);
-    unsigned long long *keys = (unsigned long long*)(ws + L.keys), *tkeys = (unsigned long long*)(ws + L.tkeys);
-    int32_t* tidx = (int32_t*)(ws + L.tidx);
-    uint8_t* mask2 = (uint8_t*)(ws + L.mask2);
-    int32_t *keep = (int32_t*)(ws + L.keep), *nbrs = nbrs_out ? nbrs_out : (int32_t*)(ws + L.nbrs);
-    const int nbp = (int)((n + 255) / 256), nbc = (n_cap + 255) / 256;
-    const unsigned bit = (unsigned)label_bit, tmask = (unsigned)L.M - 1u;
-#define FC_VALID(T)                                                                                                                       \
-    do {                                                                                                                                  \
-        if (label_bytes == 1) fc_valid_kernel<T, uint8_t><<<nbp, 256, 0, st>>>((const T*)depth, (const uint8_t*)labels, bit, n, valid, bit_dev);   \
-        else if (label_bytes == 2) fc_valid_kernel<T, uint16_t><<<nbp, 256, 0, st>>>((const T*)depth, (const uint16_t*)labels, bit, n, valid, bit_dev); \
-        else fc_valid_kernel<T, uint32_t><<<nbp, 256, 0, st>>>((const T*)depth, (const uint32_t*)labels, bit, n, valid, bit_dev);                  \
-    } while (0)
-    if (depth_is_u16) FC_VALID(uint16_t); else FC_VALID(float);
-#undef FC_VALID
-    int rc = cppf_compact_mask(valid, n, pix, count1, ws + L.cmp1, cppf_compact_workspace_bytes(n), stream);        // np.where order (:612)
-    if (rc) return rc;
-    Kinv K;
-    for (int i = 0; i < 9; ++i) K.k[i] = kinv_host[i];
-    fc_clear_kernel<<<(L.M + 255) / 256, 256, 0, st>>>(tkeys, tidx, L.M);
-    if (depth_is_u16) fc_points_kernel<uint16_t><<<nbc, 256, 0, st>>>((const uint16_t*)depth, pix, count1, W, K, divisor, res, n_cap, pcf, keys, tkeys, tidx, tmask);
-    else fc_points_kernel<float><<<nbc, 256, 0, st>>>((const float*)depth, pix, count1, W, K, divisor, res, n_cap, pcf, keys, tkeys, tidx, tmask);
-    fc_mark_kernel<<<nbc, 256, 0, st>>>(keys, tkeys, tidx, tmask, count1, n_cap, mask2);
-    rc = cppf_compact_mask(mask2, n_cap, keep, count2, ws + L.cmp2, cppf_compact_workspace_bytes(n_cap), stream);     // :140
-    if (rc) return rc;
-    fc_gather_kernel<<<nbc, 256, 0, st>>>(pcf, keep, count2, k_min, n_cap, pc_out, shape_out);                       // :141
-    rc = cppf_knn_dyn(pc_out, n_cap, shape_out, knn_k, nbrs, stream);                                                 // :142
-    if (rc) return rc;
-    fc_normals_kernel<<<nbc, 256, 0, st>>>(pc_out, nbrs, shape_out, knn_k, nrm_out);
-    fc_grid_kernel<<<1, 1024, 0, st>>>(pc_out, (float)res, corner_out, shape_out);                                    // :194-195
-    return (int)hipGetLastError();
-}
-
-int cppf_frame_cloud_dyn(const void* depth, int depth_is_u16, const void* labels, int label_bytes, int label_bit, int H, int W,
-                         const double* kinv_host, double divisor, double res, int knn_k, int k_min, int n_cap, float* pc_out,
-                         float* nrm_out, float* corner_out, int32_t* shape_out, int32_t* nbrs_out, void* workspace, size_t workspace_bytes,
-                         void* stream)
-{
-    return frame_cloud_impl(depth, depth_is_u16, labels, label_bytes, label_bit, nullptr, H, W, kinv_host, divisor, res, knn_k, k_min, n_cap,
-                            pc_out, nrm_out, corner_out, shape_out, nbrs_out, workspace, workspace_bytes, stream);
-}
-
-int cppf_frame_cloud_dyn_bit(const void* depth, int depth_is_u16, const void* labels, int label_bytes, const int32_t* label_bit_dev, int H,
-                             int W, const double* kinv_host, double divisor, double res, int knn_k, int k_min, int n_cap, float* pc_out,
-                             float* nrm_out, float* corner_out, int32_t* shape_out, int32_t* nbrs_out, void* workspace,
-                             size_t workspace_bytes, void* stream)
-{
-    if (!label_bit_dev) return CPPF_EINVAL;
-    return frame_cloud_impl(depth, depth_is_u16, labels, label_bytes, 0, label_bit_dev, H, W, kinv_host, divisor, res, knn_k, k_min, n_cap,
-                            pc_out, nrm_out, corner_out, shape_out, nbrs_out, workspace, workspace_bytes, stream);
-}
-
-int cppf_frame_cloud_dyn_batch(int n_items, const CppfFrameCloudItem* items, const void* depth, int depth_is_u16, const void* labels,
-                               int label_bytes, int H, int W, const double* kinv_host, double divisor, void* stream)
-{
-    if (n_items < 1 || n_items > FCB_MAX || !items) return CPPF_EINVAL;
     if (H < 1 || W < 1 || (int64_t)H * W > 0x7fffffffll || !depth || !labels || !kinv_host || !(divisor > 0.0)) return CPPF_EINVAL;
     if (label_bytes != 1 && label_bytes != 2 && label_bytes != 4) return CPPF_EINVAL;
-    const int64_t n = (int64_t)H * W;
-    if ((n + CMP_BLOCK - 1) / CMP_BLOCK > CMP_SELF_MAX) return CPPF_EUNSUPPORTED;
-    FcbBatch B;
     memset(&B, 0, sizeof(B));
-    B.depth = depth; B.labels = labels; B.n_pix = n; B.divisor = divisor; B.W = W; B.label_bytes = label_bytes;
+    B.depth = depth; B.labels = labels; B.n_pix = (int64_t)H * W; B.divisor = divisor; B.W = W; B.label_bytes = label_bytes;
     for (int i = 0; i < 9; ++i) B.K.k[i] = kinv_host[i];
+    return 0;
+}
+// the self-counting compaction serves up to CMP_SELF_MAX chunks of pixels
+static bool fcb_too_many_chunks(const FcbBatch& B) { return (B.n_pix + CMP_BLOCK - 1) / CMP_BLOCK > CMP_SELF_MAX; }
+
+// one member's arguments -> its FcbItem (label_bit: the bit by value when it.label_bit_dev is NULL)
+static int fcb_member(FcbItem& I, const CppfFrameCloudItem& it, int label_bit, int H, int W)
+{
+    if (!it.pc_out || !it.nrm_out || !it.corner_out || !it.shape_out) return CPPF_EINVAL;
+    if (it.n_cap < 1 || it.knn_k < 1 || it.knn_k > 64 || it.knn_k > it.n_cap || it.k_min < it.knn_k || !(it.res > 0.0)) return CPPF_EINVAL;
+    if (it.n_pairs < 0 || (it.n_pairs > 0 && (!it.idx || !it.seed_dev || (reinterpret_cast<uintptr_t>(it.idx) & (it.idx_is_i64 ? 15 : 7)))))
+        return CPPF_EINVAL;
+    const FcLayout L = fc_layout(H, W, it.n_cap, it.knn_k);
+    if (!it.workspace || it.workspace_bytes < L.total) return CPPF_EWORKSPACE;
+    char* ws = static_cast<char*>(it.workspace);
+    I.bit_dev = it.label_bit_dev; I.bit = label_bit; I.seed_dev = it.seed_dev;
+    I.valid = (uint8_t*)(ws + L.valid); I.mask2 = (uint8_t*)(ws + L.mask2);
+    I.cc1 = (int32_t*)(ws + L.cmp1); I.cc2 = (int32_t*)(ws + L.cmp2); I.pix = (int32_t*)(ws + L.pix);
+    I.count1 = (int32_t*)(ws + L.count); I.count2 = (int32_t*)(ws + L.count + 64);
+    I.tidx = (int32_t*)(ws + L.tidx); I.keep = (int32_t*)(ws + L.keep); I.nbrs = it.nbrs_out ? it.nbrs_out : (int32_t*)(ws + L.nbrs);
+    I.shape_out = it.shape_out; I.pcf = (float*)(ws + L.pcf); I.pc_out = it.pc_out; I.nrm_out = it.nrm_out; I.corner_out = it.corner_out;
+    I.u_tr = it.u_tr; I.u_rot = it.u_rot; I.keys = (unsigned long long*)(ws + L.keys); I.tkeys = (unsigned long long*)(ws + L.tkeys);
+    I.idx = it.n_pairs > 0 ? it.idx : nullptr; I.res = it.res; I.n_pairs = it.n_pairs;
+    I.knn_k = it.knn_k; I.k_min = it.k_min; I.n_cap = it.n_cap; I.M = L.M; I.idx_is_i64 = it.idx_is_i64;
+    return 0;
+}
+
+// the eight launches for the first n_items members of B
+static int fcb_launch(FcbBatch& B, int n_items, int depth_is_u16, void* stream)
+{
     CppfKnnBatchItem knn[FCB_MAX];
     int cap_max = 0;
     int64_t max_pairs = 0;
     for (int i = 0; i < n_items; ++i) {
-        const CppfFrameCloudItem& it = items[i];
-        if (!it.label_bit_dev || !it.pc_out || !it.nrm_out || !it.corner_out || !it.shape_out) return CPPF_EINVAL;
-        if (it.n_cap < 1 || it.knn_k < 1 || it.knn_k > 64 || it.knn_k > it.n_cap || it.k_min < it.knn_k || !(it.res > 0.0)) return CPPF_EINVAL;
-        if (it.n_pairs < 0 || (it.n_pairs > 0 && (!it.idx || !it.seed_dev || (reinterpret_cast<uintptr_t>(it.idx) & (it.idx_is_i64 ? 15 : 7)))))
-            return CPPF_EINVAL;
-        const FcLayout L = fc_layout(H, W, it.n_cap, it.knn_k);
-        if (!it.workspace || it.workspace_bytes < L.total) return CPPF_EWORKSPACE;
-        char* ws = static_cast<char*>(it.workspace);
-        FcbItem& I = B.item[i];
-        I.bit_dev = it.label_bit_dev; I.seed_dev = it.seed_dev;
-        I.valid = (uint8_t*)(ws + L.valid); I.mask2 = (uint8_t*)(ws + L.mask2);
-        I.cc1 = (int32_t*)(ws + L.cmp1); I.cc2 = (int32_t*)(ws + L.cmp2); I.pix = (int32_t*)(ws + L.pix);
-        I.count1 = (int32_t*)(ws + L.count); I.count2 = (int32_t*)(ws + L.count + 64);
-        I.tidx = (int32_t*)(ws + L.tidx); I.keep = (int32_t*)(ws + L.keep); I.nbrs = it.nbrs_out ? it.nbrs_out : (int32_t*)(ws + L.nbrs);
-        I.shape_out = it.shape_out; I.pcf = (float*)(ws + L.pcf); I.pc_out = it.pc_out; I.nrm_out = it.nrm_out; I.corner_out = it.corner_out;
-        I.u_tr = it.u_tr; I.u_rot = it.u_rot; I.keys = (unsigned long long*)(ws + L.keys); I.tkeys = (unsigned long long*)(ws + L.tkeys);
-        I.idx = it.n_pairs > 0 ? it.idx : nullptr; I.res = it.res; I.n_pairs = it.n_pairs;
-        I.knn_k = it.knn_k; I.k_min = it.k_min; I.n_cap = it.n_cap; I.M = L.M; I.idx_is_i64 = it.idx_is_i64;
-        knn[i] = CppfKnnBatchItem{it.pc_out, I.nbrs, it.shape_out, it.n_cap, it.knn_k};
-        cap_max = it.n_cap > cap_max ? it.n_cap : cap_max;
-        max_pairs = it.n_pairs > max_pairs ? it.n_pairs : max_pairs;
+        const FcbItem& I = B.item[i];
+        knn[i] = CppfKnnBatchItem{I.pc_out, I.nbrs, I.shape_out, I.n_cap, I.knn_k};
+        cap_max = I.n_cap > cap_max ? I.n_cap : cap_max;
+        max_pairs = I.n_pairs > max_pairs ? I.n_pairs : max_pairs;
     }
     hipStream_t st = (hipStream_t)stream;
     const unsigned ni = (unsigned)n_items;
-    const unsigned nbp = (unsigned)((n + CMP_BLOCK - 1) / CMP_BLOCK), nbc = (unsigned)((cap_max + 255) / 256),
+    const unsigned nbp = (unsigned)((B.n_pix + CMP_BLOCK - 1) / CMP_BLOCK), nbc = (unsigned)((cap_max + 255) / 256),
                    nbc4 = (unsigned)((cap_max + CMP_BLOCK - 1) / CMP_BLOCK);
     if (depth_is_u16) fcb_valid_kernel<uint16_t><<<dim3(nbp, ni), CMP_BLOCK, 0, st>>>(B);
     else fcb_valid_kernel<float><<<dim3(nbp, ni), CMP_BLOCK, 0, st>>>(B);
@@ -748,6 +587,57 @@ int cppf_frame_cloud_dyn_batch(int n_items, const CppfFrameCloudItem* items, con
     B.n_sample_blocks = (int)(nsb < 1 ? 1 : nsb);
     fcb_finish_kernel<<<dim3(nbc + 1 + (max_pairs > 0 ? (unsigned)B.n_sample_blocks : 0u), ni), 256, 0, st>>>(B, (int)nbc);
     return (int)hipGetLastError();
+}
+
+// the single entry points: a batch of one member without draws, its bit by value (it.label_bit_dev NULL) or in memory
+static int frame_cloud_one(const void* depth, int depth_is_u16, const void* labels, int label_bytes, int label_bit, int H, int W,
+                           const double* kinv_host, double divisor, const CppfFrameCloudItem& it, void* stream)
+{
+    FcbBatch B;
+    int rc = fcb_frame(B, depth, labels, label_bytes, H, W, kinv_host, divisor);
+    if (rc) return rc;
+    if (label_bit < 0 || label_bit >= 8 * label_bytes) return CPPF_EINVAL;
+    rc = fcb_member(B.item[0], it, label_bit, H, W);
+    if (rc) return rc;
+    if (fcb_too_many_chunks(B)) return CPPF_EUNSUPPORTED;
+    return fcb_launch(B, 1, depth_is_u16, stream);
+}
+
+int cppf_frame_cloud_dyn(const void* depth, int depth_is_u16, const void* labels, int label_bytes, int label_bit, int H, int W,
+                         const double* kinv_host, double divisor, double res, int knn_k, int k_min, int n_cap, float* pc_out,
+                         float* nrm_out, float* corner_out, int32_t* shape_out, int32_t* nbrs_out, void* workspace, size_t workspace_bytes,
+                         void* stream)
+{
+    const CppfFrameCloudItem it = {nullptr, nullptr, pc_out, nrm_out, corner_out, shape_out, nbrs_out, nullptr, nullptr, nullptr,
+                                   workspace, workspace_bytes, res, 0, knn_k, k_min, n_cap, 0};
+    return frame_cloud_one(depth, depth_is_u16, labels, label_bytes, label_bit, H, W, kinv_host, divisor, it, stream);
+}
+
+int cppf_frame_cloud_dyn_bit(const void* depth, int depth_is_u16, const void* labels, int label_bytes, const int32_t* label_bit_dev, int H,
+                             int W, const double* kinv_host, double divisor, double res, int knn_k, int k_min, int n_cap, float* pc_out,
+                             float* nrm_out, float* corner_out, int32_t* shape_out, int32_t* nbrs_out, void* workspace,
+                             size_t workspace_bytes, void* stream)
+{
+    if (!label_bit_dev) return CPPF_EINVAL;
+    const CppfFrameCloudItem it = {label_bit_dev, nullptr, pc_out, nrm_out, corner_out, shape_out, nbrs_out, nullptr, nullptr, nullptr,
+                                   workspace, workspace_bytes, res, 0, knn_k, k_min, n_cap, 0};
+    return frame_cloud_one(depth, depth_is_u16, labels, label_bytes, 0, H, W, kinv_host, divisor, it, stream);
+}
+
+int cppf_frame_cloud_dyn_batch(int n_items, const CppfFrameCloudItem* items, const void* depth, int depth_is_u16, const void* labels,
+                               int label_bytes, int H, int W, const double* kinv_host, double divisor, void* stream)
+{
+    if (n_items < 1 || n_items > FCB_MAX || !items) return CPPF_EINVAL;
+    FcbBatch B;
+    int rc = fcb_frame(B, depth, labels, label_bytes, H, W, kinv_host, divisor);
+    if (rc) return rc;
+    if (fcb_too_many_chunks(B)) return CPPF_EUNSUPPORTED;
+    for (int i = 0; i < n_items; ++i) {
+        if (!items[i].label_bit_dev) return CPPF_EINVAL;
+        rc = fcb_member(B.item[i], items[i], 0, H, W);
+        if (rc) return rc;
+    }
+    return fcb_launch(B, n_items, depth_is_u16, stream);
 }
 
 int cppf_sample_pairs(long long* idx, float* u_tr, float* u_rot, int64_t n_pairs, int64_t n_points, const int32_t* n_dev,

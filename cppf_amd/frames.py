@@ -90,8 +90,8 @@ class FrameRunner:
         """max_members: pipelines kept (each with its captured graph and ~0.1 GB of buffers at 100 000 pairs); max_chains: captured
         chains kept (at least the groups of one frame: a chain of the running frame is never evicted).
         chain_len: instances per captured chain (None: two chains of equal length from four instances on, at most 8 members each);
-        batch_prestage=False: round 5's form, every member's own sixteen pre-processing launches at the head of its chain and
-        chains of ceil(n / n_lanes)."""
+        batch_prestage=False: round 5's form, every member's own frame stage (a batch of one) at the head of its chain and chains
+        of ceil(n / n_lanes)."""
         from collections import OrderedDict
         self.encoders, self.point_encoders, self.device = encoders, point_encoders, device
         self.intrinsics = np.asarray(intrinsics, np.float64)
@@ -149,7 +149,6 @@ class FrameRunner:
         tight mask) until an instance of the category came back with "shape beyond the launch's capacities" -- from then on the
         category's members are of the many-tile class (any grid of up to 64 tiles)."""
         from . import _lib
-        from ._torch_util import call, scratch
         from .inference import PosePipeline
         cap = max(self.cap_bucket, 1 << int(np.ceil(np.log2(max(n_mask, 1)))))
         key = (cat, cap, cat in self._many_tile_cats)
@@ -176,31 +175,24 @@ class FrameRunner:
             raise RuntimeError("FrameRunner: no free member record; raise max_members")
         row = self._free_rows.pop()
         slot = self._slots_dev[row]                   # {label bit (low 32 bits), Philox key}: written per frame
-        dev, depth, labels, kinv = self.device, self._depth, self._labels, self.kinv
         # the normals are fitted on the k = cfg.knn neighbour sets; a point encoder with the same k (config/config.yaml: 60 for both)
         # reuses them instead of searching again (the stage writes them straight into the pipeline's neighbour buffer)
         share = pipe.point_encoder is not None and pipe.point_encoder.k == cfg.knn
         pipe.nbrs_ready = share
-        nbrs = pipe._nbrs if share else None
-
-        def prestage():
-            call("cppf_frame_cloud_dyn_bit", dev, depth, 1, labels, 4, slot, H, W, kinv, 1000.0, float(cfg.res), cfg.knn, cfg.knn + 1, cap,
-                 pipe.pc, pipe.nrm, pipe.corner, pipe.shape, nbrs, scratch(ws))
-            # pairs and bin uniforms: N from the shape record the stage just wrote, the key from the member's record
-            call("cppf_sample_pairs", dev, pipe.idx, pipe.u_tr, pipe.u_rot, pipe.idx.shape[0], 1, pipe.shape, 0, slot.data_ptr() + 8)
-        mem = dict(pipe=pipe, pre=prestage, slot=slot, row=row, ws=ws, key=key, cfg=cfg, cap=cap, nbrs=nbrs)
+        mem = dict(pipe=pipe, slot=slot, row=row, ws=ws, key=key, cfg=cfg, cap=cap, nbrs=pipe._nbrs if share else None)
+        mem["pre"] = self._batch_prestage([mem])      # (a member outside a chain: a batch of one)
         self._members[id(pipe)] = mem
         self._pool.setdefault(key, []).append(mem)
         return mem
 
     def _batch_prestage(self, mems):
-        """the frame stage of a chain's members in eight launches (cppf_frame_cloud_dyn_batch) instead of sixteen each: a callable
-        for the head of their captured chain"""
+        """the frame stage of a chain's members and their pair draws in eight launches (cppf_frame_cloud_dyn_batch), whether one member
+        or eight: a callable for the head of their captured chain"""
         from . import _lib
         from ._torch_util import call, fill, scratch
         dev, H, W = self.device, self._hw[0], self._hw[1]
         depth, labels, kinv = self._depth, self._labels, self.kinv
-        arr = (_lib.FrameCloudItem * len(mems))()
+        n, arr = len(mems), (_lib.FrameCloudItem * len(mems))()
         for a, m in zip(arr, mems):
             pipe, cfg = m["pipe"], m["cfg"]
             fill(a, label_bit_dev=m["slot"], seed_dev=m["slot"].data_ptr() + 8, pc_out=pipe.pc, nrm_out=pipe.nrm, corner_out=pipe.corner,
@@ -209,7 +201,7 @@ class FrameRunner:
                  idx_is_i64=pipe.idx.dtype == torch.int64)
 
         def prestage():
-            call("cppf_frame_cloud_dyn_batch", dev, len(mems), arr, depth, 1, labels, 4, H, W, kinv, 1000.0)
+            call("cppf_frame_cloud_dyn_batch", dev, n, arr, depth, 1, labels, 4, H, W, kinv, 1000.0)
         return prestage
 
     def _chain_for(self, pipes, pres, busy):

@@ -668,7 +668,8 @@ int cppf_point_encoder_forward_train(const float* pc, const float* nrm, const in
  * every buffer; rows >= N of pc_out / nrm_out are left untouched.  nbrs_out (may be NULL): device i32[n_cap, knn_k] that receives the
  * neighbour sets the normals were fitted on -- cppf_knn's output, which a point encoder with the same k can reuse instead of
  * searching again (nocs/inference.py:180 computes the same cdist + topk).  Results equal the four single calls on the same inputs, bit for
- * bit.  cppf_mod_pairs_dyn: idx[i] <- idx[i] mod N for pairs drawn as full-range non-negative integers before N was known (:177). */
+ * bit.  Both entry points are cppf_frame_cloud_dyn_batch (below) for one member without pair draws, so like it they return
+ * CPPF_EUNSUPPORTED for a frame of more than 8 388 608 pixels (8 192 compaction chunks of 1 024).  cppf_mod_pairs_dyn: idx[i] <- idx[i] mod N for pairs drawn as full-range non-negative integers before N was known (:177). */
 size_t cppf_frame_cloud_workspace_bytes(int H, int W, int n_cap, int knn_k);
 int cppf_frame_cloud_dyn(const void* depth, int depth_is_u16, const void* labels, int label_bytes, int label_bit, int H, int W,
                          const double* kinv_host, double divisor, double res, int knn_k, int k_min, int n_cap, float* pc_out,
@@ -681,10 +682,10 @@ int cppf_frame_cloud_dyn_bit(const void* depth, int depth_is_u16, const void* la
                              int W, const double* kinv_host, double divisor, double res, int knn_k, int k_min, int n_cap, float* pc_out,
                              float* nrm_out, float* corner_out, int32_t* shape_out, int32_t* nbrs_out, void* workspace,
                              size_t workspace_bytes, void* stream);
-/* The frame stage of up to 8 instances of ONE frame (nocs/inference.py:120 loops over them) in EIGHT launches instead of sixteen
- * per instance, their pair lists and bin uniforms included (cppf_sample_pairs, the key read from *seed_dev): per instance the results
- * of cppf_frame_cloud_dyn_bit + cppf_sample_pairs, bit for bit (ABI 4).  A frame's chain is launch-bound -- ~15 kernels of ~5 us per
- * instance, and a hipGraph launch costs the host per kernel node -- so a launch serves every member (blockIdx.y), the mask kernels
+/* The frame stage of up to 8 instances of ONE frame (nocs/inference.py:120 loops over them) in EIGHT launches, their pair lists and
+ * bin uniforms included (the key read from *seed_dev): per instance the results of the four single calls above (cppf_backproject,
+ * cppf_voxel_dedupe, cppf_knn, cppf_estimate_normals) and the draws of cppf_sample_pairs, bit for bit (ABI 4).  A frame's chain is
+ * launch-bound -- a hipGraph launch costs the host per kernel node -- so a launch serves every member (blockIdx.y), the mask kernels
  * count their own chunks (no count + scan launches), the first one clears the voxel table, the normals launch also sets up the grid
  * and draws the pairs.  Every member has its own capacity, resolution, k, workspace (cppf_frame_cloud_workspace_bytes) and outputs. */
 typedef struct CppfFrameCloudItem {

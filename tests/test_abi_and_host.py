@@ -617,6 +617,9 @@ def test_round5_entry_points_host_logic_without_a_device():
     w1, w2 = L.cppf_frame_cloud_workspace_bytes(480, 640, 4096, 60), L.cppf_frame_cloud_workspace_bytes(480, 640, 65536, 60)
     assert 0 < w1 < w2 < (1 << 27) and L.cppf_frame_cloud_workspace_bytes(0, 640, 4096, 60) == 0
     assert L.cppf_frame_cloud_dyn(None, 1, None, 2, 0, 480, 640, None, 1000.0, 0.004, 60, 61, 4096, None, None, None, None, None, None, 0, None) == -1
+    # a frame of more than 8 388 608 pixels is CPPF_EUNSUPPORTED in every form of the stage; NULL pointers are refused first
+    big = (None, 1, None, 2, 0, 4096, 2049, None, 1000.0, 0.004, 60, 61, 4096, None, None, None, None, None, None, 0, None)
+    assert L.cppf_frame_cloud_dyn(*big) == -1 and L.cppf_frame_cloud_dyn_bit(*big[:4], None, *big[5:]) == -1
 
 
 def test_bench_compact_line_fits_the_drivers_tail():

@@ -126,7 +126,7 @@ def test_real_frame_preprocessing_equals_oracle_and_poses_are_sane(oracle, dev):
 @pytest.mark.parametrize("batch_prestage", [True, False])
 def test_frame_runner_equals_the_eager_loop(oracle, dev, batch_prestage):
     """(batch_prestage: the members' frame stages in eight shared launches -- cppf_frame_cloud_dyn_batch, two chains of four for the
-    frame's eight instances -- or every member's own sixteen, three chains on three lanes.)
+    frame's eight instances -- or every member's own eight (a batch of one), three chains on three lanes.)
     FrameRunner (depth + one label image uploaded per frame, every instance's pre-processing count-driven on the device at the
     head of a captured, shape-polymorphic chain, the instances of a lane sharing their launches, ONE read-back per frame) gives
     frame_poses' poses -- the eager per-instance loop, nocs/inference.py:108-142,177-339 -- bit for bit: first sighting (members'
@@ -284,17 +284,103 @@ def test_pipelined_frames_equal_the_synchronous_ones(dev):
     assert pend[0].result() is got[0]           # idempotent
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("depth_float,label_bytes,idx64", [(False, 4, True), (True, 1, False), (False, 2, False)])
-def test_frame_cloud_batch_equals_the_single_entry_points(dev, depth_float, label_bytes, idx64):
-    """cppf_frame_cloud_dyn_batch (eight launches for all members) against cppf_frame_cloud_dyn_bit + cppf_sample_pairs per member
-    through the C ABI: members of different capacity, resolution and k, u16 and f32 depth, 8 / 16 / 32-bit label images, int32 and
-    int64 pair lists, a member whose mask is empty, one with fewer points than k_min: clouds, normals, neighbour sets, corners,
-    shape records, pairs and uniforms bit for bit"""
-    import ctypes as C
+def _eager_frame_cloud(d_dev, mask, res, k, k_min, n_cap):
+    """What the frame stage must leave for one member, from the eager path alone (frames.instance_cloud's steps -- the sort-based
+    cppf_backproject / cppf_voxel_dedupe, cppf_knn, cppf_estimate_normals -- and the host's grid_shape): the first n_cap valid
+    pixels of the mask -> dict(n_raw = de-duplicated points, n = 0 below k_min, pc, and from k_min on nrm, nbrs, corner, dims)"""
     import torch
+    from cppf_amd._torch_util import call
+    from cppf_amd.frames import NOCS_INTRINSICS
+    from cppf_amd.inference import grid_shape
+    from cppf_amd.utils.util import backproject, estimate_normals, sparse_quantize
+    pts, _ = backproject(d_dev, NOCS_INTRINSICS, mask, return_device=True)
+    n_valid = pts.shape[0]
+    pts = pts[:n_cap]
+    e = dict(n_valid=n_valid, n_raw=0, n=0, pc=torch.empty((0, 3), dtype=torch.float32, device=d_dev.device))
+    if n_valid == 0:
+        return e
+    pc = pts / 1000.0
+    pc = torch.stack([-pc[:, 0], -pc[:, 1], pc[:, 2]], -1)
+    _, keep = sparse_quantize(pc.float(), return_index=True, quantization_size=res)
+    pc = pc[keep].float().contiguous()
+    e.update(n_raw=pc.shape[0], pc=pc)
+    if pc.shape[0] >= k_min:
+        nbrs = torch.empty((pc.shape[0], k), dtype=torch.int32, device=pc.device)
+        call("cppf_knn", pc.device, pc, None, pc.shape[0], k, nbrs)
+        corners, dims = grid_shape(pc.cpu().numpy(), res)
+        e.update(n=pc.shape[0], nrm=estimate_normals(pc, k), nbrs=nbrs, corner=corners[0], dims=dims)
+    return e
+
+
+def _frame_cloud_buffers(L, dev, H, W, cap, k, n_pairs=0, idt=None):
+    import torch
+    z = lambda *s_, dt=torch.float32: torch.full(s_, -7, dtype=dt, device=dev)
+    b = dict(pc=z(cap, 3), nrm=z(cap, 3), corner=z(3), shape=z(4, dt=torch.int32), nbrs=z(cap, k, dt=torch.int32),
+             ws=torch.zeros(int(L.cppf_frame_cloud_workspace_bytes(H, W, cap, k)), dtype=torch.uint8, device=dev),
+             slot=torch.zeros(2, dtype=torch.int64, device=dev))
+    if n_pairs:
+        b.update(idx=z(n_pairs, 2, dt=idt), u_tr=z(n_pairs, 2), u_rot=z(n_pairs, 2))
+    return b
+
+
+def _frame_cloud_batch(L, dev, bufs, spec, dd, depth_u16, ld, label_bytes, H, W, kinv, n_pairs=0, idx64=0):
+    """cppf_frame_cloud_dyn_batch on the members' buffers; -> the item array"""
+    import ctypes as C
     from cppf_amd import _lib
     from cppf_amd._torch_util import stream_ptr
+    arr = (_lib.FrameCloudItem * len(spec))()
+    for a, b, (cap, res, k) in zip(arr, bufs, spec):
+        a.label_bit_dev, a.seed_dev = b["slot"].data_ptr(), b["slot"].data_ptr() + 8
+        a.pc_out, a.nrm_out, a.corner_out, a.shape_out, a.nbrs_out = (b[n].data_ptr() for n in ("pc", "nrm", "corner", "shape", "nbrs"))
+        if n_pairs:
+            a.idx, a.u_tr, a.u_rot = b["idx"].data_ptr(), b["u_tr"].data_ptr(), b["u_rot"].data_ptr()
+        a.workspace, a.workspace_bytes = b["ws"].data_ptr(), b["ws"].numel()
+        a.res, a.n_pairs, a.knn_k, a.k_min, a.n_cap, a.idx_is_i64 = res, n_pairs, k, k + 1, cap, idx64
+    _lib.check(L.cppf_frame_cloud_dyn_batch(len(spec), C.cast(arr, C.c_void_p), dd.data_ptr(), depth_u16, ld.data_ptr(), label_bytes, H, W,
+                                            kinv.ctypes.data, 1000.0, stream_ptr(dev)), "cppf_frame_cloud_dyn_batch")
+    return arr
+
+
+def _frame_cloud_single(L, dev, b, spec, dd, depth_u16, ld, label_bytes, H, W, kinv, bit=None):
+    """cppf_frame_cloud_dyn_bit (the bit in b["slot"]) or, with `bit`, cppf_frame_cloud_dyn (the bit by value) on one member's buffers"""
+    from cppf_amd import _lib
+    from cppf_amd._torch_util import stream_ptr
+    cap, res, k = spec
+    fn, name = (L.cppf_frame_cloud_dyn_bit, "cppf_frame_cloud_dyn_bit") if bit is None else (L.cppf_frame_cloud_dyn, "cppf_frame_cloud_dyn")
+    _lib.check(fn(dd.data_ptr(), depth_u16, ld.data_ptr(), label_bytes, b["slot"].data_ptr() if bit is None else bit, H, W, kinv.ctypes.data,
+                  1000.0, res, k, k + 1, cap, b["pc"].data_ptr(), b["nrm"].data_ptr(), b["corner"].data_ptr(), b["shape"].data_ptr(),
+                  b["nbrs"].data_ptr(), b["ws"].data_ptr(), b["ws"].numel(), stream_ptr(dev)), name)
+
+
+def _assert_frame_cloud(b, e, tag):
+    """whole buffers: the stage's results where the eager path has them, the -7 fill everywhere else"""
+    import torch
+    n, n_raw = e["n"], e["n_raw"]
+    assert int(b["shape"][0]) == n, (tag, b["shape"], n, n_raw)
+    # (the de-duplicated cloud is written whatever its size; a member below k_min reports N = 0, an origin corner and a 1x1x1 grid,
+    # and keeps its normals and neighbour rows untouched)
+    assert torch.equal(b["pc"][:n_raw], e["pc"]) and torch.all(b["pc"][n_raw:] == -7), tag
+    assert torch.all(b["nrm"][n:] == -7) and torch.all(b["nbrs"][n:] == -7), tag
+    if n == 0:
+        assert b["shape"].tolist() == [0, 1, 1, 1] and b["corner"].tolist() == [0.0, 0.0, 0.0], (tag, b["shape"], b["corner"])
+        return
+    assert torch.equal(b["nrm"][:n], e["nrm"]) and torch.equal(b["nbrs"][:n], e["nbrs"]), tag
+    assert tuple(b["shape"][1:].tolist()) == tuple(e["dims"]) and np.array_equal(b["corner"].cpu().numpy(), e["corner"]), tag
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("depth_float,label_bytes,idx64", [(False, 4, True), (True, 1, False), (False, 2, False)])
+def test_frame_cloud_entry_points_equal_the_eager_path(dev, depth_float, label_bytes, idx64):
+    """cppf_frame_cloud_dyn_batch (eight launches for all members, their pair draws included) and the single entry points (a batch
+    of one: cppf_frame_cloud_dyn_bit on members 0 and 3, cppf_frame_cloud_dyn with the bit by value on member 1) through the C ABI,
+    each against the eager path, which shares no kernel with the frame stage beyond the normals body -- backproject -> /1000 ->
+    flips -> sparse_quantize -> cppf_knn -> estimate_normals, inference.grid_shape, synthetic.philox_pairs: members of different
+    capacity, resolution and k, u16 and f32 depth, 8 / 16 / 32-bit label images, int32 and int64 pair lists, a member whose mask is
+    empty, one with fewer points than k_min: clouds, normals, neighbour sets, corners, shape records, pairs and uniforms bit for bit"""
+    import ctypes as C
+    import torch
+    import cppf_amd.synthetic as syn
+    from cppf_amd import _lib
     from cppf_amd.frames import NOCS_INTRINSICS
     from cppf_amd.utils.util import read_depth_png
     L = _lib.lib()
@@ -310,57 +396,82 @@ def test_frame_cloud_batch_equals_the_single_entry_points(dev, depth_float, labe
     dd = torch.from_numpy(depth.astype(np.float32) if depth_float else depth.view(np.int16)).to(dev)
     ld = torch.from_numpy(labels.view({1: np.uint8, 2: np.int16, 4: np.int32}[label_bytes])).to(dev)
     kinv = np.ascontiguousarray(np.linalg.inv(NOCS_INTRINSICS))
-    n_pairs = 5000
-    idt = torch.int64 if idx64 else torch.int32
-
-    def buffers(cap, k):
-        z = lambda *s_, dt=torch.float32: torch.full(s_, -7, dtype=dt, device=dev)
-        return dict(pc=z(cap, 3), nrm=z(cap, 3), corner=z(3), shape=z(4, dt=torch.int32), nbrs=z(cap, k, dt=torch.int32),
-                    idx=z(n_pairs, 2, dt=idt), u_tr=z(n_pairs, 2), u_rot=z(n_pairs, 2),
-                    ws=torch.zeros(int(L.cppf_frame_cloud_workspace_bytes(H, W, cap, k)), dtype=torch.uint8, device=dev),
-                    slot=torch.zeros(2, dtype=torch.int64, device=dev))
-
-    one, many = [buffers(c, k) for c, _, k in spec], [buffers(c, k) for c, _, k in spec]
-    for i, b in enumerate(one + many):
-        j = i % len(spec)
+    n_pairs, u16 = 5000, 0 if depth_float else 1
+    many = [_frame_cloud_buffers(L, dev, H, W, c, k, n_pairs, torch.int64 if idx64 else torch.int32) for c, _, k in spec]
+    one = {j: _frame_cloud_buffers(L, dev, H, W, spec[j][0], spec[j][2]) for j in (0, 1, 3)}
+    for j, b in list(enumerate(many)) + list(one.items()):
         b["slot"].copy_(torch.tensor([j, 1000003 * 7 + j], dtype=torch.int64))
     with torch.cuda.device(dev):
-        for b, (cap, res, k) in zip(one, spec):
-            _lib.check(L.cppf_frame_cloud_dyn_bit(dd.data_ptr(), 0 if depth_float else 1, ld.data_ptr(), label_bytes, b["slot"].data_ptr(), H, W,
-                                                  kinv.ctypes.data, 1000.0, res, k, k + 1, cap, b["pc"].data_ptr(), b["nrm"].data_ptr(),
-                                                  b["corner"].data_ptr(), b["shape"].data_ptr(), b["nbrs"].data_ptr(), b["ws"].data_ptr(),
-                                                  b["ws"].numel(), stream_ptr(dev)), "cppf_frame_cloud_dyn_bit")
-            if idx64:
-                _lib.check(L.cppf_sample_pairs(b["idx"].data_ptr(), b["u_tr"].data_ptr(), b["u_rot"].data_ptr(), n_pairs, 1,
-                                               b["shape"].data_ptr(), 0, b["slot"].data_ptr() + 8, stream_ptr(dev)), "cppf_sample_pairs")
-        arr = (_lib.FrameCloudItem * len(spec))()
-        for a, b, (cap, res, k) in zip(arr, many, spec):
-            a.label_bit_dev, a.seed_dev = b["slot"].data_ptr(), b["slot"].data_ptr() + 8
-            a.pc_out, a.nrm_out, a.corner_out, a.shape_out, a.nbrs_out = (b[n].data_ptr() for n in ("pc", "nrm", "corner", "shape", "nbrs"))
-            a.idx, a.u_tr, a.u_rot, a.workspace, a.workspace_bytes = b["idx"].data_ptr(), b["u_tr"].data_ptr(), b["u_rot"].data_ptr(), b["ws"].data_ptr(), b["ws"].numel()
-            a.res, a.n_pairs, a.knn_k, a.k_min, a.n_cap, a.idx_is_i64 = res, n_pairs, k, k + 1, cap, 1 if idx64 else 0
-        _lib.check(L.cppf_frame_cloud_dyn_batch(len(spec), C.cast(arr, C.c_void_p), dd.data_ptr(), 0 if depth_float else 1, ld.data_ptr(),
-                                                label_bytes, H, W, kinv.ctypes.data, 1000.0, stream_ptr(dev)), "cppf_frame_cloud_dyn_batch")
+        # the expected values: the host's mask of the member's bit, the eager path
+        want = [_eager_frame_cloud(dd, ((labels >> ldt(j)) & ldt(1)).astype(np.uint8), res, k, k + 1, cap) for j, (cap, res, k) in enumerate(spec)]
+        arr = _frame_cloud_batch(L, dev, many, spec, dd, u16, ld, label_bytes, H, W, kinv, n_pairs, 1 if idx64 else 0)
+        for j, b in one.items():
+            _frame_cloud_single(L, dev, b, spec[j], dd, u16, ld, label_bytes, H, W, kinv, bit=1 if j == 1 else None)
     torch.cuda.synchronize()
     counts = []
-    for j, (a, b) in enumerate(zip(one, many)):
-        n = int(a["shape"][0])
-        counts.append(n)
-        assert torch.equal(a["shape"], b["shape"]) and torch.equal(a["corner"], b["corner"]), j
-        # (whole buffers, pre-filled alike: what either form leaves untouched beyond the cloud is part of the comparison)
-        assert torch.equal(a["pc"], b["pc"]) and torch.equal(a["nrm"], b["nrm"]) and torch.equal(a["nbrs"], b["nbrs"]), j
-        assert torch.all(b["nrm"][n:] == -7) and torch.all(b["nbrs"][n:] == -7)
-        if idx64:
-            assert torch.equal(a["idx"], b["idx"]) and torch.equal(a["u_tr"], b["u_tr"]) and torch.equal(a["u_rot"], b["u_rot"]), j
-        else:        # the single sampler draws int64 lists: the same numbers, from the Philox twin on the host
-            import cppf_amd.synthetic as syn
-            idx_w, utr_w, urot_w = syn.philox_pairs(1000003 * 7 + j, n_pairs, n)
-            assert np.array_equal(b["idx"].cpu().numpy(), idx_w.astype(np.int32)), j
-            assert np.array_equal(b["u_tr"].cpu().numpy(), utr_w) and np.array_equal(b["u_rot"].cpu().numpy(), urot_w), j
+    for j, (b, e) in enumerate(zip(many, want)):
+        counts.append(int(b["shape"][0]))
+        _assert_frame_cloud(b, e, ("batch", j))
+        if j in one:
+            _assert_frame_cloud(one[j], e, ("single", j))
+        idx_w, utr_w, urot_w = syn.philox_pairs(1000003 * 7 + j, n_pairs, e["n"])         # the Philox twin on the host
+        assert np.array_equal(b["idx"].cpu().numpy(), idx_w if idx64 else idx_w.astype(np.int32)), j
+        assert np.array_equal(b["u_tr"].cpu().numpy(), utr_w) and np.array_equal(b["u_rot"].cpu().numpy(), urot_w), j
     assert counts[3] == 0 and counts[4] == 0 and counts[1] > 2000 and counts[0] > 100, counts      # (member 4: fewer points than k_min)
+    assert want[3]["n_raw"] == 0 and 0 < want[4]["n_raw"] < 61
     # argument checks
     assert L.cppf_frame_cloud_dyn_batch(0, C.cast(arr, C.c_void_p), dd.data_ptr(), 1, ld.data_ptr(), 4, H, W, kinv.ctypes.data, 1000.0, None) == -1
     assert L.cppf_frame_cloud_dyn_batch(9, C.cast(arr, C.c_void_p), dd.data_ptr(), 1, ld.data_ptr(), 4, H, W, kinv.ctypes.data, 1000.0, None) == -1
     assert L.cppf_frame_cloud_dyn_batch(1, C.cast(arr, C.c_void_p), dd.data_ptr(), 1, ld.data_ptr(), 3, H, W, kinv.ctypes.data, 1000.0, None) == -1
     arr[0].workspace_bytes = 16
     assert L.cppf_frame_cloud_dyn_batch(1, C.cast(arr, C.c_void_p), dd.data_ptr(), 1, ld.data_ptr(), 4, H, W, kinv.ctypes.data, 1000.0, None) == -2
+
+
+def _synthetic_frame(H, W):
+    """u16 depth of a smooth surface ~0.7 m away (millimetres) with a few holes; pixel 1024 is never one"""
+    r, c = np.mgrid[0:H, 0:W].astype(np.float64)
+    depth = np.round(700 + 40 * np.sin(0.37 * r) + 30 * np.cos(0.23 * c) + 0.8 * r + 0.5 * c).astype(np.uint16)
+    depth.reshape(-1)[[3, 77, 500, 1000, 1023]] = 0
+    return depth
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("H,W", [(25, 41), (32, 64)])
+def test_frame_cloud_chunk_edges_and_capacity_clamps(dev, H, W):
+    """The frame stage at the edges of its 1 024-pixel compaction chunks and of its capacities: a frame of 1 025 pixels (the second
+    chunk holds one) and one of 2 048 (exactly two); a mask of all ones, one whose only pixel is pixel 1024 (fewer points than
+    k_min), an empty one; capacities 300 (below the full mask's valid pixels: the first 300 are the cloud) and 1 100 (neither a
+    multiple of 256 or 1 024).  The batch of three and cppf_frame_cloud_dyn_bit member by member against the eager path, and
+    against each other."""
+    import torch
+    from cppf_amd import _lib
+    from cppf_amd.frames import NOCS_INTRINSICS
+    L = _lib.lib()
+    depth = _synthetic_frame(H, W)
+    assert int((depth > 0).sum()) == H * W - 5 and depth.reshape(-1)[1024] > 0
+    full, single = np.ones((H, W), np.uint8), np.zeros((H, W), np.uint8)
+    single.reshape(-1)[1024] = 1
+    masks = [full, single, np.zeros((H, W), np.uint8)]
+    labels = np.zeros((H, W), np.uint8)
+    for i, m in enumerate(masks):
+        labels |= m << np.uint8(i)
+    dd, ld = torch.from_numpy(depth.view(np.int16)).to(dev), torch.from_numpy(labels).to(dev)
+    kinv = np.ascontiguousarray(np.linalg.inv(NOCS_INTRINSICS))
+    k, res = 4, 0.003
+    with torch.cuda.device(dev):
+        for cap in (300, 1100):
+            spec = [(cap, res, k)] * 3
+            many, one = ([_frame_cloud_buffers(L, dev, H, W, cap, k) for _ in spec] for _ in range(2))
+            for j, b in list(enumerate(many)) + list(enumerate(one)):
+                b["slot"].copy_(torch.tensor([j, 0], dtype=torch.int64))
+            want = [_eager_frame_cloud(dd, m, res, k, k + 1, cap) for m in masks]
+            assert [e["n_valid"] for e in want] == [H * W - 5, 1, 0] and want[0]["n_valid"] > 300
+            assert want[0]["n"] >= k + 1 and want[1]["n_raw"] == 1 and want[1]["n"] == 0 and want[2]["n_raw"] == 0
+            _frame_cloud_batch(L, dev, many, spec, dd, 1, ld, 1, H, W, kinv)
+            for b in one:
+                _frame_cloud_single(L, dev, b, spec[0], dd, 1, ld, 1, H, W, kinv)
+            torch.cuda.synchronize()
+            for j, (a, b, e) in enumerate(zip(one, many, want)):
+                _assert_frame_cloud(a, e, ("single", cap, j))
+                _assert_frame_cloud(b, e, ("batch", cap, j))
+                assert all(torch.equal(a[n], b[n]) for n in ("pc", "nrm", "nbrs", "corner", "shape")), (cap, j)
