@@ -1,9 +1,17 @@
 """NOCS evaluation of pose predictions: 3D-IoU AP and degree / centimetre AP over the
 result dictionaries `nocs/inference.py:338-345` pickles (see cppf_amd.inference.nocs_result for this package's side).
 
-Host-side numpy, like the reference's (`utils/util.py:181-255,342-527,709-1008`, driven by `nocs/eval.py:16-49`): this is
-offline metric code, there is nothing here for the GPU.  Same entry points, arguments, return values and matching rules;
-the implementation is this repository's own:
+Two paths with the same entry points, arguments, return values and matching rules as the reference (`utils/util.py:181-255,
+342-527,709-1008`, driven by `nocs/eval.py:16-49`):
+
+* the host path (device=None) is numpy, like the reference's, and is the checker of the other one;
+* the device path (device=a HIP device) flattens the whole result list once into (image, class) groups and work pairs, uploads
+  it once, runs the box IoUs with their 20-rotation symmetry sweep, the degree / centimetre errors and both greedy matchings
+  in three launches (csrc/pose_eval.hip, include/cppf.h "Pose evaluation") and reads the match tables back once; the AP sums
+  stay on the host.  At a pose every 0.2 ms the host metric (about 1.3 ms per box pair with the sweep) is the slow end of a
+  REAL275-sized run; pose_metrics_device gives a training loop the per-pair figures without leaving the device.
+
+The implementation is this repository's own:
 
 * the intersection volume of two oriented boxes is computed with the divergence theorem over the clipped faces of
   both boxes (each face of one box clipped by the six half-spaces of the other), not by collecting intersection points
@@ -249,12 +257,28 @@ def _unit_scale(RTs, scales, eps):
     return RTs, scales * s[:, None]
 
 
+def _write_tables(log_dir, iou_list, deg_list, sh_list, iou_3d_aps, pose_aps, use_matches_for_pose):
+    """the two tables the reference pickles next to its figures"""
+    os.makedirs(log_dir, exist_ok=True)
+    with open(os.path.join(log_dir, "IoU_3D_AP_{}-{}.pkl".format(iou_list[0], iou_list[-1])), "wb") as f:
+        pickle.dump({"thres_list": iou_list, "aps": iou_3d_aps}, f)
+    prefix = "Pose_Only_" if use_matches_for_pose else "Pose_Detection_"
+    name = prefix + "AP_{}-{}degree_{}-{}cm.pkl".format(deg_list[0], deg_list[-2], sh_list[0], sh_list[-2])
+    with open(os.path.join(log_dir, name), "wb") as f:
+        pickle.dump({"degree_thres": deg_list, "shift_thres_list": sh_list, "aps": pose_aps}, f)
+
+
 def compute_degree_cm_mAP(final_results, synset_names, log_dir, degree_thresholds=[360], shift_thresholds=[100],
-                          iou_3d_thresholds=[0.1], iou_pose_thres=0.1, use_matches_for_pose=False):
+                          iou_3d_thresholds=[0.1], iou_pose_thres=0.1, use_matches_for_pose=False, device=None):
     """utils/util.py:709-1008 (called by nocs/eval.py:44-49).  final_results: one dict per image with gt_class_ids,
     gt_RTs, gt_scales, gt_up_syms, pred_class_ids, pred_RTs, pred_scales, pred_scores (pred_bboxes is ignored, as there).
     Returns (iou_3d_aps [C+1, T], pose_aps [C+1, D+1, S+1], pose_pred_matches, pose_gt_matches [D+1, S+1, images, 20]);
-    row C of the AP tables is the mean over the classes, the extra threshold is 360 degrees / 100 cm."""
+    row C of the AP tables is the mean over the classes, the extra threshold is 360 degrees / 100 cm.
+    device: None = the host path; a HIP device = IoUs, errors and matchings on that device (same return values; see
+    _map_on_device for what it checks first)."""
+    if device is not None:
+        return _map_on_device(final_results, synset_names, log_dir, degree_thresholds, shift_thresholds, iou_3d_thresholds,
+                              iou_pose_thres, use_matches_for_pose, device)
     n_cls = len(synset_names)
     deg_list = list(degree_thresholds) + [360]
     sh_list = list(shift_thresholds) + [100]
@@ -320,14 +344,271 @@ def compute_degree_cm_mAP(final_results, synset_names, log_dir, degree_threshold
                 pose_aps[c, d, s] = compute_ap_from_matches_scores(pose_pm[c][d, s], pose_ps[c][d, s], pose_gm[c][d, s])
     iou_3d_aps[-1] = iou_3d_aps[1:-1].mean(0)
     pose_aps[-1] = pose_aps[1:-1].mean(0)
-    if log_dir:                                             # the two tables the reference pickles next to its figures
-        os.makedirs(log_dir, exist_ok=True)
-        with open(os.path.join(log_dir, "IoU_3D_AP_{}-{}.pkl".format(iou_list[0], iou_list[-1])), "wb") as f:
-            pickle.dump({"thres_list": iou_list, "aps": iou_3d_aps}, f)
-        prefix = "Pose_Only_" if use_matches_for_pose else "Pose_Detection_"
-        name = prefix + "AP_{}-{}degree_{}-{}cm.pkl".format(deg_list[0], deg_list[-2], sh_list[0], sh_list[-2])
-        with open(os.path.join(log_dir, name), "wb") as f:
-            pickle.dump({"degree_thres": deg_list, "shift_thres_list": sh_list, "aps": pose_aps}, f)
+    if log_dir:
+        _write_tables(log_dir, iou_list, deg_list, sh_list, iou_3d_aps, pose_aps, use_matches_for_pose)
+    return iou_3d_aps, pose_aps, pose_pred_matches, pose_gt_matches
+
+
+# ------------------------------------------------------------------------------------------------ the device path
+GROUP_CAP = 32      # predictions / ground truths of one (image, class) group: include/cppf.h CPPF_POSE_EVAL_GROUP_CAP
+
+
+def _device_tensor(x, np_dtype, device, tail, name):
+    """a numpy array or a tensor -> a contiguous tensor of that dtype on `device` with the trailing shape `tail`"""
+    import torch
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np_dtype))
+    x = x.to(device=device, dtype=getattr(torch, np.dtype(np_dtype).name)).contiguous()
+    if tuple(x.shape[1:]) != tuple(tail) or x.dim() != 1 + len(tail):
+        raise ValueError(f"{name}: expected shape [n{''.join(', %d' % t for t in tail)}], got {tuple(x.shape)}")
+    return x
+
+
+def _pairs_on_device(dev, pred_RTs, pred_scales, gt_RTs, gt_scales, gt_up_syms, pairs, sweep):
+    """cppf_pose_eval_pairs on device tensors: (iou f64[M], err f64[M,2])"""
+    import torch
+    from . import _lib
+    from ._torch_util import call, scratch, workspace
+    M = int(pairs.shape[0])
+    iou = torch.empty(M, dtype=torch.float64, device=dev)
+    err = torch.empty((M, 2), dtype=torch.float64, device=dev)
+    if M:
+        need = _lib.lib().cppf_pose_eval_pairs_workspace_bytes(M)
+        if need == 0:
+            raise ValueError(f"{M} work pairs: more than one call takes")
+        ws = workspace(need, dev, "pose_eval")
+        call("cppf_pose_eval_pairs", dev, pred_RTs, pred_scales, int(pred_RTs.shape[0]), gt_RTs, gt_scales, gt_up_syms,
+             int(gt_RTs.shape[0]), pairs, sweep, M, iou, err, scratch(ws))
+    return iou, err
+
+
+def pose_metrics_device(pred_RTs, pred_scales, gt_RTs, gt_scales, gt_up_syms, pairs, sweep, device=None):
+    """Box IoU, rotation error (degrees) and translation error (centimetres) of M (prediction, ground truth) pairs on the device,
+    e.g. as a validation metric inside a training loop: no host synchronisation when the arguments are device tensors.
+
+    pred_RTs [Np,4,4], pred_scales [Np,3], gt_RTs [Ng,4,4], gt_scales [Ng,3], gt_up_syms [Ng], pairs [M,2] = (prediction index,
+    ground-truth index), sweep [M] (non-zero: this pair's IoU is the best of the 20 rotations of the prediction about its y axis,
+    what compute_3d_iou does for an up-symmetric ground truth of the same class); numpy arrays or tensors.  The RTs are used as
+    given (compute_3d_iou / compute_RT_degree_cm_symmetry of the same arguments; compute_degree_cm_mAP passes them through
+    _unit_scale first).  Returns device tensors (iou f64[M], degrees f64[M], centimetres f64[M]).  A pair index outside the arrays
+    raises ValueError when `pairs` is a host array and gives NaN in all three when it is a device tensor."""
+    import torch
+    from ._torch_util import require_cuda
+    require_cuda()
+    if device is None:
+        on_dev = [x.device for x in (pred_RTs, pred_scales, gt_RTs, gt_scales, gt_up_syms, pairs, sweep)
+                  if isinstance(x, torch.Tensor) and x.is_cuda]
+        device = on_dev[0] if on_dev else torch.device("cuda", 0)
+    dev = torch.device(device)
+    if not isinstance(pairs, torch.Tensor):
+        pr = np.asarray(pairs).reshape(-1, 2)
+        n_p, n_g = len(pred_RTs), len(gt_RTs)
+        if len(pr) and (pr.min() < 0 or pr[:, 0].max() >= n_p or pr[:, 1].max() >= n_g):
+            raise ValueError(f"pairs: an index outside {n_p} predictions x {n_g} ground truths")
+        pairs = pr
+    a = _device_tensor(pred_RTs, np.float64, dev, (4, 4), "pred_RTs")
+    b = _device_tensor(pred_scales, np.float64, dev, (3,), "pred_scales")
+    c = _device_tensor(gt_RTs, np.float64, dev, (4, 4), "gt_RTs")
+    d = _device_tensor(gt_scales, np.float64, dev, (3,), "gt_scales")
+    e = _device_tensor(gt_up_syms, np.int32, dev, (), "gt_up_syms")
+    f = _device_tensor(pairs, np.int32, dev, (2,), "pairs")
+    g = _device_tensor(sweep, np.int32, dev, (), "sweep")
+    if a.shape[0] != b.shape[0] or c.shape[0] != d.shape[0] or c.shape[0] != e.shape[0] or f.shape[0] != g.shape[0]:
+        raise ValueError("pose_metrics_device: one scale row per RT, one symmetry flag per ground truth, one sweep flag per pair")
+    iou, err = _pairs_on_device(dev, a, b, c, d, e, f, g)
+    return iou, err[:, 0], err[:, 1]
+
+
+def _check_poses(RTs, scales, img, what):
+    """what the device path refuses before anything is uploaded: non-finite values, a singular rotation block, a last row other
+    than [0 0 0 1] (the host path divides by the determinant and raises on the last row, pair by pair)"""
+    RTs = np.asarray(RTs, dtype=np.float64).reshape(-1, 4, 4)
+    scales = np.asarray(scales, dtype=np.float64).reshape(-1, 3)
+    if len(RTs) != len(scales):
+        raise ValueError(f"image {img}: {len(RTs)} {what} poses and {len(scales)} scales")
+    if len(RTs) == 0:
+        return
+    bad = ~(np.isfinite(RTs).all((1, 2)) & np.isfinite(scales).all(1))
+    if bad.any():
+        raise ValueError(f"image {img}, {what} instance {int(np.argmax(bad))}: non-finite pose or scale")
+    bad = (RTs[:, 3] != np.array([0.0, 0.0, 0.0, 1.0])).any(1)
+    if bad.any():
+        k = int(np.argmax(bad))
+        raise ValueError(f"image {img}, {what} instance {k}: homogeneous row {RTs[k, 3]} differs from [0 0 0 1]")
+    det = np.linalg.det(RTs[:, :3, :3])
+    # zero to rounding: |det| <= 1e-12 * the product of the column norms (a scaled rotation has the ratio 1)
+    with np.errstate(divide="ignore", over="ignore", invalid="ignore"):
+        bad = ~(np.abs(det) > 1e-12 * np.linalg.norm(RTs[:, :3, :3], axis=1).prod(1)) | ~np.isfinite(1.0 / det)
+    if bad.any():
+        k = int(np.argmax(bad))
+        raise ValueError(f"image {img}, {what} instance {k}: singular rotation block (determinant {det[k]})")
+
+
+def _iou_threshold_as_compared(thr):
+    """the value the host's `overlaps[i, j] < thr` compares a float32 IoU with: numpy's promotion of (float32 scalar, thr) decides
+    whether thr is rounded to float32 first (a Python float under NEP 50) or the IoU is widened (a float64 scalar)"""
+    return float(np.asarray(thr).astype(np.result_type(np.float32(0), thr)))
+
+
+def _flatten_results(final_results, n_cls):
+    """the result list as (image, class) groups: every array compute_degree_cm_mAP's loop would select, concatenated in group
+    order, predictions in each group in the host's descending-score order.  Groups with neither predictions nor ground truths
+    are left out (they add nothing to any table)."""
+    acc = dict(pred_RT=[], pred_sc=[], pred_score=[], pred_img=[], pred_inst=[], pred_cls=[], pred_g0=[],
+               gt_RT=[], gt_sc=[], gt_sym=[], gt_img=[], gt_inst=[], gt_cls=[], gt_p0=[], pairs=[], sweep=[])
+    pred_off, gt_off, pair_off = [0], [0], []
+    n_pairs = 0
+    for img, res in enumerate(final_results):
+        gt_cls = np.asarray(res["gt_class_ids"]).astype(np.int32)
+        _check_poses(res["gt_RTs"], res["gt_scales"], img, "ground-truth")
+        _check_poses(res["pred_RTs"], res["pred_scales"], img, "predicted")
+        gt_RTs, gt_scales = _unit_scale(res["gt_RTs"], res["gt_scales"], 0.0)
+        gt_sym = np.asarray(res["gt_up_syms"])
+        pr_cls = np.asarray(res["pred_class_ids"])
+        pr_scores = np.asarray(res["pred_scores"])
+        pr_RTs, pr_scales = _unit_scale(res["pred_RTs"], res["pred_scales"], 1e-9)
+        if len(gt_cls) == 0 and len(pr_cls) == 0:
+            continue
+        if len(gt_sym) != len(gt_cls) or len(gt_RTs) != len(gt_cls) or len(pr_RTs) != len(pr_cls) or len(pr_scores) != len(pr_cls):
+            raise ValueError(f"image {img}: one class id, pose, scale (and score / symmetry flag) per instance")
+        for c in range(1, n_cls):
+            g_sel = np.where(gt_cls == c)[0] if len(gt_cls) else np.zeros(0, dtype=int)
+            p_sel = np.where(pr_cls == c)[0] if len(pr_cls) else np.zeros(0, dtype=int)
+            n_p, n_g = len(p_sel), len(g_sel)
+            if n_p == 0 and n_g == 0:
+                continue
+            if n_p > GROUP_CAP or n_g > GROUP_CAP:
+                raise ValueError(f"image {img}, class {c}: {n_p} predictions and {n_g} ground truths; the device path takes "
+                                 f"at most {GROUP_CAP} of each per image and class (device=None has no cap)")
+            if n_p:
+                p_sel = p_sel[np.argsort(pr_scores[p_sel])[::-1]]         # compute_3d_matches' order, ties included
+            p0, g0 = pred_off[-1], gt_off[-1]
+            acc["pred_RT"].append(pr_RTs[p_sel]); acc["pred_sc"].append(pr_scales[p_sel]); acc["pred_score"].append(pr_scores[p_sel])
+            acc["pred_img"].append(np.full(n_p, img)); acc["pred_inst"].append(p_sel); acc["pred_cls"].append(np.full(n_p, c))
+            acc["pred_g0"].append(np.full(n_p, g0))
+            acc["gt_RT"].append(gt_RTs[g_sel]); acc["gt_sc"].append(gt_scales[g_sel]); acc["gt_sym"].append(gt_sym[g_sel] != 0)
+            acc["gt_img"].append(np.full(n_g, img)); acc["gt_inst"].append(g_sel); acc["gt_cls"].append(np.full(n_g, c))
+            acc["gt_p0"].append(np.full(n_g, p0))
+            if n_p and n_g:
+                gi = np.tile(np.arange(n_g), n_p)
+                acc["pairs"].append(np.stack([p0 + np.repeat(np.arange(n_p), n_g), g0 + gi], -1))
+                acc["sweep"].append((gt_sym[g_sel] != 0)[gi])
+            pair_off.append(n_pairs)
+            n_pairs += n_p * n_g
+            pred_off.append(p0 + n_p)
+            gt_off.append(g0 + n_g)
+
+    def cat(key, dtype, tail):
+        parts = acc[key]
+        return (np.concatenate(parts) if parts else np.zeros((0,) + tail)).astype(dtype).reshape((-1,) + tail)
+
+    flat = dict(pred_RT=cat("pred_RT", np.float64, (4, 4)), pred_sc=cat("pred_sc", np.float64, (3,)),
+                pred_score=cat("pred_score", np.float64, ()),
+                gt_RT=cat("gt_RT", np.float64, (4, 4)), gt_sc=cat("gt_sc", np.float64, (3,)), gt_sym=cat("gt_sym", np.int32, ()),
+                pairs=cat("pairs", np.int32, (2,)), sweep=cat("sweep", np.int32, ()),
+                pred_off=np.asarray(pred_off, np.int32), gt_off=np.asarray(gt_off, np.int32), pair_off=np.asarray(pair_off, np.int64))
+    for key in ("pred_img", "pred_inst", "pred_cls", "pred_g0", "gt_img", "gt_inst", "gt_cls", "gt_p0"):
+        flat[key] = cat(key, np.int64, ())
+    return flat
+
+
+def _match_tables_on_device(flat, iou_cmp, deg_list, sh_list, keep_row, dev):
+    """one upload, cppf_pose_eval_pairs / _match_iou / _match_pose, one read-back: (iou_pm [T,P], iou_gm [T,G], pose_pm [D,S,P],
+    pose_gm [D,S,G]) int32 with group-local indices; keep_row: the IoU threshold row whose matches select the instances scored
+    for pose (read by the third kernel where the second wrote it), or None"""
+    import torch
+    from ._torch_util import call, require_cuda
+    require_cuda()
+    P, G, M, n_groups = len(flat["pred_RT"]), len(flat["gt_RT"]), len(flat["pairs"]), len(flat["pair_off"])
+    nT, nD, nS = len(iou_cmp), len(deg_list), len(sh_list)
+    parts = [("pred_RT", flat["pred_RT"]), ("pred_sc", flat["pred_sc"]), ("gt_RT", flat["gt_RT"]), ("gt_sc", flat["gt_sc"]),
+             ("iou_thr", np.asarray(iou_cmp, np.float64)), ("deg_thr", np.asarray(deg_list, np.float64)),
+             ("sh_thr", np.asarray(sh_list, np.float64)), ("pair_off", flat["pair_off"]), ("gt_sym", flat["gt_sym"]),
+             ("pairs", flat["pairs"]), ("sweep", flat["sweep"]), ("pred_off", flat["pred_off"]), ("gt_off", flat["gt_off"])]
+    chunks, where, pos = [], {}, 0
+    for name, arr in parts:                                  # one byte buffer, every section 8-byte aligned
+        raw = np.ascontiguousarray(arr).reshape(-1).view(np.uint8)
+        pad = (-len(raw)) % 8
+        where[name] = (pos, len(raw), arr.dtype, arr.shape)
+        chunks += [raw, np.zeros(pad, np.uint8)]
+        pos += len(raw) + pad
+    buf = torch.from_numpy(np.concatenate(chunks)).to(dev)   # the one upload
+
+    def sec(name):
+        o, n, dt, shape = where[name]
+        return buf[o:o + n].view(getattr(torch, np.dtype(dt).name)).reshape(shape)
+
+    tables = torch.empty((nT + nD * nS) * (P + G), dtype=torch.int32, device=dev)
+    iou_pm, iou_gm = tables[:nT * P].view(nT, P), tables[nT * P:nT * (P + G)].view(nT, G)
+    rest = tables[nT * (P + G):]
+    pose_pm, pose_gm = rest[:nD * nS * P].view(nD, nS, P), rest[nD * nS * P:].view(nD, nS, G)
+    if n_groups:
+        iou, err = _pairs_on_device(dev, sec("pred_RT"), sec("pred_sc"), sec("gt_RT"), sec("gt_sc"), sec("gt_sym"), sec("pairs"),
+                                    sec("sweep"))
+        nul = lambda t_: t_ if t_.numel() else None
+        call("cppf_pose_eval_match_iou", dev, nul(iou), sec("pred_off"), sec("gt_off"), sec("pair_off"), n_groups, sec("iou_thr"), nT,
+             P, G, M, nul(iou_pm), nul(iou_gm))
+        keep_p = nul(iou_pm[keep_row]) if keep_row is not None else None
+        keep_g = nul(iou_gm[keep_row]) if keep_row is not None else None
+        call("cppf_pose_eval_match_pose", dev, nul(err), sec("pred_off"), sec("gt_off"), sec("pair_off"), n_groups, sec("deg_thr"), nD,
+             sec("sh_thr"), nS, keep_p, keep_g, P, G, M, nul(pose_pm), nul(pose_gm))
+    host = tables.cpu().numpy()                              # the one read-back
+    a, b = nT * P, nT * (P + G)
+    c = b + nD * nS * P
+    return host[:a].reshape(nT, P), host[a:b].reshape(nT, G), host[b:c].reshape(nD, nS, P), host[c:].reshape(nD, nS, G)
+
+
+def _map_on_device(final_results, synset_names, log_dir, degree_thresholds, shift_thresholds, iou_3d_thresholds, iou_pose_thres,
+                   use_matches_for_pose, device):
+    """compute_degree_cm_mAP with the per-pair work and the matchings on `device`.  Differences from the host path, all refusals:
+    a pose or scale that is not finite, a singular rotation block or a last row other than [0 0 0 1] raises ValueError naming the
+    image and the instance before anything is uploaded, and so does an (image, class) group of more than GROUP_CAP predictions or
+    ground truths.  Among ground truths of EQUAL IoU (or equal degree + cm sum) the device takes the higher (lower) index
+    (include/cppf.h); the host's choice there is np.argsort's."""
+    import torch
+    n_cls = len(synset_names)
+    deg_list = list(degree_thresholds) + [360]
+    sh_list = list(shift_thresholds) + [100]
+    iou_list = list(iou_3d_thresholds)
+    nD, nS, nT = len(deg_list), len(sh_list), len(iou_list)
+    if use_matches_for_pose and iou_pose_thres not in iou_list:
+        raise ValueError("iou_pose_thres must be one of iou_3d_thresholds")
+    keep_row = iou_list.index(iou_pose_thres) if use_matches_for_pose else None
+    flat = _flatten_results(final_results, n_cls)
+    iou_pm, iou_gm, pose_pm, pose_gm = _match_tables_on_device(
+        flat, [_iou_threshold_as_compared(t) for t in iou_list], [float(d) for d in deg_list], [float(s) for s in sh_list], keep_row,
+        torch.device(device))
+
+    P, G = len(flat["pred_RT"]), len(flat["gt_RT"])
+    keep_p = iou_pm[keep_row] > -1 if use_matches_for_pose else np.ones(P, bool)
+    keep_g = iou_gm[keep_row] > -1 if use_matches_for_pose else np.ones(G, bool)
+    # per-image tables in the image's own instance numbering
+    pose_gt_matches = np.full((nD, nS, len(final_results), 20), -1, dtype=int)
+    pose_pred_matches = np.full((nD, nS, len(final_results), 20), -1, dtype=int)
+    if P:
+        m = pose_pm[:, :, keep_p].astype(np.int64)
+        to = flat["gt_inst"][np.clip(flat["pred_g0"][keep_p][None, None] + np.maximum(m, 0), 0, max(G - 1, 0))] if G else m
+        pose_pred_matches[:, :, flat["pred_img"][keep_p], flat["pred_inst"][keep_p]] = np.where(m >= 0, to, -1)
+    if G:
+        m = pose_gm[:, :, keep_g].astype(np.int64)
+        to = flat["pred_inst"][np.clip(flat["gt_p0"][keep_g][None, None] + np.maximum(m, 0), 0, max(P - 1, 0))] if P else m
+        pose_gt_matches[:, :, flat["gt_img"][keep_g], flat["gt_inst"][keep_g]] = np.where(m >= 0, to, -1)
+
+    iou_3d_aps = np.zeros((n_cls + 1, nT))
+    pose_aps = np.zeros((n_cls + 1, nD, nS))
+    scores = flat["pred_score"]
+    for c in range(1, n_cls):
+        pc, gc = flat["pred_cls"] == c, flat["gt_cls"] == c
+        for s in range(nT):
+            iou_3d_aps[c, s] = compute_ap_from_matches_scores(iou_pm[s][pc], scores[pc], iou_gm[s][gc])
+        pk, gk = pc & keep_p, gc & keep_g
+        for d in range(nD):
+            for s in range(nS):
+                pose_aps[c, d, s] = compute_ap_from_matches_scores(pose_pm[d, s][pk], scores[pk], pose_gm[d, s][gk])
+    iou_3d_aps[-1] = iou_3d_aps[1:-1].mean(0)
+    pose_aps[-1] = pose_aps[1:-1].mean(0)
+    if log_dir:
+        _write_tables(log_dir, iou_list, deg_list, sh_list, iou_3d_aps, pose_aps, use_matches_for_pose)
     return iou_3d_aps, pose_aps, pose_pred_matches, pose_gt_matches
 
 
@@ -351,9 +632,10 @@ def mark_up_symmetry(result, synset_names=SYNSET_NAMES):
     return result
 
 
-def evaluate_prediction_dir(pred_dir, stride=10, synset_names=SYNSET_NAMES):
+def evaluate_prediction_dir(pred_dir, stride=10, synset_names=SYNSET_NAMES, device=None):
     """nocs/eval.py:16-49: every `stride`-th results_*.pkl of a prediction directory -> the four arrays of
-    compute_degree_cm_mAP with the thresholds the paper reports (5/10/15 degrees, 5/10/15 cm, IoU 0..1 in steps of 0.01)."""
+    compute_degree_cm_mAP with the thresholds the paper reports (5/10/15 degrees, 5/10/15 cm, IoU 0..1 in steps of 0.01);
+    `device` as there."""
     import glob
     files = sorted(glob.glob(os.path.join(pred_dir, "results_*.pkl")))[::stride]
     if not files:
@@ -366,4 +648,4 @@ def evaluate_prediction_dir(pred_dir, stride=10, synset_names=SYNSET_NAMES):
             results.append(mark_up_symmetry(one, synset_names))
     return compute_degree_cm_mAP(results, synset_names, pred_dir + "_map", degree_thresholds=[5, 10, 15],
                                  shift_thresholds=[5, 10, 15], iou_3d_thresholds=np.linspace(0, 1, 101), iou_pose_thres=0.1,
-                                 use_matches_for_pose=True)
+                                 use_matches_for_pose=True, device=device)

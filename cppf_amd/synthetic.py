@@ -242,3 +242,54 @@ def philox_pairs(seed, n_pairs, n_points):
     idx = np.stack([(a[0] * N) >> s32, (a[1] * N) >> s32], -1).astype(np.int64)
     u = lambda w: ((w >> np.uint64(8)).astype(np.float32) * np.float32(2.0 ** -24))
     return idx, np.stack([u(a[2]), u(a[3])], -1), np.stack([u(b[0]), u(b[1])], -1)
+
+
+# ---------------------------------------------------------------------------------------------------------- evaluation results
+def _small_rotation(rng, max_deg):
+    """a turn by at most max_deg about a random axis"""
+    ax = rng.standard_normal(3)
+    ax /= np.linalg.norm(ax)
+    th = np.deg2rad(rng.uniform(0.0, max_deg))
+    K = np.array([[0.0, -ax[2], ax[1]], [ax[2], 0.0, -ax[0]], [-ax[1], ax[0], 0.0]])
+    return np.eye(3) + np.sin(th) * K + (1.0 - np.cos(th)) * (K @ K)
+
+
+def make_eval_results(n_images, seed=0, max_instances=6):
+    """Seeded result dictionaries in the layout nocs/inference.py:338-345 pickles and cppf_amd.evaluation scores (before
+    mark_up_symmetry): per image 1..max_instances ground truths of the six NOCS classes with the object's size inside the RT, and
+    predictions that are perturbed copies (up to 20 degrees, about 3 cm per axis, 15 % in size) -- one in five missing, one in ten
+    with another class, and now and then a detection of nothing."""
+    rng = np.random.default_rng(seed)
+
+    def rt(R, t, s):
+        M = np.eye(4)
+        M[:3, :3] = R * s
+        M[:3, 3] = t
+        return M
+
+    out = []
+    for _ in range(n_images):
+        n = int(rng.integers(1, max_instances + 1))
+        cls = rng.integers(1, 7, n).astype(np.int32)
+        gt_RTs = np.stack([rt(random_rotation(rng), rng.uniform(-0.5, 0.5, 3) + [0.0, 0.0, 1.0], rng.uniform(0.15, 0.5)) for _ in range(n)])
+        gt_scales = rng.uniform(0.3, 1.0, (n, 3))
+        vis = np.where((cls == 6) & (rng.random(n) < 0.5), 0, 1).astype(np.int32)
+        p_cls, p_RTs, p_scales = [], [], []
+        for k in range(n):
+            if rng.random() < 0.2:
+                continue
+            s = np.cbrt(np.linalg.det(gt_RTs[k, :3, :3]))
+            p_RTs.append(rt((gt_RTs[k, :3, :3] / s) @ _small_rotation(rng, 20.0), gt_RTs[k, :3, 3] + rng.normal(0, 0.03, 3),
+                            s * rng.uniform(0.9, 1.1)))
+            p_scales.append(gt_scales[k] * rng.uniform(0.85, 1.15, 3))
+            p_cls.append(cls[k] if rng.random() < 0.9 else rng.integers(1, 7))
+        if rng.random() < 0.3:
+            p_RTs.append(rt(random_rotation(rng), rng.uniform(-0.5, 0.5, 3) + [0.0, 0.0, 1.0], rng.uniform(0.15, 0.5)))
+            p_scales.append(rng.uniform(0.3, 1.0, 3))
+            p_cls.append(rng.integers(1, 7))
+        out.append(dict(gt_class_ids=cls, gt_RTs=gt_RTs, gt_scales=gt_scales, gt_handle_visibility=vis,
+                        pred_class_ids=np.array(p_cls, np.int32), pred_RTs=np.array(p_RTs, np.float64).reshape(-1, 4, 4).astype(np.float32),
+                        pred_scales=np.array(p_scales, np.float64).reshape(-1, 3).astype(np.float32),
+                        pred_scores=rng.uniform(0.3, 1.0, len(p_cls)).astype(np.float32),
+                        pred_bboxes=np.zeros((len(p_cls), 4), np.int32)))
+    return out

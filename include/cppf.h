@@ -934,6 +934,63 @@ int cppf_mesh_vote_stats_batch(const double* points, int n_meshes, int64_t n_poi
                                int64_t first_mesh, double* stats, int32_t* status, void* workspace, size_t workspace_bytes,
                                void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Pose evaluation (nocs/eval.py -> utils/util.py:181-255,342-416,470-517, csrc/pose_eval.hip): the per-pair box IoU and pose
+ * errors and the two greedy matchings of compute_degree_cm_mAP, for a whole result set in three launches with no host
+ * synchronisation.  The arithmetic is cppf_amd/evaluation.py's (its host path is the checker), in IEEE double without contraction.
+ *
+ * cppf_pose_eval_pairs: M work pairs (pairs device i32[M,2] = {prediction index, ground-truth index}).
+ *   pred_RT / gt_RT device f64[.,4,4] (row-major; the last row is not read), pred_scales / gt_scales device f64[.,3], gt_up_sym
+ *   device i32[n_gt], sweep device i32[M] (non-zero: the up-symmetry sweep applies to this pair's IoU -- the host sets it where the
+ *   classes agree and the ground truth is up-symmetric).  Outputs iou device f64[M], err device f64[M,2] = {degrees, centimetres}.
+ *   - A work item is (pair, rotation k): 20 for a swept pair (box 1 = RT_1 @ rot_y(2 pi k / 20), the cos / sin table the host's libm
+ *     gives), 1 otherwise; a swept pair's IoU is the maximum over k (taken with an integer max on the bits: exact in any order).
+ *   - Box of (RT, s): R = RT[:3,:3] / cbrt(det), axes = the normalised columns, half extents = 0.5 s * column norms, centre =
+ *     RT[:3,3] (_frame).  Intersection volume: 1/3 of the sum over the faces of box 1 clipped by box 2's six half-spaces and vice
+ *     versa of (n . x) * area (_faces, _clip, _flux, box_intersection_volume): a vertex is inside when n.x - d <= tol, tol = +1e-9 *
+ *     (largest half extent of both boxes) while box 1's faces are clipped and -tol for box 2's; a crossing's t is clamped to [0,1];
+ *     clipping of a face stops once fewer than 3 vertices are left.  IoU = v / (va + vb - v), and 0.0 when v <= 1e-9 min(va, vb)
+ *     (_iou_frames).  A clipped quad has at most 10 vertices.
+ *   - Errors (compute_RT_degree_cm_symmetry): with gt_up_sym the angle between the two y axes, else acos((trace(R1 R2^T) - 1) / 2),
+ *     the cosine clamped to [-1,1], in degrees; 100 * |t1 - t2|.
+ *   - A pair index outside [0, n_pred) x [0, n_gt) reads nothing and gives NaN in all three outputs.
+ *   M <= CPPF_POSE_EVAL_MAX_PAIRS; M = 0 is a no-op.  Workspace >= cppf_pose_eval_pairs_workspace_bytes(M) (the work-item offsets).
+ *
+ * Groups: one (image, class) with its predictions [pred_off[g], pred_off[g+1]) -- in the order they claim, i.e. descending score as
+ * the host sorts them -- and ground truths [gt_off[g], gt_off[g+1]) (device i32[G+1] each); its np x ng values (IoU, errors) are
+ * rows [pair_off[g], pair_off[g] + np ng) of the pair arrays, prediction-major (device i64[G]).  At most
+ * CPPF_POSE_EVAL_GROUP_CAP predictions and as many ground truths per group (the claimed set is one 32-bit mask; the reference's own
+ * per-image tables stop at 20): a larger group, or one whose rows leave [0, n_pairs), gets -1 everywhere -- callers refuse it first.
+ * Match tables are i32 with -1 = no match and hold indices LOCAL to the group; every entry of every group is written.
+ *
+ * cppf_pose_eval_match_iou (compute_3d_matches), one lane per (group, threshold): pred_match device i32[T, n_pred], gt_match
+ *   device i32[T, n_gt].  IoUs are rounded to float32 before any comparison (the host's overlaps are float32).  Each prediction in
+ *   turn takes the unclaimed ground truth with the largest IoU if that IoU is strictly above the threshold (the host's walk in
+ *   descending IoU skips claimed ones and stops below the threshold, so only this one can match).
+ *   TIE RULE: of several unclaimed ground truths with EQUAL float32 IoU the one with the HIGHER index is taken.  (The host's order
+ *   among equals is whatever np.argsort does on its platform; it is not reproduced.)
+ *
+ * cppf_pose_eval_match_pose (compute_match_from_degree_cm), one lane per (group, degree threshold, shift threshold): pred_match
+ *   device i32[D, S, n_pred], gt_match device i32[D, S, n_gt].  Each kept prediction in turn takes the unclaimed kept ground truth
+ *   with the smallest degrees + centimetres among those with degrees <= threshold and centimetres <= threshold.
+ *   TIE RULE: of several with EQUAL sum the one with the LOWER index is taken.
+ *   keep_pred device i32[n_pred] / keep_gt device i32[n_gt]: an instance takes part when its entry is >= 0 -- one row of
+ *   cppf_pose_eval_match_iou's tables, used where it lies (use_matches_for_pose); NULL: every prediction / ground truth takes part.
+ * ------------------------------------------------------------------------------------------- */
+#define CPPF_POSE_EVAL_GROUP_CAP 32
+#define CPPF_POSE_EVAL_MAX_PAIRS 100000000
+size_t cppf_pose_eval_pairs_workspace_bytes(int64_t n_pairs);
+int cppf_pose_eval_pairs(const double* pred_RT, const double* pred_scales, int64_t n_pred, const double* gt_RT,
+                         const double* gt_scales, const int32_t* gt_up_sym, int64_t n_gt, const int32_t* pairs, const int32_t* sweep,
+                         int64_t n_pairs, double* iou, double* err, void* workspace, size_t workspace_bytes, void* stream);
+int cppf_pose_eval_match_iou(const double* iou, const int32_t* pred_off, const int32_t* gt_off, const int64_t* pair_off, int n_groups,
+                             const double* thresholds, int n_thresholds, int64_t n_pred, int64_t n_gt, int64_t n_pairs,
+                             int32_t* pred_match, int32_t* gt_match, void* stream);
+int cppf_pose_eval_match_pose(const double* err, const int32_t* pred_off, const int32_t* gt_off, const int64_t* pair_off, int n_groups,
+                              const double* degree_thresholds, int n_degree, const double* shift_thresholds, int n_shift,
+                              const int32_t* keep_pred, const int32_t* keep_gt, int64_t n_pred, int64_t n_gt, int64_t n_pairs,
+                              int32_t* pred_match, int32_t* gt_match, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
