@@ -24,12 +24,16 @@
  *   - the closed-form (mu, nu) targets and the Fibonacci sphere are pinned against the
  *     reference's own utils/dataset.py:generate_target / utils/util.py:fibonacci_sphere,
  *     executed from their source text (same script).
- *   - the three vote kernels exist in the reference only as CUDA text inside CuPy RawKernel
- *     strings whose header needs the CUDA toolkit; that is unbuildable in this image without
- *     writing stand-ins, so for orc_ppf_voting / orc_backvote / orc_rot_voting:
- *     PARITY UNPINNED against executed reference code.  They are pinned only through the
- *     closed-form known answer (every vote circle of an exact (mu,nu) passes through the
- *     object centre, utils/dataset.py:27-36) and by line-by-line citation below.
+ *   - orc_ppf_voting / orc_backvote / orc_rot_voting are pinned on the reference's own EXECUTED kernel text:
+ *     oracle/ref_build.py reads the three CuPy RawKernel strings of models/voting.py and helper_math.cuh at
+ *     build time (nothing of them is stored here), redirects the header's CUDA-toolkit include to
+ *     oracle/ref_shim.h and compiles them as host C++ (contraction off, glibc trig) and for gfx950.  The host
+ *     build is bit-equal to voting_variants.c's ORV_LIBM member (rot_voting, backvote) and its serial fp32
+ *     grid lies within the accumulation bound of that member's exact grid (tests/test_ref_vote_cpu.py, also
+ *     against tests/golden/ref_vote.npz where there is no reference); variant 0 of that file is this file
+ *     bit for bit (tests/test_oracle_variants.py).  The device builds run against the HIP kernels in
+ *     tests/test_gpu_ref_vote.py.  The closed-form known answer (every vote circle of an exact (mu,nu)
+ *     passes through the object centre, utils/dataset.py:27-36) and the citations below remain.
  *
  * Arithmetic conventions (they are what makes the HIP path comparable bit-for-bit):
  *   - compiled with -ffp-contract=off; every fused multiply-add is an explicit fmaf()/fma().

@@ -274,18 +274,22 @@ VARIANTS = {
 }
 
 
-def ppf_voting_variant(points, outputs, probs, point_idxs, dims, corner, res, n_rots, adaptive, variant, threads=None):
-    """models/voting.py:8-66 under an arithmetic variant -> the exact (fp64) vote grid."""
+def ppf_voting_variant(points, outputs, probs, point_idxs, dims, corner, res, n_rots, adaptive, variant, threads=None,
+                       return_counts=False):
+    """models/voting.py:8-66 under an arithmetic variant -> the exact (fp64) vote grid; with return_counts also the number of
+    deposits per cell (i32), computed on one thread."""
     points, outputs, probs = _c(points, _f), _c(outputs, _f), _c(probs, _f)
     point_idxs, corner = _c(point_idxs, np.int32), _c(corner, _f)
     gx, gy, gz = (int(d) for d in dims)
     grid = np.zeros((gx, gy, gz), np.float64)
+    counts = np.zeros((gx, gy, gz), np.int32) if return_counts else None
     if threads is None:
         threads = max(1, min(num_threads(), 16, int(2 ** 31 // max(grid.nbytes, 1))))
     lib().orv_ppf_voting_f64(_p(points, _pf), _p(outputs, _pf), _p(probs, _pf), _p(point_idxs, _pi32), _p(grid, _pd),
                              _p(corner, _pf), C.c_float(res), C.c_int64(point_idxs.shape[0]), C.c_int(n_rots), C.c_int(gx),
-                             C.c_int(gy), C.c_int(gz), C.c_int(1 if adaptive else 0), C.c_int(int(variant)), C.c_int(threads))
-    return grid
+                             C.c_int(gy), C.c_int(gz), C.c_int(1 if adaptive else 0), C.c_int(int(variant)), C.c_int(threads),
+                             _p(counts, _pi32) if return_counts else None)
+    return (grid, counts) if return_counts else grid
 
 
 def vote_flips(points, outputs, point_idxs, dims, corner, res, n_rots, adaptive, variant):

@@ -7,10 +7,13 @@
  * Why this exists.  The reference compiles its kernels at run time with NVRTC (cupy.RawKernel, models/voting.py:67,113,148:
  * the only option passed is `-I models/include`), so it runs with NVRTC's defaults: --fmad=true (a multiply feeding an add
  * may be contracted into one fused multiply-add, at the compiler's discretion, in NVVM or later in ptxas) and CUDA's device
- * cosf / sinf / tanf (documented maximum error 1-2 ulp for sin/cos, 4 ulp for tan; source not available).  Neither can be
- * executed here (no CUDA), and neither is specified tightly enough to be restated: WHICH products are fused is the compiler's
- * choice.  oracle/cppf_oracle.c therefore fixes one member of the family (no contraction, correctly rounded trigonometry) and
- * the HIP kernels follow it bit for bit.  This file evaluates OTHER members of the family:
+ * cosf / sinf / tanf (documented maximum error 1-2 ulp for sin/cos, 4 ulp for tan; source not available).  That toolchain
+ * cannot be run here (no CUDA), and neither freedom is specified tightly enough to be restated: WHICH products are fused is the
+ * compiler's choice.  The kernel TEXT can be executed, and is: oracle/ref_build.py compiles it as host C++ (no contraction,
+ * glibc trig: exactly ORV_LIBM below, which tests/test_ref_vote_cpu.py demands bit for bit) and for gfx950 with hipcc (its
+ * contraction choices and ocml's trig: one more member of the family, tests/test_gpu_ref_vote.py).  oracle/cppf_oracle.c
+ * therefore fixes one member of the family (no contraction, correctly rounded trigonometry) and the HIP kernels follow it bit
+ * for bit.  This file evaluates OTHER members of the family:
  *
  *   ORV_FMAD_LEFT   every `p*q + r` becomes fma(p,q,r); of two products in a sum the LEFT one is fused (`p*q + r*s` ->
  *                   fma(p,q, r*s)), the combine order of LLVM's DAG combiner which NVVM derives from; a 3-term dot product
@@ -205,14 +208,15 @@ static inline int in_grid(v3 g, int gx, int gy, int gz)
 }
 
 /* models/voting.py:8-66 under `variant`, accumulated in fp64 (the exact sum every ordering of the reference's fp32
- * atomicAdd approximates), OpenMP over pair slices with private grids.  grid is ADDED to. */
+ * atomicAdd approximates), OpenMP over pair slices with private grids.  grid is ADDED to.  counts (may be NULL; forces one
+ * thread): the number of deposits each cell received, ADDED to. */
 void orv_ppf_voting_f64(const float* points, const float* outputs, const float* probs, const int32_t* point_idxs,
                         double* grid, const float* corner, float res, int64_t n_ppfs, int n_rots, int gx, int gy, int gz,
-                        int adaptive, int variant, int threads)
+                        int adaptive, int variant, int threads, int32_t* counts)
 {
     const int v = variant;
     const size_t G = (size_t)gx * gy * gz;
-    if (threads < 1) threads = 1;
+    if (threads < 1 || counts) threads = 1;
     double* priv = threads > 1 ? (double*)calloc((size_t)threads * G, sizeof(double)) : grid;
     const v3 cr = {corner[0], corner[1], corner[2]};
 #pragma omp parallel num_threads(threads)
@@ -242,6 +246,8 @@ void orv_ppf_voting_f64(const float* points, const float* outputs, const float* 
                 int64_t syz = (int64_t)gy * gz, b = fx * syz + fy * gz + fz;
                 int64_t off[8] = {0, 1, gz, gz + 1, syz, syz + 1, syz + gz, syz + gz + 1};
                 for (int q = 0; q < 8; ++q) g_[b + off[q]] += (double)w[q];
+                if (counts)
+                    for (int q = 0; q < 8; ++q) counts[b + off[q]] += 1;
             }
         }
     }
