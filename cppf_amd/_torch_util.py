@@ -22,14 +22,42 @@ class scratch:
         self.buf = buf
 
 
-def _arg(a):
-    """what ctypes is handed for one argument: the address of a tensor or of a C-contiguous numpy array, 0 / 1 for a bool; None
-    (NULL), Python numbers and ctypes arrays / pointers pass unchanged"""
+def _cuda_device(device):
+    """`device` of call() as a torch.device with its index filled in; anything but a HIP device is refused"""
+    if isinstance(device, torch.device) and device.index is not None and device.type == "cuda":
+        return device                                # (what every call site passes: pc.device and its like)
+    d = device if isinstance(device, torch.device) else torch.device(device)
+    if d.type != "cuda":
+        raise ValueError(f"expected a HIP device, got {d}")
+    return d if d.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _where(name, pos):
+    """the entry point and the argument position (call) or the struct and the field (fill) of an error message"""
+    return f"{name}, argument {pos}" if isinstance(pos, int) else f"{name}.{pos}"
+
+
+def _arg(a, didx=-1, name="the C ABI", pos=0, placed=True):
+    """what ctypes is handed for one argument: the address of a C-contiguous tensor or numpy array, 0 / 1 for a bool; None (NULL),
+    Python numbers and ctypes arrays / pointers pass unchanged.  The last line of defence in front of a kernel: a tensor that is
+    not C-contiguous is refused, and so is one in the wrong place -- with `didx` >= 0 (the index of the launch's HIP device) it must
+    live on that device or in pinned host memory (what the header allows there is the entry point's business: cppf_copy_words),
+    with -1 (a host-only entry point) it must not live on a device; placed=False: contiguity only.  `name` / `pos` name the entry
+    point and the argument in the error.  (get_device() / is_cuda: the two cheapest questions that settle the place.)"""
     if isinstance(a, torch.Tensor):
+        if not a.is_contiguous():
+            raise ValueError(f"{_where(name, pos)}: a tensor passed to the C ABI must be C-contiguous (shape {tuple(a.shape)}, "
+                             f"strides {a.stride()})")
+        if placed and (a.get_device() != didx or a.is_cuda != (didx >= 0)):
+            if didx < 0:
+                raise ValueError(f"{_where(name, pos)}: a host-only entry point was handed a tensor on {a.device}")
+            if not (a.device.type == "cpu" and a.is_pinned()):
+                raise ValueError(f"{_where(name, pos)}: tensor on {a.device}, the launch is on cuda:{didx} (only pinned host memory "
+                                 "may stand in)")
         return a.data_ptr()
     if isinstance(a, np.ndarray):
         if not a.flags.c_contiguous:
-            raise ValueError("a numpy array passed to the C ABI must be C-contiguous")
+            raise ValueError(f"{_where(name, pos)}: a numpy array passed to the C ABI must be C-contiguous")
         return a.ctypes.data
     return int(a) if isinstance(a, bool) else a
 
@@ -37,10 +65,14 @@ def _arg(a):
 def call(name, device, *args, ok=()):
     """The one path into the C ABI: `name`(*args, stream) with `device` current, on its current stream (device None: a host-only
     entry point, which takes no stream); raises CppfError naming `name` on a non-zero return unless the code is listed in `ok`.
-    Returns the code."""
+    Returns the code.  Every tensor argument is checked by _arg before anything is launched."""
     fn, conv = getattr(_lib.lib(), name), []
-    for a in args:              # (`args` keeps every tensor / array referenced until the call has returned)
-        conv += [a.buf.data_ptr(), a.buf.nbytes] if isinstance(a, scratch) else [_arg(a)]
+    didx = -1 if device is None else _cuda_device(device).index
+    for i, a in enumerate(args):  # (`args` keeps every tensor / array referenced until the call has returned)
+        if isinstance(a, scratch):
+            conv += [_arg(a.buf, didx, name, i), a.buf.nbytes]
+        else:
+            conv.append(_arg(a, didx, name, i))
     if device is None:
         rc = fn(*conv)
     else:
@@ -51,17 +83,44 @@ def call(name, device, *args, ok=()):
     return rc
 
 
-def fill(item, **fields):
-    """set fields of a ctypes item struct (_lib.*Item) with the conversion of call(); field=scratch(buf) also sets field_bytes"""
+def fill(item, _device=None, **fields):
+    """set fields of a ctypes item struct (_lib.*Item) with the conversion and the checks of call(); field=scratch(buf) also sets
+    field_bytes.  _device: the device of the launch the item is for -- tensors elsewhere (pinned host memory aside) are refused;
+    None: only contiguity is checked (the call the item goes into names no device for its members)."""
     known = dict(item._fields_)
+    didx = -1 if _device is None else _cuda_device(_device).index
     for k, v in fields.items():
         if isinstance(v, scratch):
-            fill(item, **{k: v.buf, k + "_bytes": v.buf.nbytes})
+            fill(item, _device, **{k: v.buf, k + "_bytes": v.buf.nbytes})
             continue
         if k not in known:
             raise AttributeError(f"{type(item).__name__} has no field {k!r}")
-        setattr(item, k, _arg(v))
+        setattr(item, k, _arg(v, didx, type(item).__name__, k, placed=_device is not None))
     return item
+
+
+def canon(x, dtype, dev, name, tail=None):
+    """The caller's data in the form the kernels read: a C-contiguous tensor of `dtype` on `dev`, detached -- x itself when it is
+    that already, else a converted copy (x.to(dtype).contiguous(): any floating type, any strides, any storage offset).  `dtype`
+    may be a tuple of index types (int32, int64): x is then used with the one it has, and any other raises TypeError.  Raises
+    ValueError naming the argument for a tensor on another device than `dev` (the CPU included: nothing is uploaded behind the
+    caller's back where a device tensor is expected) or a trailing shape other than `tail`."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch.Tensor on {dev}, got {type(x).__name__}")
+    if x.device != dev:
+        raise ValueError(f"{name}: tensor on {x.device}, expected {dev}")
+    if tail is not None and (x.dim() < len(tail) or tuple(x.shape[x.dim() - len(tail):]) != tuple(tail)):
+        raise ValueError(f"{name}: expected trailing shape {tuple(tail)}, got {tuple(x.shape)}")
+    if (x.dtype is dtype or (isinstance(dtype, tuple) and x.dtype in dtype)) and not x.requires_grad and x.is_contiguous():
+        return x                                     # (canonical already: what every internal caller passes)
+    if isinstance(dtype, tuple):
+        if x.dtype not in dtype:
+            raise TypeError(f"{name}: expected one of {', '.join(str(d) for d in dtype)}, got {x.dtype}")
+    elif x.dtype != dtype:
+        if dtype.is_floating_point and not x.dtype.is_floating_point:
+            raise TypeError(f"{name}: expected a floating-point tensor, got {x.dtype}")
+        x = x.detach().to(dtype)
+    return x.detach().contiguous()
 
 
 def copy_words(dst, src, device):

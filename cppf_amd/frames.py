@@ -195,7 +195,7 @@ class FrameRunner:
         n, arr = len(mems), (_lib.FrameCloudItem * len(mems))()
         for a, m in zip(arr, mems):
             pipe, cfg = m["pipe"], m["cfg"]
-            fill(a, label_bit_dev=m["slot"], seed_dev=m["slot"].data_ptr() + 8, pc_out=pipe.pc, nrm_out=pipe.nrm, corner_out=pipe.corner,
+            fill(a, dev, label_bit_dev=m["slot"], seed_dev=m["slot"].data_ptr() + 8, pc_out=pipe.pc, nrm_out=pipe.nrm, corner_out=pipe.corner,
                  shape_out=pipe.shape, nbrs_out=m["nbrs"], idx=pipe.idx, u_tr=pipe.u_tr, u_rot=pipe.u_rot, workspace=scratch(m["ws"]),
                  res=float(cfg.res), n_pairs=pipe.idx.shape[0], knn_k=cfg.knn, k_min=cfg.knn + 1, n_cap=m["cap"],
                  idx_is_i64=pipe.idx.dtype == torch.int64)

@@ -27,10 +27,29 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._torch_util import call, copy_words, fill, release_scope, require_cuda, scratch, workspace, workspace_scope
+from ._torch_util import call, canon, copy_words, fill, release_scope, require_cuda, scratch, workspace, workspace_scope
 from .models import voting
 
 F32, I32 = torch.float32, torch.int32
+
+
+def _canon_inputs(pc, pc_normal, feat, point_idxs, u_tr, u_rot, probs=None):
+    """The caller's tensors of estimate_center / estimate_pose in the form every launch of the chain reads ("Input
+    forms"): f32 / index dtype, C-contiguous, on pc's device -- converted once, so the centre half and the tail see the same
+    tensors; a tensor elsewhere (the CPU included) is refused by name before anything is launched.  A numpy pair list is uploaded
+    as PPFEncoder takes it (nocs/inference.py:177,182)."""
+    if not isinstance(pc, torch.Tensor) or not pc.is_cuda:
+        raise ValueError(f"pc: expected a tensor on a HIP device, got {getattr(pc, 'device', type(pc).__name__)}")
+    dev = pc.device
+    pc = canon(pc, F32, dev, "pc", (3,))
+    P = int(point_idxs.shape[0])
+    if isinstance(point_idxs, np.ndarray):
+        from .models.model import PPFEncoder
+        point_idxs = PPFEncoder._as_index_tensor(point_idxs, dev)
+    return (pc, canon(pc_normal, F32, dev, "pc_normal", (3,)), canon(feat, F32, dev, "feat"),
+            canon(point_idxs, (torch.int64, I32), dev, "point_idxs", (2,)), canon(u_tr, F32, dev, "u_tr", (P, 2)),
+            None if u_rot is None else canon(u_rot, F32, dev, "u_rot", (P, 2)),
+            None if probs is None else canon(probs, F32, dev, "probs"))
 
 
 def grid_shape(pc_host, res):
@@ -107,12 +126,16 @@ def estimate_center(encoder, pc, pc_normal, feat, point_idxs, u_tr, cfg, corner,
     """PPF -> MLP -> decode -> centre vote -> arg-max, all on device (the benchmarked chain).
     Returns (out_idx i64[1], out_val f32[1], outputs f32[P,2], heads f32[P,8] | None, grid)."""
     require_cuda()
+    pc, pc_normal, feat, point_idxs, u_tr, u_rot, probs = _canon_inputs(pc, pc_normal, feat, point_idxs, u_tr, u_rot, probs)
     dev = pc.device
+    corner = canon(corner, F32, dev, "corner")
     P = point_idxs.shape[0]
     if ws is None:
         ws = PoseWorkspace(dev, P, dims, 1)
     if idx32 is None:
         idx32 = point_idxs.to(I32)
+    else:
+        idx32 = canon(idx32, (I32,), dev, "idx32", (2,))
     # probs=None: all ones (nocs/inference.py:201) -- the vote then reads no probs at all
     outputs, heads = encoder.forward_decode(pc, pc_normal, feat, point_idxs, u_tr, cfg.vote_range, u_rot,
                                             cfg.tr_num_bins, cfg.rot_num_bins)
@@ -450,6 +473,8 @@ def estimate_pose(encoder, pc, pc_normal, feat, point_idxs, u_tr, u_rot, cfg, sp
     Returns a dict of host values: T f64[3], up/right f64[3], R f64[3,3], scale f64[3], scale_norm,
     argmax (flat grid index), peak, n_surv, counts_up/right (i32[S])."""
     require_cuda()
+    # once, at the top: the centre half, the second pass and the tail below all read these tensors
+    pc, pc_normal, feat, point_idxs, u_tr, u_rot, _ = _canon_inputs(pc, pc_normal, feat, point_idxs, u_tr, u_rot)
     dev = pc.device
     P = point_idxs.shape[0]
     if pc_host is None:
@@ -820,7 +845,7 @@ class PoseChain(_Captured):
         pipes = self.pipes
         arr = (_lib.StageItem * len(pipes))()
         for i, p in enumerate(pipes):
-            fill(arr[i], desc=self.desc[i], pc=p.pc, nrm=p.nrm, corner=p.corner, feat=p.feat if p.point_encoder is None else None,
+            fill(arr[i], self.device, desc=self.desc[i], pc=p.pc, nrm=p.nrm, corner=p.corner, feat=p.feat if p.point_encoder is None else None,
                  shape=p.shape if p.dynamic else None, idx=p.idx, u_tr=p.u_tr, u_rot=p.u_rot, n_pairs=p.idx.shape[0], n_cap=p.pc.shape[0],
                  F=p.feat.shape[1], res=float(np.float32(p.cfg.res)), idx_is_i64=p.idx.dtype == torch.int64)
         call("cppf_stage_batch", self.device, len(pipes), arr)
@@ -861,7 +886,7 @@ class PoseChain(_Captured):
             packed = p.encoder._packed_weights(self.device)
             gx, gy, gz = (1, 1, 1) if p.dynamic else p.dims
             # (idx64 None: the list is int32, idx32 is the input)
-            fill(arr[i], pc=p.pc, nrm=p.nrm, feat=feats[i], idx32=p.idx32, idx64=p.idx if p.idx.dtype == torch.int64 else None,
+            fill(arr[i], self.device, pc=p.pc, nrm=p.nrm, feat=feats[i], idx32=p.idx32, idx64=p.idx if p.idx.dtype == torch.int64 else None,
                  outputs=outputs[i], u_rot=p.u_rot, heads=heads[i], corner=p.corner, shape_dev=p.shape if p.dynamic else None,
                  argmax_idx=p.out_idx, peak=p.out_val, packed=packed, mlp_workspace=scratch(tables[i]),
                  vote_workspace=vws[i] if vws[i].numel() >= 32768 else None, rec=ws.rec, T32=ws.T32, tail0=scratch(ws._tail0),
@@ -870,7 +895,7 @@ class PoseChain(_Captured):
                  res=float(p.cfg.res), tol=float(np.float32(3 * p.cfg.res)), gx=gx, gy=gy, gz=gz, n_dirs=2 if p.cfg.regress_right else 1,
                  second_pass=not self.full_first)
             if self.staged:                      # the finished record, assembled by the last launch (:299-339)
-                fill(arr[i], record_out=self.records[i], object_id_dev=self.desc[i].data_ptr() + 40,
+                fill(arr[i], self.device, record_out=self.records[i], object_id_dev=self.desc[i].data_ptr() + 40,
                      scale_mean=(C.c_double * 3)(*[float(v) for v in p.cfg.scale_mean]), regress_right=bool(p.cfg.regress_right))
             keep.append((pws, packed))
         dims = (C.c_int * len(p0.encoder.ppffcs))(*p0.encoder.ppffcs)

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._torch_util import call, require_cuda, scratch, workspace
+from ._torch_util import call, canon, require_cuda, scratch, workspace
 from .config import CategoryConfig
 from .synthetic import philox4x32_10
 
@@ -84,6 +84,7 @@ def sample_surface_packed(verts, faces, vert_off, face_off, n_points, seed=0, fi
     tensors, no host synchronisation"""
     require_cuda()
     dev = verts.device
+    verts, faces = canon(verts, torch.float64, dev, "verts", (3,)), canon(faces, (torch.int32,), dev, "faces", (3,))
     M = len(face_off) - 1
     vert_off, face_off = np.ascontiguousarray(vert_off, np.int64), np.ascontiguousarray(face_off, np.int64)
     pts = torch.empty((M, int(n_points), 3), dtype=torch.float64, device=dev)
@@ -125,8 +126,8 @@ def sample_surface(vertices, faces, n, seed=0, device=None, return_faces=False):
 def vote_stats_batch(points, n_pairs=100000, seed=0, first_mesh=0):
     """cppf_mesh_vote_stats_batch on device points f64[M,N,3]: (stats f64[M,6] (STAT_COLUMNS), status i32[M]) device tensors"""
     require_cuda()
-    points = points.contiguous()
-    assert points.dtype == torch.float64 and points.dim() == 3 and points.shape[2] == 3
+    points = canon(points, torch.float64, points.device, "points", (3,))
+    assert points.dim() == 3
     M, N = int(points.shape[0]), int(points.shape[1])
     dev = points.device
     stats = torch.empty((M, 6), dtype=torch.float64, device=dev)

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._torch_util import call, require_cuda, scratch, workspace
+from ._torch_util import call, canon, require_cuda, scratch, workspace
 from .config import CATEGORIES, NOCS_CATEGORIES
 
 DATASET_K = np.array([[591.0125, 0, 320], [0, 590.16775, 240], [0, 0, 1]])   # utils/dataset.py:96 (not the inference intrinsics)
@@ -143,6 +143,9 @@ def render_depth(vertices, faces, pose, cull=True, fx=FX, fy=FY, width=WIDTH, he
 def depth_points(depth, intrinsics=DATASET_K):
     """The covered pixels of a rendered depth image as the dataset's cloud (utils/dataset.py:203-207): (pts f64[H*W,3], count
     i32[1]) device tensors, the first count rows valid, in row-major pixel order (include/cppf.h: cppf_depth_points)."""
+    depth = canon(depth, torch.float32, depth.device, "depth")      # (a strided view or another float type: a converted copy)
+    if depth.dim() != 2:
+        raise ValueError(f"depth must be [H,W], got {tuple(depth.shape)}")
     H, W = depth.shape
     pts = torch.empty((H * W, 3), dtype=torch.float64, device=depth.device)
     pix = torch.empty(H * W, dtype=torch.int32, device=depth.device)

@@ -31,7 +31,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib
-from .._torch_util import call, fill, require_cuda, scratch, workspace
+from .._torch_util import call, canon, dev_tensor, fill, require_cuda, scratch, workspace
 from .sprin import GlobalInfoProp, SparseSO3Conv, pack_point_encoder
 
 __all__ = ["ResLayer", "PPFEncoder", "PointEncoder"]
@@ -243,7 +243,7 @@ class PointEncoder(_DeviceWeights, nn.Module):
         if self._needs_graph(pc):
             if self._has_device_backward(pc, pc_normal):
                 pc2, nrm2 = self._check_inputs(pc, pc_normal)
-                d2 = None if dist is None else dist.detach().reshape(pc2.shape[0], pc2.shape[0]).float().contiguous()
+                d2 = None if dist is None else self._check_dist(dist, pc2)
                 out = _PointEncoderFunction.apply(self, pc2, nrm2, self.neighbours(pc2, d2), *self._ordered_params())
                 return out.reshape(*pc.shape[:-1], -1)
             if dist is None:
@@ -252,21 +252,19 @@ class PointEncoder(_DeviceWeights, nn.Module):
             return self._composite(pc, pc_normal, nbrs)
         pc2, nrm2 = self._check_inputs(pc, pc_normal)
         if dist is not None:
-            if dist.shape[-2:] != (pc2.shape[0], pc2.shape[0]):
-                raise ValueError(f"dist must be [..., N, N], got {tuple(dist.shape)}")
-            dist = dist.detach().reshape(pc2.shape[0], pc2.shape[0]).float().contiguous()
+            dist = self._check_dist(dist, pc2)
         return self._forward_device(pc2, nrm2, self.neighbours(pc2, dist)).reshape(*pc.shape[:-1], -1)
 
     def forward_nbrs(self, pc, pc_normal, nbrs_idx):
         if self._needs_graph(pc):
             if self._has_device_backward(pc, pc_normal):
                 pc2, nrm2 = self._check_inputs(pc, pc_normal)
-                nbrs = nbrs_idx.reshape(pc2.shape[0], -1).to(device=pc2.device, dtype=torch.int32).contiguous()
+                nbrs = self._check_nbrs(nbrs_idx, pc2)
                 out = _PointEncoderFunction.apply(self, pc2, nrm2, nbrs, *self._ordered_params())
                 return out.reshape(*pc.shape[:-1], -1)
             return self._composite(pc, pc_normal, nbrs_idx)
         pc2, nrm2 = self._check_inputs(pc, pc_normal)
-        nbrs = nbrs_idx.reshape(pc2.shape[0], -1).to(device=pc2.device, dtype=torch.int32).contiguous()
+        nbrs = self._check_nbrs(nbrs_idx, pc2)
         return self._forward_device(pc2, nrm2, nbrs).reshape(*pc.shape[:-1], -1)
 
     # ------------------------------------------------------------------ device path
@@ -355,7 +353,21 @@ class PointEncoder(_DeviceWeights, nn.Module):
                                  "move the module and its inputs to cuda")
         if pc.shape[-1] != 3 or pc_normal.shape != pc.shape or pc.dim() not in (2, 3) or (pc.dim() == 3 and pc.shape[0] != 1):
             raise ValueError("pc / pc_normal must be [1,N,3] (or [N,3])")
-        return (pc.detach().reshape(-1, 3).float().contiguous(), pc_normal.detach().reshape(-1, 3).float().contiguous())
+        return (canon(pc, torch.float32, pc.device, "pc").reshape(-1, 3), canon(pc_normal, torch.float32, pc.device, "pc_normal").reshape(-1, 3))
+
+    @staticmethod
+    def _check_nbrs(nbrs_idx, pc2):
+        """the caller's neighbour lists [..., N, k] (int32 / int64, any strides, on the cloud's device) as the i32[N,k] the
+        kernels read"""
+        nbrs = canon(nbrs_idx, (torch.int32, torch.int64), pc2.device, "nbrs_idx")
+        return nbrs.reshape(pc2.shape[0], -1).to(torch.int32)
+
+    @staticmethod
+    def _check_dist(dist, pc2):
+        """the caller's distance matrix [..., N, N] as the f32[N,N] the neighbour search reads, on the cloud's device"""
+        if dist.shape[-2:] != (pc2.shape[0], pc2.shape[0]):
+            raise ValueError(f"dist must be [..., N, N], got {tuple(dist.shape)}")
+        return canon(dist, torch.float32, pc2.device, "dist").reshape(pc2.shape[0], pc2.shape[0])
 
     def _packed_weights(self, device):
         key = self._param_key(device)
@@ -446,7 +458,7 @@ def point_encoder_forward_batch(members):
         packed, desc = m["encoder"]._packed_weights(dev)
         n_cap = m["pc"].shape[0]
         ws = workspace(L.cppf_point_encoder_workspace_bytes(n_cap, desc["n_out"], desc["n_glob"], 1), dev, f"point_encoder{i}")
-        fill(arr[i], pc=m["pc"], nrm=m["nrm"], nbrs=m["nbrs"], out=m["out"], n_dev=m.get("n_dev"), packed=packed, workspace=scratch(ws),
+        fill(arr[i], dev, pc=m["pc"], nrm=m["nrm"], nbrs=m["nbrs"], out=m["out"], n_dev=m.get("n_dev"), packed=packed, workspace=scratch(ws),
              n_cap=n_cap, nbrs_ready=bool(m.get("nbrs_ready")))
         keep.append((packed, ws))
     hid = (C.c_int * len(desc["hidden"]))(*desc["hidden"])
@@ -483,11 +495,11 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         return self.forward_with_idx(pc[0], pc_normal[0], feat[0], allp).reshape(1, n, n, self.out_dim)
 
     def forward_with_idx(self, pc, pc_normal, feat, idxs):
-        idxs = self._as_index_tensor(idxs, pc.device)
+        if self._needs_graph(feat) and not self._has_device_backward(pc, feat):      # torch ops: wherever the tensors are
+            return self._composite(pc, pc_normal, feat, self._as_index_tensor(idxs, pc.device))
+        idxs = self._as_index_tensor(idxs, self._device_of(pc))
         if self._needs_graph(feat):
-            if self._has_device_backward(pc, feat):
-                return _PairMlpFunction.apply(self, pc, pc_normal, feat, idxs, *self._ordered_params())
-            return self._composite(pc, pc_normal, feat, idxs)
+            return _PairMlpFunction.apply(self, pc, pc_normal, feat, idxs, *self._ordered_params())
         return self._forward_device(pc, pc_normal, feat, idxs)
 
     def _forward_device(self, pc, pc_normal, feat, idxs):
@@ -507,13 +519,11 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         u_rot is given): returns (outputs f32[P,2] = (mu, nu), heads f32[P,8] or None) without ever
         writing the [P,out_dim] logits.  u_* are uniforms in [0,1) standing in for torch.multinomial
         (negative = arg-max bin)."""
-        idxs = self._as_index_tensor(idxs, pc.device)
+        idxs = self._as_index_tensor(idxs, self._device_of(pc))
         pc, pc_normal, feat = self._check_inputs(pc, pc_normal, feat)
         P = idxs.shape[0]
-        for nm, u in (("u_tr", u_tr), ("u_rot", u_rot)):
-            if u is not None and (u.dtype != torch.float32 or not u.is_contiguous() or tuple(u.shape) != (P, 2)
-                                  or u.device != pc.device):
-                raise ValueError(f"{nm} must be a contiguous f32[P,2] tensor on {pc.device}")
+        u_tr = canon(u_tr, torch.float32, pc.device, "u_tr", (P, 2))
+        u_rot = None if u_rot is None else canon(u_rot, torch.float32, pc.device, "u_rot", (P, 2))
         outputs = torch.empty((P, 2), dtype=torch.float32, device=pc.device)
         heads = torch.empty((P, 8), dtype=torch.float32, device=pc.device) if u_rot is not None else None
         dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
@@ -543,9 +553,14 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         `heads` f32[P,8] (other rows untouched); u_rot f32[P,2] is indexed by original pair.  Must follow a forward_decode /
         forward_with_idx call on the same (feat, parameters) in the same scratch scope: the per-point table it left is reused.
         sel i32[>=max_sel] and n_sel i32[1] are device tensors (cppf_compact_mask's outputs), so no host sync."""
-        idxs = self._as_index_tensor(idxs, pc.device)
+        idxs = self._as_index_tensor(idxs, self._device_of(pc))
         pc, pc_normal, feat = self._check_inputs(pc, pc_normal, feat)
         P = idxs.shape[0]
+        u_rot = canon(u_rot, torch.float32, pc.device, "u_rot", (P, 2))
+        # (sel / n_sel are another kernel's outputs and heads is written in place: checked, never converted)
+        dev_tensor(sel, torch.int32, "sel", None, pc.device)
+        dev_tensor(n_sel, torch.int32, "n_sel", None, pc.device)
+        dev_tensor(heads, torch.float32, "heads", (P, 8), pc.device)
         max_sel = P if max_sel is None else min(int(max_sel), P)
         dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
         ws = self._scratch(pc, feat, dims)
@@ -628,19 +643,29 @@ class PPFEncoder(_DeviceWeights, nn.Module):
             raise TypeError(f"idxs: expected int64/int32, got {idxs.dtype}")
         if idxs.dim() != 2 or idxs.shape[1] != 2:
             raise ValueError(f"idxs: expected shape [P,2], got {tuple(idxs.shape)}")
-        return idxs.to(device).contiguous()
+        if idxs.device != torch.device(device):
+            raise ValueError(f"idxs: tensor on {idxs.device}, expected {device} (a numpy pair list is uploaded, a tensor is not)")
+        return idxs.contiguous()
+
+    @staticmethod
+    def _device_of(pc):
+        """the device every other argument must share: pc's -- looked at first, so that a cloud left on the host is what the error
+        names (not the pair list that disagrees with it)"""
+        if not isinstance(pc, torch.Tensor) or not pc.is_cuda:
+            raise _lib.CppfError(f"pc: PPFEncoder inference runs on a HIP device only (no CPU fallback), got pc on "
+                                 f"{getattr(pc, 'device', type(pc).__name__)}; move the module and its inputs to cuda")
+        return pc.device
 
     def _check_inputs(self, pc, pc_normal, feat):
         require_cuda()
-        if not pc.is_cuda:
-            raise _lib.CppfError("PPFEncoder inference runs on a HIP device only (no CPU fallback); "
-                                 "move the module and its inputs to cuda")
+        self._device_of(pc)
         if pc.dim() != 2 or pc.shape[1] != 3 or pc_normal.shape != pc.shape:
             raise ValueError("pc / pc_normal must be [N,3]")
         if feat.dim() != 2 or feat.shape[0] != pc.shape[0] or 2 * feat.shape[1] + 4 != self.ppffcs[0]:
             raise ValueError(f"feat must be [N,F] with 2F+4 == ppffcs[0] == {self.ppffcs[0]}")
-        return (pc.detach().float().contiguous(), pc_normal.detach().float().contiguous(),
-                feat.detach().float().contiguous())
+        # (a pc_normal / feat left on the host or on another GPU is refused here: its address means nothing to the launch)
+        return (canon(pc, torch.float32, pc.device, "pc"), canon(pc_normal, torch.float32, pc.device, "pc_normal"),
+                canon(feat, torch.float32, pc.device, "feat"))
 
     def _flat_params(self, device):
         """(flat device f32 copy of the parameters in `flatten_state_dict` order, host i64 offset table), rebuilt when a
@@ -748,7 +773,7 @@ def forward_decode_batch(items, tr_num_bins=32, rot_num_bins=36, tables_out=None
     if not 1 <= len(items) <= 8:
         raise ValueError("1 to 8 pair lists per launch")
     enc0 = items[0]["encoder"]
-    dev = items[0]["pc"].device
+    dev = enc0._device_of(items[0]["pc"])
     dims = (C.c_int * len(enc0.ppffcs))(*enc0.ppffcs)
     arr = (_lib.PairMlpItem * len(items))()
     keep, outs = [], []
@@ -758,20 +783,21 @@ def forward_decode_batch(items, tr_num_bins=32, rot_num_bins=36, tables_out=None
             raise ValueError("the encoders of one launch must share an architecture")
         idxs = enc._as_index_tensor(it["idxs"], dev)
         pc, nrm, feat = enc._check_inputs(it["pc"], it["pc_normal"], it["feat"])
+        if pc.device != dev:
+            raise ValueError(f"item {i}: pc on {pc.device}, the launch is on {dev}")
         P = idxs.shape[0]
-        u_tr, u_rot = it["u_tr"], it.get("u_rot")
-        for nm, u in (("u_tr", u_tr), ("u_rot", u_rot)):
-            if u is not None and (u.dtype != torch.float32 or not u.is_contiguous() or tuple(u.shape) != (P, 2) or u.device != dev):
-                raise ValueError(f"{nm} must be a contiguous f32[P,2] tensor on {dev}")
+        # (converted like forward_decode's: a captured pipeline's own buffers are canonical and pass as they are)
+        u_tr, u_rot = canon(it["u_tr"], torch.float32, dev, "u_tr", (P, 2)), it.get("u_rot")
+        u_rot = None if u_rot is None else canon(u_rot, torch.float32, dev, "u_rot", (P, 2))
         outputs = torch.empty((P, 2), dtype=torch.float32, device=dev)
         heads = torch.empty((P, 8), dtype=torch.float32, device=dev) if u_rot is not None else None
         need = _lib.lib().cppf_pair_mlp_workspace_bytes(pc.shape[0], feat.shape[1], dims, len(enc.ppffcs) - 1, enc.out_dim)
         ws = workspace(max(int(need), 256), dev, f"pair_mlp_batch{i}")       # (each list its own per-point table)
         packed = enc._packed_weights(dev)
-        fill(arr[i], pc=pc, nrm=nrm, feat=feat, idxs=idxs, packed=packed, u_tr=u_tr, u_rot=u_rot, outputs=outputs, heads=heads,
+        fill(arr[i], dev, pc=pc, nrm=nrm, feat=feat, idxs=idxs, packed=packed, u_tr=u_tr, u_rot=u_rot, outputs=outputs, heads=heads,
              workspace=scratch(ws), n_points=pc.shape[0], n_pairs=P, vr0=float(it["vote_range"][0]), vr1=float(it["vote_range"][1]),
              idx_is_i64=idxs.dtype == torch.int64)
-        keep.append((idxs, pc, nrm, feat, ws, packed))
+        keep.append((idxs, pc, nrm, feat, ws, packed, u_tr, u_rot))
         outs.append((outputs, heads))
     call("cppf_pair_mlp_decode_batch", dev, len(items), arr, items[0]["feat"].shape[1], dims, len(enc0.ppffcs) - 1, enc0.out_dim,
          tr_num_bins, rot_num_bins)

@@ -36,7 +36,7 @@ def _as_device_tensor(a):
     # temporary and the caller's array stay zero)
     t = torch.as_tensor(a)
     ptr = a.__cuda_array_interface__["data"][0]
-    if not t.is_cuda or (t.numel() > 0 and t.data_ptr() != ptr):
+    if not t.is_cuda or not t.is_contiguous() or (t.numel() > 0 and t.data_ptr() != ptr):
         raise ValueError("could not wrap the __cuda_array_interface__ array zero-copy (a strided or read-only view?): pass a "
                          "C-contiguous device array")
     return t
@@ -207,7 +207,7 @@ def vote_argmax_batch(items, n_rots, adaptive, accumulate=False, workgroups=0, w
             dev_tensor(shape, I32, "shape", None, dev)
             many = _lib.tile_class(it.get("many_tiles") or 0)
             ws = workspace(L.cppf_vote_workspace_bytes_dyn_pairs(many, int(n_ppfs)), dev, f"{ws_tag}dyn{i}", zero=True)
-            fill(a, shape_dev=shape, grid_capacity=grid.numel(), many_tiles=many, gx=1, gy=1, gz=1)
+            fill(a, dev, shape_dev=shape, grid_capacity=grid.numel(), many_tiles=many, gx=1, gy=1, gz=1)
         else:
             if grid.dim() != 3:
                 raise ValueError("grid must be [gx,gy,gz] (or pass `shape` for a capacity buffer)")
@@ -217,7 +217,7 @@ def vote_argmax_batch(items, n_rots, adaptive, accumulate=False, workgroups=0, w
                 raise ValueError(f"n_rots must be in 1..360, got {n_rots}")
             ws = workspace(need, dev, f"{ws_tag}{i}", zero=True)
             fill(a, shape_dev=None, grid_capacity=0, many_tiles=0, gx=gx, gy=gy, gz=gz)
-        fill(a, points=points, outputs=outputs, probs=probs, point_idxs=idx, idx_is_i64=i64, grid=grid, corner=corner, out_idx=out_idx,
+        fill(a, dev, points=points, outputs=outputs, probs=probs, point_idxs=idx, idx_is_i64=i64, grid=grid, corner=corner, out_idx=out_idx,
              out_val=out_val, workspace=scratch(ws), n_points=points.shape[0], n_ppfs=n_ppfs, res=float(scalar(it["res"])))
         keep.append(ws)
     call("cppf_vote_argmax_batch", dev, len(items), arr, int(n_rots), bool(adaptive), flags)

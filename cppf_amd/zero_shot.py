@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._torch_util import call, require_cuda, scratch, workspace
+from ._torch_util import call, canon, require_cuda, scratch, workspace
 from .models import voting
 from .utils.util import fibonacci_sphere, num_sphere_bins
 
@@ -120,12 +120,21 @@ def scene_proposals(grid, corner, res, sigma=1, thresh=50, margin=10, max_propos
 
 
 def _pairs_tensor(idx, dev):
-    t = torch.as_tensor(idx)
-    if t.dim() != 2 or t.shape[1] != 2:
-        raise ValueError(f"pair list must be [P,2], got {tuple(t.shape)}")
-    if t.dtype not in (torch.int32, torch.int64):
-        t = t.long()
-    return t.to(dev).contiguous()
+    """the pair list as PPFEncoder takes it: a numpy array is host data and is uploaded (other integer widths widened); a tensor
+    must be int32 / int64 on `dev` -- any strides"""
+    if not isinstance(idx, torch.Tensor):
+        a = np.asarray(idx)
+        if a.dtype.kind not in "iu":
+            raise TypeError(f"pair list: expected integers, got {a.dtype}")
+        idx = torch.from_numpy(np.ascontiguousarray(a if a.dtype in (np.int32, np.int64) else a.astype(np.int64))).to(dev)
+    return canon(idx, (torch.int64, torch.int32), dev, "pair list", (2,))
+
+
+def _on_device(x, dev, name, tail=None):
+    """f32 data of the caller on `dev`: a numpy array (or list) is uploaded, a tensor is converted where it is or refused"""
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32)).to(dev)
+    return canon(x, F32, dev, name, tail)
 
 
 def _compact(mask, dev):
@@ -144,7 +153,7 @@ def distinct_pairs(pc, nrm, idx):
     """Cell 6: the pairs of `idx` that are not "indistinguishable", in their order (same dtype as idx, on pc's device)."""
     require_cuda()
     dev = pc.device
-    pc, nrm = pc.float().contiguous(), nrm.float().contiguous()
+    pc, nrm = canon(pc, F32, dev, "pc", (3,)), canon(nrm, F32, dev, "nrm", (3,))
     idx = _pairs_tensor(idx, dev)
     P = idx.shape[0]
     keep = torch.empty(max(P, 1), dtype=U8, device=dev)
@@ -174,11 +183,10 @@ def _segment_enqueue(pc, outputs, idx32, T32, corner, res, dims, num_rots, tol, 
 def _prep(pc, outputs, idx, corner):
     require_cuda()
     dev = pc.device
-    pc = pc.float().contiguous()
+    pc = canon(pc, F32, dev, "pc", (3,))
     idx32 = _pairs_tensor(idx, dev).to(I32).contiguous()
-    outputs = outputs.to(dev).float()[:, :2].contiguous()
-    corner = corner.float() if isinstance(corner, torch.Tensor) else torch.from_numpy(np.asarray(corner, np.float32).copy())
-    corner = corner.to(dev).contiguous()
+    outputs = _on_device(outputs, dev, "outputs")[:, :2].contiguous()
+    corner = _on_device(corner, dev, "corner")
     return dev, pc, outputs, idx32, corner
 
 
@@ -222,7 +230,7 @@ def zero_shot_scene(encoder9, pc, nrm, feat, idx, cfg, angle_tol=2, max_rot_pair
     from .inference import grid_shape
     require_cuda()
     dev = pc.device
-    pc, nrm = pc.float().contiguous(), nrm.float().contiguous()
+    pc, nrm = canon(pc, F32, dev, "pc", (3,)), canon(nrm, F32, dev, "nrm", (3,))     # (detached: the host copy below is of a leaf too)
     idx = _pairs_tensor(idx, dev)
     idx32 = idx.to(I32).contiguous()
     P = idx.shape[0]
@@ -231,7 +239,7 @@ def zero_shot_scene(encoder9, pc, nrm, feat, idx, cfg, angle_tol=2, max_rot_pair
             raise ValueError(f"the zero-shot path needs the 9-wide regression head, the encoder has out_dim {encoder9.out_dim}")
         with torch.no_grad():
             preds = encoder9.forward_with_idx(pc, nrm, feat, idx)                             # cell 7
-    preds = torch.as_tensor(preds).to(dev).float().contiguous()
+    preds = _on_device(preds, dev, "preds")
     if tuple(preds.shape) != (P, 9):
         raise ValueError(f"preds must be [{P}, 9], got {tuple(preds.shape)}")
     outputs = preds[:, :2].contiguous()

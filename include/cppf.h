@@ -17,6 +17,10 @@
  *     CPPF_E* code for argument errors.  No exceptions cross the ABI.
  *   - outputs follow the reference: caller-allocated, (zero-)initialised by the caller, updated
  *     in place.
+ *   - arrays are DENSE, C-ordered, of exactly the element type named, and aligned to their element (the 12-byte rows of points and
+ *     normals are read float by float: 4-byte alignment is enough; pair lists, (mu, nu) and the bin uniforms are read a row at a
+ *     time: 8 bytes for int32[.,2] / float[.,2], 16 for int64[.,2]) -- the ABI takes no strides; what the Python layer converts or
+ *     refuses in front of it is INTEGRATION.md, "Input forms".
  *   - workspaces are caller-provided device scratch; size them with the *_workspace_bytes()
  *     queries.  The library allocates nothing and keeps no global state.
  *   - ONE exception to "plain scratch": the workspace of the centre vote (cppf_vote_argmax*, cppf_ppf_voting, cppf_vote_grid_raw,

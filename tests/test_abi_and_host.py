@@ -157,6 +157,104 @@ def test_call_helper_converts_arguments_and_reports_errors(monkeypatch):
         tu.fill(item, feat=a.T)
 
 
+class _On(torch.Tensor):
+    """a host tensor that reports another device: stands in for a device tensor where no device is present (the checks look at
+    .device / .get_device() / .is_cuda, .is_contiguous() and .data_ptr() only).  `_where` is set on the instance by _on(); a VIEW of
+    such a tensor is an _On again but falls back to the class default cuda:0 -- so views are only ever taken of tensors that
+    report cuda:0 (t0, ws); a tensor that reports another device (t1) is passed whole."""
+    _where = torch.device("cuda", 0)
+
+    @property
+    def device(self):
+        return self._where
+
+    @property
+    def is_cuda(self):
+        return True
+
+    def get_device(self):
+        return self._where.index
+
+
+def _on(t, index):
+    out = t.as_subclass(_On)
+    out._where = torch.device("cuda", index)
+    return out
+
+
+def test_call_helper_refuses_strided_and_misplaced_tensors(monkeypatch):
+    """the last line of defence of _torch_util.call / fill ("Input forms"): a tensor that is not C-contiguous, one
+    that is neither on the launch's device nor in pinned host memory, and a device tensor handed to a host-only entry point are
+    refused with the entry point and the argument in the message, and the library is never reached; what is in order passes"""
+    import contextlib
+    from cppf_amd import _lib, _torch_util as tu
+    fake = _FakeLib()
+    monkeypatch.setattr(_lib, "_lib", fake)
+    monkeypatch.setattr(tu, "stream_ptr", lambda device=None: 77)
+    monkeypatch.setattr(torch.cuda, "device", lambda d: contextlib.nullcontext())
+    pinned = set()
+    monkeypatch.setattr(torch.Tensor, "is_pinned", lambda self, *a: self.data_ptr() in pinned)
+    dev0 = torch.device("cuda", 0)
+    host = torch.arange(12, dtype=torch.float32).reshape(4, 3)
+    t0, t1 = _on(host.clone(), 0), _on(host.clone(), 1)
+    assert t0.device == dev0 and t1.device == torch.device("cuda", 1) and t0.is_contiguous()
+    ws = _on(torch.empty(320, dtype=torch.uint8), 0)
+    pin = torch.zeros(4, dtype=torch.int64)
+    pinned.add(pin.data_ptr())
+    # in order: contiguous tensors on the launch's device (a row and a row range of one included), pinned host memory, scratch
+    assert tu.call("cppf_x", dev0, t0, t0[1], t0[1:3], pin, None, 5, tu.scratch(ws)) == 0
+    assert fake.calls == [("cppf_x", (t0.data_ptr(), t0.data_ptr() + 12, t0.data_ptr() + 12, pin.data_ptr(), None, 5, ws.data_ptr(), 320, 77))]
+    assert tu.call("cppf_x", "cuda:0", t0) == 0 and len(fake.calls) == 2            # (the device as a string)
+    refusals = [
+        (dev0, (t0, t0.t()), "cppf_x, argument 1.*C-contiguous"),                   # transposed
+        (dev0, (t0[:, :2],), "cppf_x, argument 0.*C-contiguous"),                   # column slice
+        (dev0, (t0[::2],), "cppf_x, argument 0.*C-contiguous"),                     # row stride
+        (dev0, (t0[:1].expand(4, 3),), "cppf_x, argument 0.*C-contiguous"),         # zero stride
+        (dev0, (7, 0.5, host), "cppf_x, argument 2.*tensor on cpu, the launch is on cuda:0"),      # pageable host memory
+        (dev0, (t0, t1), "cppf_x, argument 1.*tensor on cuda:1, the launch is on cuda:0"),         # another GPU
+        (torch.device("cuda", 1), (t0,), "cppf_x, argument 0.*tensor on cuda:0, the launch is on cuda:1"),
+        (dev0, (tu.scratch(_on(torch.empty(8, dtype=torch.uint8), 1)),), "cppf_x, argument 0.*cuda:1"),
+        (None, (host, t0), "cppf_x, argument 1.*host-only entry point.*cuda:0"),    # a device tensor, no device
+        (None, (host.t(),), "cppf_x, argument 0.*C-contiguous"),
+        ("cpu", (host,), "expected a HIP device, got cpu"),                         # a launch has no CPU to run on
+    ]
+    for device, args, msg in refusals:
+        with pytest.raises(ValueError, match=msg):
+            tu.call("cppf_x", device, *args)
+    assert len(fake.calls) == 2                                   # no refusal reached the library
+    # fill: the same checks, the field named; without a device only contiguity is looked at
+    item = tu.fill(_lib.PoseTailItem(), dev0, pc=t0, feat=pin, mlp_workspace=tu.scratch(ws), idx64=None, n_pairs=5)
+    assert (item.pc, item.feat, item.mlp_workspace, item.mlp_workspace_bytes, item.n_pairs) == (t0.data_ptr(), pin.data_ptr(), ws.data_ptr(), 320, 5)
+    before = item.pc
+    for device, fields, msg in [(dev0, dict(pc=t0[::2]), "PoseTailItem.pc.*C-contiguous"), (None, dict(pc=host.t()), "PoseTailItem.pc.*C-contiguous"),
+                                (dev0, dict(pc=host), "PoseTailItem.pc.*tensor on cpu"), (dev0, dict(nrm=t1), "PoseTailItem.nrm.*cuda:1"),
+                                (dev0, dict(mlp_workspace=tu.scratch(_on(torch.empty(8, dtype=torch.uint8), 1))), "PoseTailItem.mlp_workspace.*cuda:1")]:
+        with pytest.raises(ValueError, match=msg):
+            tu.fill(item, device, **fields)
+    assert item.pc == before
+    assert tu.fill(item, None, pc=t1).pc == t1.data_ptr()
+    # canon: the caller's data converted, or refused by name
+    c = tu.canon(host, torch.float32, torch.device("cpu"), "pc", (3,))
+    assert c.data_ptr() == host.data_ptr()                                          # canonical already: no copy
+    wide = torch.arange(36, dtype=torch.float64).reshape(4, 9)
+    v = tu.canon(wide[:, 3:6], torch.float32, torch.device("cpu"), "pc_normal", (3,))
+    assert v.is_contiguous() and v.dtype == torch.float32 and torch.equal(v, wide[:, 3:6].float()) and not v.requires_grad
+    i = torch.arange(8, dtype=torch.int32).reshape(4, 2)
+    assert tu.canon(i, (torch.int64, torch.int32), torch.device("cpu"), "idxs").dtype == torch.int32
+    with pytest.raises(TypeError, match="idxs: expected one of torch.int64, torch.int32, got torch.int16"):
+        tu.canon(i.short(), (torch.int64, torch.int32), torch.device("cpu"), "idxs")
+    with pytest.raises(TypeError, match="pc: expected a floating-point tensor"):
+        tu.canon(i, torch.float32, torch.device("cpu"), "pc")
+    with pytest.raises(ValueError, match="pc_normal: tensor on cpu, expected cuda:0"):
+        tu.canon(host, torch.float32, dev0, "pc_normal")
+    with pytest.raises(ValueError, match="feat: tensor on cuda:1, expected cuda:0"):
+        tu.canon(t1, torch.float32, dev0, "feat")
+    with pytest.raises(ValueError, match=r"u_tr: expected trailing shape \(4, 2\)"):
+        tu.canon(host, torch.float32, torch.device("cpu"), "u_tr", (4, 2))
+    with pytest.raises(TypeError, match="pc: expected a torch.Tensor"):
+        tu.canon(host.numpy(), torch.float32, dev0, "pc")
+
+
 def test_workspace_queries_and_argument_errors_without_a_device():
     from cppf_amd import _lib
     L = _lib.lib()

@@ -176,3 +176,25 @@ def test_kernels_accept_any_cuda_array_interface_object(dev):
         rot_voting_kernel(_blocks(P), (THREADS, 1, 1), (wrap(args_t[0]), wrap(args_t[1]), wrap(rot), wrap(out), wrap(args_t[3]),
                                                          wrap(args_t[5]), np.float32(cfg.res), P, ROTS, int(dims[0]), int(dims[1]), int(dims[2])))
     assert torch.equal(c_t, c_f)
+    # a strided foreign array ("strides" not None: every other row of a taller grid, every other column of a wider cloud) cannot be
+    # wrapped as the dense array the kernels write: refused by _as_device_tensor, nothing launched, the caller's memory untouched
+    class Strided(Foreign):
+        def __init__(self, t):
+            super().__init__(t)
+            self.__cuda_array_interface__["strides"] = tuple(s * t.element_size() for s in t.stride())
+    import cppf_amd.models.voting as V
+    tall = torch.zeros((2 * g_t.shape[0],) + tuple(g_t.shape[1:]), device="cuda")
+    wide = torch.zeros((600, 6), device="cuda")
+    wide[:, :3] = args_t[0]
+    assert Strided(tall[::2]).__cuda_array_interface__["strides"] is not None and not tall[::2].is_contiguous()
+    launched = []
+    orig_call = V.call
+    V.call = lambda *a, **k: launched.append(a[0])
+    try:
+        with pytest.raises(ValueError, match="could not wrap the __cuda_array_interface__ array zero-copy"):
+            ppf_kernel(_blocks(P), (THREADS, 1, 1), args_t[:4] + (Strided(tall[::2]),) + args_t[5:])
+        with pytest.raises(ValueError, match="could not wrap the __cuda_array_interface__ array zero-copy"):
+            ppf_kernel(_blocks(P), (THREADS, 1, 1), (Strided(wide[:, :3]),) + args_t[1:4] + (Foreign(tall[:g_t.shape[0]]),) + args_t[5:])
+    finally:
+        V.call = orig_call
+    assert launched == [] and float(tall.abs().sum()) == 0
