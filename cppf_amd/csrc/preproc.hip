@@ -16,19 +16,36 @@
 
 namespace {
 
+// The voxel index of one coordinate, v = floor((double)p / res), is packed into 21 bits with a bias of 2^20: the key holds
+// -2^20 <= v < 2^20 and nothing else.  A coordinate outside that range (NaN and +-inf included: every comparison with NaN is false)
+// is REFUSED, never masked into the range, where it would merge distinct voxels: *in_range goes false and the biased index
+// returned is 0, so that no out-of-range value is ever converted to an integer.
+__device__ __forceinline__ unsigned long long vox_axis(float p, double res, bool* in_range)
+{
+    const double v = floor((double)p / res);
+    const bool ok = v >= -1048576.0 && v < 1048576.0;
+    *in_range = *in_range && ok;
+    return ok ? (unsigned long long)((int64_t)v + (1 << 20)) : 0ull;
+}
+
+// *flag <- 1 when a point of the cloud is out of range (cleared by the caller before the launch)
 __global__ __launch_bounds__(256) void vox_keys_kernel(const float* __restrict__ pc, int64_t N, double res, int64_t* __restrict__ keys,
-                                                       int32_t* __restrict__ vals)
+                                                       int32_t* __restrict__ vals, int32_t* __restrict__ flag)
 {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    int64_t k = 0;
+    unsigned long long k = 0;
+    bool ok = true;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int64_t v = (int64_t)floor((double)pc[3 * i + c] / res) + (1 << 20);
-        k = (k << 21) | (v & ((1 << 21) - 1));
-    }
-    keys[i] = k;
+    for (int c = 0; c < 3; ++c) k = (k << 21) | vox_axis(pc[3 * i + c], res, &ok);
+    keys[i] = (int64_t)k;
     vals[i] = (int32_t)i;
+    if (!ok) *flag = 1;
+}
+// the tail of cppf_voxel_dedupe: a refused cloud reports count = -1
+__global__ void vox_refuse_kernel(const int32_t* __restrict__ flag, int32_t* __restrict__ count)
+{
+    if (*flag) *count = -1;
 }
 // the first entry of every run of equal keys (stable sort: the lowest index of the voxel) marks its point
 __global__ __launch_bounds__(256) void vox_mark_kernel(const int64_t* __restrict__ skeys, const int32_t* __restrict__ svals, int64_t N,
@@ -160,12 +177,13 @@ __device__ __forceinline__ unsigned fc_hash(unsigned long long k, unsigned mask)
 }
 // back-projection of the compacted pixels (bp_points_kernel's arithmetic), nocs/inference.py:132 `pc = pts / 1000.0` (fp64), the axis
 // flips of :136-137 (negations of utils/util.py:629-630's negations: exact), `.float()` of :140, the voxel key (vox_keys_kernel) and
-// the point's entry in the table
+// the point's entry in the table; a point out of the key's range (vox_axis) raises *refused
 template <typename T>
 __device__ __forceinline__ void fc_points_body(const T* __restrict__ depth, const int32_t* __restrict__ pix,
                                                const int32_t* __restrict__ count, int W, const Kinv& K, double divisor, double res,
                                                int n_cap, float* __restrict__ pcf, unsigned long long* __restrict__ keys,
-                                               unsigned long long* __restrict__ tkeys, int32_t* __restrict__ tidx, unsigned tmask)
+                                               unsigned long long* __restrict__ tkeys, int32_t* __restrict__ tidx, unsigned tmask,
+                                               int32_t* __restrict__ refused)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= min(*count, n_cap)) return;
@@ -177,12 +195,13 @@ __device__ __forceinline__ void fc_points_body(const T* __restrict__ depth, cons
     const double pts[3] = {-(xyz[0] * z / xyz[2]), -(xyz[1] * z / xyz[2]), xyz[2] * z / xyz[2]};
     const float f[3] = {(float)-(pts[0] / divisor), (float)-(pts[1] / divisor), (float)(pts[2] / divisor)};
     unsigned long long k = 0;
+    bool ok = true;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         pcf[3 * i + c] = f[c];
-        const int64_t q = (int64_t)floor((double)f[c] / res) + (1 << 20);     // (vox_keys_kernel)
-        k = (k << 21) | (unsigned long long)(q & ((1 << 21) - 1));
+        k = (k << 21) | vox_axis(f[c], res, &ok);     // (vox_keys_kernel)
     }
+    if (!ok) *refused = 1;      // (the member reports N = 0: fcb_gather_kernel; its point still enters the table, under a key in range)
     keys[i] = k;
     for (unsigned h = fc_hash(k, tmask);; h = (h + 1) & tmask) {
         const unsigned long long prev = atomicCAS(&tkeys[h], FC_EMPTY, k);
@@ -249,7 +268,7 @@ FcLayout fc_layout(int H, int W, int n_cap, int k)
     L.cmp1 = L.valid + up(n);
     L.pix = L.cmp1 + up(cppf_compact_workspace_bytes((int64_t)n));
     L.count = L.pix + up(n * sizeof(int32_t));
-    L.pcf = L.count + 256;                                        // count1 at +0, count2 at +64
+    L.pcf = L.count + 256;                                        // count1 at +0, count2 at +64, the refusal mark at +128
     L.keys = L.pcf + up((size_t)n_cap * 3 * sizeof(float));
     L.tkeys = L.keys + up((size_t)n_cap * sizeof(unsigned long long));
     L.tidx = L.tkeys + up((size_t)L.M * sizeof(unsigned long long));
@@ -330,7 +349,7 @@ __global__ __launch_bounds__(256) void stage_batch_kernel(StageBatch B)
 struct FcbItem {
     const int32_t* bit_dev; const unsigned long long* seed_dev;
     uint8_t *valid, *mask2;
-    int32_t *cc1, *cc2, *pix, *count1, *count2, *tidx, *keep, *nbrs, *shape_out;
+    int32_t *cc1, *cc2, *pix, *count1, *count2, *refused, *tidx, *keep, *nbrs, *shape_out;
     float *pcf, *pc_out, *nrm_out, *corner_out, *u_tr, *u_rot;
     unsigned long long *keys, *tkeys;
     void* idx;
@@ -341,13 +360,14 @@ struct FcbItem {
 struct FcbBatch { FcbItem item[FCB_MAX]; const void* depth; const void* labels; long long n_pix; Kinv K; double divisor; int W, label_bytes, n_sample_blocks; };
 static_assert(sizeof(FcbBatch) <= 4096, "FcbBatch travels by value: kernel arguments are limited to 4 KB");
 
-// 1. valid pixels of every member's label bit + their chunk counts; the member's voxel table cleared on the way
+// 1. valid pixels of every member's label bit + their chunk counts; the member's voxel table and refusal mark cleared on the way
 template <typename T>
 __global__ __launch_bounds__(CMP_BLOCK) void fcb_valid_kernel(FcbBatch B)
 {
     const FcbItem& I = B.item[blockIdx.y];
     const long long i = (long long)blockIdx.x * CMP_BLOCK + threadIdx.x;
     for (long long k = i; k < I.M; k += (long long)gridDim.x * CMP_BLOCK) { I.tkeys[k] = FC_EMPTY; I.tidx[k] = 0x7fffffff; }
+    if (i == 0) *I.refused = 0;
     bool f = false;
     if (i < B.n_pix) {
         const T d = static_cast<const T*>(B.depth)[i];
@@ -376,7 +396,7 @@ __global__ __launch_bounds__(256) void fcb_points_kernel(FcbBatch B)
 {
     const FcbItem& I = B.item[blockIdx.y];
     fc_points_body<T>(static_cast<const T*>(B.depth), I.pix, I.count1, B.W, B.K, B.divisor, I.res, I.n_cap, I.pcf, I.keys, I.tkeys, I.tidx,
-                      (unsigned)I.M - 1u);
+                      (unsigned)I.M - 1u, I.refused);
 }
 // 4. the representatives of the voxels + their chunk counts
 __global__ __launch_bounds__(CMP_BLOCK) void fcb_mark_kernel(FcbBatch B)
@@ -392,13 +412,14 @@ __global__ __launch_bounds__(CMP_BLOCK) void fcb_mark_kernel(FcbBatch B)
     const int s = compact_chunk_count(f);
     if (threadIdx.x == 0) I.cc2[blockIdx.x] = s;
 }
-// 6. pc = pc[keep], the point count
+// 6. pc = pc[keep], the point count: 0 below k_min, and 0 for a member with a point outside the voxel key's range (vox_axis) --
+// refused like a cloud that is too small, which every consumer of the shape record already skips, instead of merged voxels
 __global__ __launch_bounds__(256) void fcb_gather_kernel(FcbBatch B)
 {
     const FcbItem& I = B.item[blockIdx.y];
     const int n = min(*I.count2, I.n_cap);
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i == 0) I.shape_out[0] = n >= I.k_min ? n : 0;
+    if (i == 0) I.shape_out[0] = n >= I.k_min && !*I.refused ? n : 0;
     if (i >= n) return;
     const int sidx = I.keep[i];
     I.pc_out[3 * i] = I.pcf[3 * sidx]; I.pc_out[3 * i + 1] = I.pcf[3 * sidx + 1]; I.pc_out[3 * i + 2] = I.pcf[3 * sidx + 2];
@@ -435,7 +456,7 @@ __global__ __launch_bounds__(64) void gather_words_kernel(GatherRows G, unsigned
     for (int t = threadIdx.x; t < n_words; t += 64) dst[(size_t)blockIdx.x * n_words + t] = s_[t];
 }
 
-struct VoxLayout { size_t keys, vals, mask, compact, temp, temp_bytes, total; };
+struct VoxLayout { size_t keys, vals, mask, flag, compact, temp, temp_bytes, total; };
 VoxLayout vox_layout(int64_t N)
 {
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -443,7 +464,8 @@ VoxLayout vox_layout(int64_t N)
     L.keys = 0;
     L.vals = L.keys + up(2 * (size_t)N * sizeof(int64_t));   // keys + sorted keys
     L.mask = L.vals + up(2 * (size_t)N * sizeof(int32_t));   // vals + sorted vals
-    L.compact = L.mask + up((size_t)N);
+    L.flag = L.mask + up((size_t)N);                         // behind the mask: one memset clears both
+    L.compact = L.flag + 256;
     L.temp = L.compact + up(cppf_compact_workspace_bytes(N));
     L.temp_bytes = up((size_t)48 * N + (1u << 20));
     L.total = L.temp + L.temp_bytes;
@@ -469,19 +491,23 @@ int cppf_voxel_dedupe(const float* pc, int64_t n_points, double res, int32_t* ke
     int64_t *keys = (int64_t*)(ws + L.keys), *skeys = keys + n_points;
     int32_t *vals = (int32_t*)(ws + L.vals), *svals = vals + n_points;
     uint8_t* mask = (uint8_t*)(ws + L.mask);
+    int32_t* flag = (int32_t*)(ws + L.flag);
     const int nb = (int)((n_points + 255) / 256);
-    vox_keys_kernel<<<nb, 256, 0, st>>>(pc, n_points, res, keys, vals);
+    hipError_t e = hipMemsetAsync(mask, 0, L.flag + sizeof(int32_t) - L.mask, st);
+    if (e != hipSuccess) return (int)e;
+    vox_keys_kernel<<<nb, 256, 0, st>>>(pc, n_points, res, keys, vals, flag);
     size_t need = 0;
-    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, need, keys, skeys, vals, svals, (int)n_points, 0, 63, st);
+    e = hipcub::DeviceRadixSort::SortPairs(nullptr, need, keys, skeys, vals, svals, (int)n_points, 0, 63, st);
     if (e != hipSuccess) return (int)e;
     if (need > L.temp_bytes) return CPPF_EWORKSPACE;
     need = L.temp_bytes;
     e = hipcub::DeviceRadixSort::SortPairs(ws + L.temp, need, keys, skeys, vals, svals, (int)n_points, 0, 63, st);
     if (e != hipSuccess) return (int)e;
-    e = hipMemsetAsync(mask, 0, (size_t)n_points, st);
-    if (e != hipSuccess) return (int)e;
     vox_mark_kernel<<<nb, 256, 0, st>>>(skeys, svals, n_points, mask);
-    return cppf_compact_mask(mask, n_points, keep_idx, count, ws + L.compact, cppf_compact_workspace_bytes(n_points), stream);
+    const int rc = cppf_compact_mask(mask, n_points, keep_idx, count, ws + L.compact, cppf_compact_workspace_bytes(n_points), stream);
+    if (rc) return rc;
+    vox_refuse_kernel<<<1, 1, 0, st>>>(flag, count);      // (the flag becomes the count on the stream: no host synchronisation)
+    return (int)hipGetLastError();
 }
 
 size_t cppf_backproject_workspace_bytes(int H, int W)
@@ -546,6 +572,7 @@ static int fcb_member(FcbItem& I, const CppfFrameCloudItem& it, int label_bit, i
     I.valid = (uint8_t*)(ws + L.valid); I.mask2 = (uint8_t*)(ws + L.mask2);
     I.cc1 = (int32_t*)(ws + L.cmp1); I.cc2 = (int32_t*)(ws + L.cmp2); I.pix = (int32_t*)(ws + L.pix);
     I.count1 = (int32_t*)(ws + L.count); I.count2 = (int32_t*)(ws + L.count + 64);
+    I.refused = (int32_t*)(ws + L.count + 128);
     I.tidx = (int32_t*)(ws + L.tidx); I.keep = (int32_t*)(ws + L.keep); I.nbrs = it.nbrs_out ? it.nbrs_out : (int32_t*)(ws + L.nbrs);
     I.shape_out = it.shape_out; I.pcf = (float*)(ws + L.pcf); I.pc_out = it.pc_out; I.nrm_out = it.nrm_out; I.corner_out = it.corner_out;
     I.u_tr = it.u_tr; I.u_rot = it.u_rot; I.keys = (unsigned long long*)(ws + L.keys); I.tkeys = (unsigned long long*)(ws + L.tkeys);

@@ -96,7 +96,9 @@ def sparse_quantize(pc, return_index=True, quantization_size=1.0):
     """The call of nocs/inference.py:140, `ME.utils.sparse_quantize(pc, return_index=True, quantization_size=res)`, on
     the device: one representative per occupied voxel floor(p / res).  Returns (discrete_coords i32[M,3], indices
     i64[M]) like MinkowskiEngine (numpy in -> numpy out).  The representative is the lowest original index and the
-    output is in index order (MinkowskiEngine's choice is hash-order dependent: parity unpinned)."""
+    output is in index order (MinkowskiEngine's choice is hash-order dependent: parity unpinned).  Raises ValueError for
+    a cloud with a non-finite point or a voxel index outside [-2^20, 2^20) on an axis (the supported extent is
+    2^20 * quantization_size): such voxels would alias, so the cloud is refused, never silently thinned."""
     import torch
     from .. import _lib
     from .._torch_util import call, scratch, workspace
@@ -106,8 +108,17 @@ def sparse_quantize(pc, return_index=True, quantization_size=1.0):
     count = torch.zeros(1, dtype=torch.int32, device=t.device)
     ws = workspace(_lib.lib().cppf_voxel_dedupe_workspace_bytes(N), t.device, "voxel")
     call("cppf_voxel_dedupe", t.device, t, N, float(quantization_size), keep, count, scratch(ws))
-    idx = keep[:int(count.item())].long()
-    coords = torch.floor(t[idx].double() / float(quantization_size)).to(torch.int32)
+    n = int(count.item())
+    if n < 0:           # cppf_voxel_dedupe refuses such a cloud rather than merge distinct voxels (include/cppf.h, RANGE)
+        raise ValueError(f"sparse_quantize: a point is not finite or lies beyond the supported extent 2^20 * quantization_size = "
+                         f"{2 ** 20 * float(quantization_size):g} from the origin (quantization_size={float(quantization_size):g}); "
+                         "is the cloud in the units quantization_size is given in?")
+    idx = keep[:n].long()
+    # floor((double)p / res) as the kernel computes it: a true division.  Dividing a device tensor by a Python number multiplies by
+    # its reciprocal instead, which puts points that lie on a voxel face into the neighbouring voxel (26 of 12 000 face coordinates
+    # at res = 0.03); a tensor divisor divides.
+    p64 = t[idx].double()
+    coords = torch.floor(p64 / torch.full_like(p64, float(quantization_size))).to(torch.int32)
     if was_np:
         idx, coords = idx.cpu().numpy(), coords.cpu().numpy()
     return (coords, idx) if return_index else coords

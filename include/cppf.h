@@ -649,6 +649,11 @@ int cppf_point_encoder_forward_train(const float* pc, const float* nrm, const in
  *  cppf_voxel_dedupe     the role of ME.utils.sparse_quantize(pc, return_index=True, quantization_size=res)[1]
  *                        (nocs/inference.py:140): keep_idx device i32[n_points] receives, in ascending order, the lowest
  *                        index of every occupied voxel floor(p / res) (fp64 divide); count device i32[1] = how many.
+ *                        RANGE: per axis v = floor((double)p / res); a point is in range iff it is finite and
+ *                        -2^20 <= v < 2^20 on all three axes (the voxel key holds 21 bits per axis).  If ANY point is out of
+ *                        range the call writes count[0] = -1 and keep_idx is unspecified: distinct voxels are never merged,
+ *                        the cloud is refused (a cloud left in millimetres with a metre-sized res, a NaN).  The refusal is
+ *                        decided on the stream; the call does not synchronise.
  *  cppf_estimate_normals open3d estimate_normals(KDTreeSearchParamKNN(knn)) (utils/util.py:61-65): nbrs device
  *                        i32[n_points, k] (cppf_knn output: the point itself is a neighbour); normals device
  *                        f32[n_points, 3] = unit eigenvector of the smallest eigenvalue of the neighbours' covariance
@@ -664,11 +669,12 @@ int cppf_point_encoder_forward_train(const float* pc, const float* nrm, const in
  * captured, shape-polymorphic chains: no size visits the host.  A frame's depth image and a LABEL image (bit `label_bit` of pixel p
  * set <=> p belongs to the instance: up to 8 / 16 / 32 possibly overlapping instance masks in one upload) stay on the device;
  * the stage back-projects the instance's valid pixels (cppf_backproject's arithmetic), divides by `divisor` (1000: millimetres,
- * :132), flips x and y (:136-137), de-duplicates per voxel of edge `res` (cppf_voxel_dedupe's definition, :140-141), writes the cloud
+ * :132), flips x and y (:136-137), de-duplicates per voxel of edge `res` (cppf_voxel_dedupe's definition and RANGE, :140-141), writes the cloud
  * to pc_out f32[n_cap,3], its PCA normals over knn_k neighbours (cppf_knn + cppf_estimate_normals, :142) to nrm_out f32[n_cap,3], the
  * grid corner to corner_out f32[3] and the instance's shape record to shape_out i32[4] = {N, gx, gy, gz} -- what the *_dyn entry
  * points read.  N = 0 (and a 1x1x1 grid) when fewer than k_min points are left: the reference skips such instances (:121-123);
- * the *_dyn vote then reports arg-max -1.  n_cap >= the number of set label pixels (the caller counts them on the host) bounds
+ * the *_dyn vote then reports arg-max -1.  A member with a point outside cppf_voxel_dedupe's RANGE (a voxel index beyond +-2^20, a
+ * non-finite depth) reports N = 0 in the same way -- refused, not merged -- and leaves the other members of a batch untouched.  n_cap >= the number of set label pixels (the caller counts them on the host) bounds
  * every buffer; rows >= N of pc_out / nrm_out are left untouched.  nbrs_out (may be NULL): device i32[n_cap, knn_k] that receives the
  * neighbour sets the normals were fitted on -- cppf_knn's output, which a point encoder with the same k can reuse instead of
  * searching again (nocs/inference.py:180 computes the same cdist + topk).  Results equal the four single calls on the same inputs, bit for
@@ -698,7 +704,7 @@ typedef struct CppfFrameCloudItem {
     float* pc_out;                         /* device f32[n_cap,3] */
     float* nrm_out;                        /* device f32[n_cap,3] */
     float* corner_out;                     /* device f32[3] */
-    int32_t* shape_out;                    /* device i32[4] {N (0: fewer than k_min points), gx, gy, gz} */
+    int32_t* shape_out;                    /* device i32[4] {N (0: fewer than k_min points, or a point out of the voxel range), gx, gy, gz} */
     int32_t* nbrs_out;                     /* device i32[n_cap,knn_k] or NULL (kept in the workspace) */
     void* idx;                             /* device i64[n_pairs,2] (idx_is_i64) or i32[n_pairs,2] */
     float* u_tr;                           /* device f32[n_pairs,2] or NULL */

@@ -617,10 +617,13 @@ def pair_mlp_backward(pc, nrm, feat, idxs, sd, ppffcs, out_dim, grad_out, n_part
 # --------------------------------------------------------------------------- pre-processing (row f3)
 def voxel_dedupe(pc, res):
     """one representative (lowest index) per occupied voxel floor(p / res), ascending -- the role of
-    ME.utils.sparse_quantize(..., return_index=True)[1] at nocs/inference.py:140"""
+    ME.utils.sparse_quantize(..., return_index=True)[1] at nocs/inference.py:140.  A cloud with a point that is not finite or
+    whose voxel index floor(p / res) is outside [-2^20, 2^20) on an axis is refused (ValueError), never merged."""
     pc = _c(pc, _f)
     keep = np.empty(pc.shape[0], np.int32)
     n = lib().orc_voxel_dedupe(_p(pc, _pf), C.c_int64(pc.shape[0]), C.c_double(float(res)), _p(keep, _pi32))
+    if n < 0:
+        raise ValueError(f"voxel_dedupe: a point is not finite or lies beyond the supported extent 2^20 * res = {2 ** 20 * float(res):g}")
     return keep[:n].copy()
 
 

@@ -14,7 +14,7 @@
  *                          (the point itself included); open3d leaves the SIGN unspecified.
  *                          Here: covariance from fp64 cumulants like open3d (E[xx] - E[x]E[x]), cyclic Jacobi (8 sweeps,
  *                          fp64), sign chosen so that the component of largest magnitude is positive.
- * What IS pinned: these definitions against numpy (np.unique on the voxel keys, np.linalg.eigh up to sign) in
+ * What IS pinned: these definitions against numpy (np.unique on the int64 voxel index triples -- never on a packed key --, np.linalg.eigh up to sign) in
  * tests/test_oracle_golden.py, and the HIP kernels against this file bit for bit.
  */
 #include <math.h>
@@ -32,22 +32,29 @@ static int vox_cmp(const void* a, const void* b)
 static int i32_cmp(const void* a, const void* b) { return (*(const int32_t*)a > *(const int32_t*)b) - (*(const int32_t*)a < *(const int32_t*)b); }
 
 /* voxel coordinate: floor((double)p / (double)res) (numpy float64 semantics of the scripts: pc is float64 there,
- * nocs/inference.py:131-140); packed 21 bits per axis with a 2^20 bias */
+ * nocs/inference.py:131-140); packed 21 bits per axis with a 2^20 bias.  The key holds -2^20 <= v < 2^20 per axis: a point outside
+ * that range, or not finite (every comparison with NaN is false), is out of range -> -1; it is never masked into the range, where
+ * distinct voxels would merge, and never converted to an integer */
 static int64_t vox_key(const float* p, double res)
 {
     int64_t k = 0;
     for (int c = 0; c < 3; ++c) {
-        const int64_t v = (int64_t)floor((double)p[c] / res) + (1 << 20);
-        k = (k << 21) | (v & ((1 << 21) - 1));
+        const double v = floor((double)p[c] / res);
+        if (!(v >= -1048576.0 && v < 1048576.0)) return -1;
+        k = (k << 21) | ((int64_t)v + (1 << 20));
     }
     return k;
 }
 
-/* keep[] = lowest index of every occupied voxel, ascending; returns the count */
+/* keep[] = lowest index of every occupied voxel, ascending; returns the count, or -1 (keep unspecified) when any point is out of range */
 int64_t orc_voxel_dedupe(const float* pc, int64_t N, double res, int32_t* keep)
 {
     vox_ent* e = malloc(sizeof(vox_ent) * (size_t)(N > 0 ? N : 1));
-    for (int64_t i = 0; i < N; ++i) { e[i].key = vox_key(pc + 3 * i, res); e[i].idx = (int32_t)i; }
+    for (int64_t i = 0; i < N; ++i) {
+        e[i].key = vox_key(pc + 3 * i, res);
+        e[i].idx = (int32_t)i;
+        if (e[i].key < 0) { free(e); return -1; }
+    }
     qsort(e, (size_t)N, sizeof(vox_ent), vox_cmp);
     int64_t n = 0;
     for (int64_t i = 0; i < N; ++i)

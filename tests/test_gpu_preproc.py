@@ -46,11 +46,12 @@ def test_normals_match_oracle_numpy_and_known_answers(dev, oracle):
     radial = S / np.linalg.norm(S, axis=1, keepdims=True)
     assert np.degrees(np.arccos(np.clip(np.abs((ns * radial).sum(1)), 0, 1))).max() < 3.0
     nb = oracle.knn(S, 60)
-    for i in range(0, 4096, 257):
-        q = S[nb[i]].astype(np.float64)
-        w, v = np.linalg.eigh(np.cov(q.T, bias=True))
-        e = v[:, 0] * np.sign(v[np.abs(v[:, 0]).argmax(), 0])
-        np.testing.assert_allclose(ns[i], e, atol=2e-6)
+    q = S[nb].astype(np.float64)                                                       # all 4096 neighbour sets, one batched eigh
+    c = q - q.mean(1, keepdims=True)
+    w, v = np.linalg.eigh(np.einsum("nki,nkj->nij", c, c) / q.shape[1])
+    e = v[:, :, 0]
+    e = e * np.sign(e[np.arange(4096), np.abs(e).argmax(1)])[:, None]
+    np.testing.assert_allclose(ns, e, atol=2e-6)
 
 
 def test_raw_points_to_pose_entirely_on_device(dev, oracle):

@@ -294,7 +294,8 @@ def test_pair_mlp_backward_matches_reference_autograd(oracle, golden, tag, ppffc
 # --------------------------------------------------------------------------- pre-processing (row f3)
 def test_preprocessing_oracle_against_numpy(oracle):
     """oracle/preproc_oracle.c (parity with MinkowskiEngine / open3d is unpinned: absent here and under-specified) against
-    numpy's definitions: np.unique on the voxel keys, np.linalg.eigh of the neighbour covariance up to sign."""
+    numpy's definitions: np.unique on the int64 voxel index triples (never on a packed key: a packed key can alias, the triples
+    cannot), np.linalg.eigh of the neighbour covariance up to sign."""
     rng = np.random.default_rng(0)
     pc = rng.uniform(-0.2, 0.3, (5000, 3)).astype(np.float32)
     pc[4000:] = pc[:1000]
@@ -311,6 +312,94 @@ def test_preprocessing_oracle_against_numpy(oracle):
         w, v = np.linalg.eigh(np.cov(q.T, bias=True))
         e = v[:, 0] * np.sign(v[np.abs(v[:, 0]).argmax(), 0])
         np.testing.assert_allclose(nr[i], e, atol=2e-6)
+
+
+def _refused_not_merged(dedupe, pc, res, finite, tag):
+    """`dedupe(pc, res)` must raise ValueError.  If it returns instead, say what it did: its result is compared with np.unique over
+    the int64 index triples first, so that silently merged voxels are reported as such."""
+    import preproc_cases as PC
+    assert not PC.in_range(pc, res), tag
+    try:
+        keep = np.asarray(dedupe(pc, res))
+    except ValueError as e:
+        return str(e)
+    if finite:
+        assert np.array_equal(keep, PC.unique_first(pc, res)), (tag, "distinct voxels were merged", keep.tolist(), PC.unique_first(pc, res).tolist())
+    pytest.fail(f"{tag}: a cloud with a point out of the voxel range was not refused (kept {keep.size} of {pc.shape[0]})")
+
+
+def test_voxel_dedupe_oracle_edges_against_numpy_unique(oracle):
+    """orc_voxel_dedupe against np.unique over int64 index triples where a de-duplication goes wrong: coordinates on voxel faces and
+    one float32 step to either side, -0.0 and mixed signs around the origin, the extreme voxel indices -2^20 and 2^20 - 1 next to
+    their neighbours, block-edge sizes with one voxel and with all voxels distinct; and the range contract: indices 2^20 and
+    -2^20 - 1, the four-point aliasing cloud, NaN and +-inf are refused (ValueError), never merged."""
+    import preproc_cases as PC
+    for res in (0.004, 0.01, 0.03, 0.1):
+        pc = PC.faces_cloud(res)
+        assert np.array_equal(oracle.voxel_dedupe(pc, res), PC.unique_first(pc, res)), res
+    for res in (0.004, 0.01):
+        pc = PC.signs_cloud(res)
+        want = PC.unique_first(pc, res)
+        assert np.array_equal(oracle.voxel_dedupe(pc, res), want) and want.size == 8, (res, want.size)
+    pc = PC.range_edge_cloud()
+    want = PC.unique_first(pc, PC.RANGE_RES)
+    assert PC.in_range(pc, PC.RANGE_RES) and want.size == 13
+    assert np.array_equal(oracle.voxel_dedupe(pc, PC.RANGE_RES), want)
+    for n in PC.SIZES:
+        one, distinct = PC.size_clouds(n)
+        assert np.array_equal(oracle.voxel_dedupe(one, 0.004), [0]) and PC.unique_first(one, 0.004).tolist() == [0], n
+        assert np.array_equal(oracle.voxel_dedupe(distinct, 0.004), np.arange(n)) and PC.unique_first(distinct, 0.004).size == n, n
+    for name, pc, res, finite in PC.refused_clouds():
+        msg = _refused_not_merged(oracle.voxel_dedupe, pc, res, finite, name)
+        assert "2^20" in msg, msg
+
+
+def test_knn_oracle_against_numpy_stable_argsort(oracle):
+    """orc_knn against float32 keys + stable argsort in numpy on the clouds the device tests use: 64 interleaved clusters (more
+    candidates than the search keeps in LDS at k = 60, none of them duplicates), a raster-ordered lattice full of exact ties, and
+    clouds as small as one point"""
+    import preproc_cases as PC
+    for name, pc, ks in (("clusters", PC.clusters_cloud(), (60, 16, 1)), ("lattice", PC.lattice_cloud(), (30,))):
+        for k in ks:
+            want, key = PC.knn_numpy(pc, k)
+            assert np.array_equal(oracle.knn(pc, k), want), (name, k)
+            n_cand = PC.knn_candidates(key, k)
+            if k == 60:       # the case is what it claims to be: every query is beyond the 512 candidate slots, none at k <= 16
+                assert n_cand.min() > 512, (name, k, n_cand.min())
+            elif k == 30:     # the lattice: ties on both sides of that threshold
+                assert n_cand.min() <= 512 < n_cand.max(), (name, k, n_cand.min(), n_cand.max())
+            else:
+                assert n_cand.max() <= 512, (name, k, n_cand.max())
+    for n, k in PC.SMALL_NK:
+        pc = PC.small_cloud(n)
+        assert np.array_equal(oracle.knn(pc, k), PC.knn_numpy(pc, k)[0]), (n, k)
+
+
+def test_normals_oracle_every_point_against_eigh(oracle):
+    """orc_estimate_normals against np.linalg.eigh of the two-pass fp64 covariance, EVERY point, measured as s = |n x e| (an angle
+    from arccos(|n . e|) cannot go below ~3e-4 rad for fp32 output) within the per-point bound of preproc_cases.normal_errors:
+    planes at the origin, off it, in millimetres and at offsets where only fp64 cumulants survive, a depth-quantised camera surface,
+    a sphere, a crease, a solid, k = 3 / 4 / 64; unit length, sign and finiteness always; k = 1, k = 2, a line, 100 copies of a point."""
+    import preproc_cases as PC
+    for name, pc, k, surface in PC.normal_clouds():
+        nb = PC.knn_numpy(pc, k)[0]
+        PC.check_normals(oracle.estimate_normals(pc, nb), pc, nb, surface, name)
+    # the sign tie: both largest components equal -> (+, +, 0)
+    pc = PC.tie_plane_cloud()
+    nr = oracle.estimate_normals(pc, PC.knn_numpy(pc, 30)[0])
+    r = np.float32(np.sqrt(0.5))
+    assert np.all(np.abs(nr - np.array([r, r, 0], np.float32)) <= 2.0 ** -23) and (nr[:, :2] > 0).all()
+    # no normal to compare: orthogonal to the segment (k = 2) and to the line (k = 10); k = 1 and copies of one point: a finite unit vector
+    for pc, k in ((PC.small_cloud(300), 2), (PC.line_cloud(), 10)):
+        nb = PC.knn_numpy(pc, k)[0]
+        nr = oracle.estimate_normals(pc, nb).astype(np.float64)
+        d = pc[nb[:, -1]].astype(np.float64) - pc[nb[:, 0]].astype(np.float64)
+        d /= np.linalg.norm(d, axis=1, keepdims=True)
+        assert np.abs((nr * d).sum(1)).max() <= 2.0 ** -23, k
+        assert np.abs(np.linalg.norm(nr, axis=1) - 1).max() <= 2.0 ** -23
+    for pc, k in ((PC.small_cloud(100), 1), (np.repeat(PC.small_cloud(1), 100, 0), 30)):
+        nr = oracle.estimate_normals(pc, PC.knn_numpy(pc, k)[0]).astype(np.float64)
+        assert np.isfinite(nr).all() and np.abs(np.linalg.norm(nr, axis=1) - 1).max() <= 2.0 ** -23
 
 
 def test_point_encoder_backward_oracle_matches_reference_autograd(oracle, golden):
