@@ -61,6 +61,14 @@ _SIGS = {
     "cppf_pair_mlp_batch_plan": (C.c_int, [i32, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "cppf_pair_mlp_decode_sel": (C.c_int, [vp, vp, vp, vp, i32, vp, i64, i32, C.POINTER(C.c_int), i32, i64, i32, i32, i32, vp, vp, vp,
                                            i64, vp, vp, sz, vp]),
+    # bf16 pair encoder (csrc/pair_mlp_bf16.hip): images in bytes, one list = the batch of one
+    "cppf_pair_mlp_bf16_packed_bytes": (sz, [i32, C.POINTER(C.c_int), i32, i32]),
+    "cppf_pair_mlp_bf16_pack": (C.c_int, [vp, vp, i32, C.POINTER(C.c_int), i32, i32, vp]),
+    "cppf_pair_mlp_bf16_pack_device": (C.c_int, [vp, C.POINTER(C.c_int64), i32, C.POINTER(C.c_int), i32, i32, vp, vp]),
+    "cppf_pair_mlp_bf16_forward": (C.c_int, [vp, vp, vp, vp, i32, vp, i64, i32, C.POINTER(C.c_int), i32, i64, i32, vp, vp,
+                                             sz, vp]),
+    "cppf_pair_mlp_bf16_decode_batch": (C.c_int, [i32, vp, i32, C.POINTER(C.c_int), i32, i32, i32, i32, vp]),
+    "cppf_pair_mlp_bf16_decode_sel_batch": (C.c_int, [i32, vp, i32, C.POINTER(C.c_int), i32, i32, i32, i32, vp]),
     "cppf_decode_center": (C.c_int, [vp, i64, i32, i32, f32, f32, vp, vp, vp]),
     "cppf_decode_rot": (C.c_int, [vp, i64, i32, i32, i32, i32, vp, vp, vp]),
     "cppf_reduce_workspace_bytes": (sz, []),

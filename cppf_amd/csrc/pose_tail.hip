@@ -1290,7 +1290,7 @@ extern "C" int cppf_pose_tail_batch(int n_items, const CppfPoseTailItem* items, 
     B.n = n_items; B.n_rots = n_rots; B.n_sphere = n_sphere; B.descending = sphere_sorted_by_y > 0 ? 1 : 0;
     B.max_rot_pairs = max_rot_pairs; B.sphere32 = sphere32; B.thr = thr;
     CppfPairMlpItem sel_items[TAIL_BATCH_MAX];
-    int n_second = 0, max_dirs = 1;
+    int n_second = 0, second_kind = 0, max_dirs = 1;
     int64_t bv_blocks = 1, cmp_blocks = 1, rot_blocks = 1;
     for (int i = 0; i < n_items; ++i) {
         const CppfPoseTailItem& it = items[i];
@@ -1330,6 +1330,9 @@ extern "C" int cppf_pose_tail_batch(int n_items, const CppfPoseTailItem* items, 
         rot_blocks = nb > rot_blocks ? nb : rot_blocks;
         max_dirs = it.n_dirs > max_dirs ? it.n_dirs : max_dirs;
         if (it.second_pass) {
+            const int kind = it.second_pass == 2 ? 2 : 1;   // 2: the item's image is a bf16 one (cppf_pair_mlp_bf16_pack*)
+            if (second_kind != 0 && second_kind != kind) return CPPF_EINVAL;   // one launch, one precision
+            second_kind = kind;
             if (!it.feat || !it.packed || !it.u_rot || !it.mlp_workspace) return CPPF_EINVAL;
             CppfPairMlpItem& M = sel_items[n_second++];
             M = CppfPairMlpItem{};
@@ -1352,7 +1355,8 @@ extern "C" int cppf_pose_tail_batch(int n_items, const CppfPoseTailItem* items, 
     CPPF_CHECK_LAUNCH();
     // 4. second MLP pass on the survivors (:236-256) for the items in their split form
     if (n_second > 0) {
-        const int rc = cppf_pair_mlp_decode_sel_batch(n_second, sel_items, F, dims, n_res, out_dim, tr_bins, rot_bins, stream);
+        const int rc = second_kind == 2 ? cppf_pair_mlp_bf16_decode_sel_batch(n_second, sel_items, F, dims, n_res, out_dim, tr_bins, rot_bins, stream)
+                                        : cppf_pair_mlp_decode_sel_batch(n_second, sel_items, F, dims, n_res, out_dim, tr_bins, rot_bins, stream);
         if (rc != 0) return rc;
     }
     // 5. orientation vote + sphere-bin count (:259-284), both directions

@@ -202,7 +202,13 @@ class _GraphCache:
             entry = None
             if self.use_graph and not eager:
                 entry = self.entries.get(form)
-                key = (self._images(members, check_weights, entry), extra)
+                # the pair encoders' precision is part of the key whatever `check_weights` says (another kernel, another image): after
+                # a switch the entry is dropped before the images are looked at, so the new key holds the new precision's addresses
+                precision = tuple(p.encoder.precision for p in members)
+                if entry is not None and entry[1][2] != precision:
+                    self.entries.pop(form, None)
+                    entry = None
+                key = (self._images(members, check_weights, entry), extra, precision)
                 if entry is None or entry[1] != key:
                     self.entries.pop(form, None)
                     entry = None                          # (a stale graph's memory goes before the new one's is taken)
@@ -429,9 +435,10 @@ class CenterPipeline(_Captured):
         """the addresses of the weight images as they are NOW, without looking at the parameters (a caller that has just refreshed
         the images of its encoders -- BatchPoseRunner, once per batch -- only needs to know whether an image MOVED since capture)"""
         enc, penc = self.encoder, self.point_encoder
-        if enc._packed is None or (penc is not None and getattr(penc, "_packed", None) is None):
+        image = enc._current_image()               # (of the encoder's current precision: each keeps its own buffer)
+        if image is None or (penc is not None and getattr(penc, "_packed", None) is None):
             return self._weight_images()
-        return (enc._packed.data_ptr(),) if penc is None else (enc._packed.data_ptr(), penc._packed[0].data_ptr())
+        return (image.data_ptr(),) if penc is None else (image.data_ptr(), penc._packed[0].data_ptr())
 
     def run(self, check_weights=True):
         """check_weights: how far the encoders' weight images are looked at before the run (_GraphCache._images)"""
@@ -893,7 +900,7 @@ class PoseChain(_Captured):
                  mask=ws.mask, chunk_counts=ws.chunk_counts, surv=ws.surv, count=ws.count, counts=ws.counts, best_idx=ws.best_idx,
                  ticket=ws.ticket, sums_workspace=scratch(pws), n_points=p.pc.shape[0], n_pairs=p.idx.shape[0], res64=float(p.cfg.res),
                  res=float(p.cfg.res), tol=float(np.float32(3 * p.cfg.res)), gx=gx, gy=gy, gz=gz, n_dirs=2 if p.cfg.regress_right else 1,
-                 second_pass=not self.full_first)
+                 second_pass=0 if self.full_first else (2 if p.encoder.precision == "bf16" else 1))
             if self.staged:                      # the finished record, assembled by the last launch (:299-339)
                 fill(arr[i], self.device, record_out=self.records[i], object_id_dev=self.desc[i].data_ptr() + 40,
                      scale_mean=(C.c_double * 3)(*[float(v) for v in p.cfg.scale_mean]), regress_right=bool(p.cfg.regress_right))

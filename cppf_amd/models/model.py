@@ -477,8 +477,39 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         self.final = nn.Linear(self.ppffcs[-1], self.out_dim)
         self._packed = None
         self._packed_key = None
+        self._packed_bf16 = None
+        self._packed_bf16_key = None
         self._flat = None
         self._flat_key = None
+
+    # ------------------------------------------------------------------ precision (this package)
+    @property
+    def precision(self):
+        """"fp32" (the default: bit for bit the oracle's arithmetic) or "bf16" (set_precision)"""
+        return self.__dict__.get("_cppf_precision", "fp32")
+
+    def set_precision(self, precision):
+        """Choose the arithmetic of the inference kernels.  "fp32": csrc/pair_mlp.hip, exact fp32 MFMAs.  "bf16":
+        csrc/pair_mlp_bf16.hip -- layer 0 in fp32 as before, every later layer as bf16 x bf16 products accumulated in fp32, fp32
+        logits and the unchanged fp32 decode (DESIGN.md "bf16 pair encoder").  bf16 is inference only (the backward stays fp32: a
+        bf16 encoder asked for gradients raises CppfError) and serves the standard architecture only (no fall-back to fp32).
+        Each precision keeps its own weight image; captured pipelines capture again after a switch.  Returns self."""
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
+        if precision == "bf16" and not (self.ppffcs == [84, 32, 32, 16] and 1 <= self.out_dim <= 144):
+            raise _lib.CppfError(f"no bf16 kernel for ppffcs={self.ppffcs}, out_dim={self.out_dim}: csrc/pair_mlp_bf16.hip covers "
+                                 "ppffcs=[84,32,32,16], out_dim<=144 (train.py:35); there is no fall-back to fp32")
+        self.__dict__["_cppf_precision"] = precision
+        return self
+
+    def _current_image(self):
+        """the cached weight image of the current precision as it is now (None before its first pack)"""
+        return self._packed_bf16 if self.precision == "bf16" else self._packed
+
+    def _refuse_gradients(self, feat):
+        if torch.is_grad_enabled() and (self.training or feat.requires_grad):
+            raise _lib.CppfError("PPFEncoder with precision 'bf16' is inference only (the backward kernels are fp32): call it in eval "
+                                 "mode on inputs that need no gradient, or set_precision('fp32') to train")
 
     # ------------------------------------------------------------------ reference signatures
     def forward(self, pc, pc_normal, feat, dist=None, idxs=None):
@@ -495,6 +526,10 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         return self.forward_with_idx(pc[0], pc_normal[0], feat[0], allp).reshape(1, n, n, self.out_dim)
 
     def forward_with_idx(self, pc, pc_normal, feat, idxs):
+        if self.precision == "bf16":
+            self._refuse_gradients(feat)
+            with torch.no_grad():
+                return self._forward_device(pc, pc_normal, feat, self._as_index_tensor(idxs, self._device_of(pc)))
         if self._needs_graph(feat) and not self._has_device_backward(pc, feat):      # torch ops: wherever the tensors are
             return self._composite(pc, pc_normal, feat, self._as_index_tensor(idxs, pc.device))
         idxs = self._as_index_tensor(idxs, self._device_of(pc))
@@ -508,6 +543,10 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         out = torch.empty((P, self.out_dim), dtype=torch.float32, device=pc.device)
         dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
         ws = self._scratch(pc, feat, dims)
+        if self.precision == "bf16":
+            call("cppf_pair_mlp_bf16_forward", pc.device, pc, pc_normal, feat, idxs, idxs.dtype == torch.int64,
+                 self._packed_weights(pc.device), pc.shape[0], feat.shape[1], dims, len(self.ppffcs) - 1, P, self.out_dim, out, scratch(ws))
+            return out
         call("cppf_pair_mlp_forward", pc.device, pc, pc_normal, feat, idxs, idxs.dtype == torch.int64, self._packed_weights(pc.device),
              pc.shape[0], feat.shape[1], dims, len(self.ppffcs) - 1, P, self.out_dim, out, scratch(ws))
         return out
@@ -528,11 +567,20 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         heads = torch.empty((P, 8), dtype=torch.float32, device=pc.device) if u_rot is not None else None
         dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
         ws = self._scratch(pc, feat, dims)
-        rc = call("cppf_pair_mlp_decode", pc.device, pc, pc_normal, feat, idxs, idxs.dtype == torch.int64, self._packed_weights(pc.device),
-                  pc.shape[0], feat.shape[1], dims, len(self.ppffcs) - 1, P, self.out_dim, tr_num_bins, rot_num_bins,
-                  float(vote_range[0]), float(vote_range[1]), u_tr, u_rot, outputs, heads, scratch(ws), ok=(_lib.EUNSUPPORTED,))
-        if rc == _lib.EUNSUPPORTED:  # architecture / bin counts outside the fused kernel: logits + decode kernels
-            logits = self.forward_with_idx(pc, pc_normal, feat, idxs)
+        if self.precision == "bf16":             # one list = the batch of one (no per-variant single entry points)
+            item = fill(_lib.PairMlpItem(), pc.device, pc=pc, nrm=pc_normal, feat=feat, idxs=idxs, packed=self._packed_weights(pc.device),
+                        u_tr=u_tr, u_rot=u_rot, outputs=outputs, heads=heads, workspace=scratch(ws), n_points=pc.shape[0], n_pairs=P,
+                        vr0=float(vote_range[0]), vr1=float(vote_range[1]), idx_is_i64=idxs.dtype == torch.int64)
+            rc = call("cppf_pair_mlp_bf16_decode_batch", pc.device, 1, C.byref(item), feat.shape[1], dims, len(self.ppffcs) - 1,
+                      self.out_dim, tr_num_bins, rot_num_bins, ok=(_lib.EUNSUPPORTED,))
+        else:
+            rc = call("cppf_pair_mlp_decode", pc.device, pc, pc_normal, feat, idxs, idxs.dtype == torch.int64, self._packed_weights(pc.device),
+                      pc.shape[0], feat.shape[1], dims, len(self.ppffcs) - 1, P, self.out_dim, tr_num_bins, rot_num_bins,
+                      float(vote_range[0]), float(vote_range[1]), u_tr, u_rot, outputs, heads, scratch(ws), ok=(_lib.EUNSUPPORTED,))
+        if rc == _lib.EUNSUPPORTED:  # architecture / bin counts outside the fused kernel: logits (of the same precision) + decode kernels
+            with torch.no_grad():
+                logits = self._forward_device(pc, pc_normal, feat, idxs) if self.precision == "bf16" else \
+                    self.forward_with_idx(pc, pc_normal, feat, idxs)
             call("cppf_decode_center", pc.device, logits, P, self.out_dim, tr_num_bins, float(vote_range[0]), float(vote_range[1]), u_tr,
                  outputs)
             if heads is not None:
@@ -564,9 +612,16 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         max_sel = P if max_sel is None else min(int(max_sel), P)
         dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
         ws = self._scratch(pc, feat, dims)
-        rc = call("cppf_pair_mlp_decode_sel", pc.device, pc, pc_normal, feat, idxs, idxs.dtype == torch.int64,
-                  self._packed_weights(pc.device), pc.shape[0], feat.shape[1], dims, len(self.ppffcs) - 1, P, self.out_dim, tr_num_bins,
-                  rot_num_bins, u_rot, sel, n_sel, max_sel, heads, scratch(ws), ok=(_lib.EUNSUPPORTED,))
+        if self.precision == "bf16":
+            item = fill(_lib.PairMlpItem(), pc.device, pc=pc, nrm=pc_normal, feat=feat, idxs=idxs, packed=self._packed_weights(pc.device),
+                        u_rot=u_rot, heads=heads, workspace=scratch(ws), n_points=pc.shape[0], n_pairs=P,
+                        idx_is_i64=idxs.dtype == torch.int64, sel=sel, n_sel_dev=n_sel, max_sel=max_sel)
+            rc = call("cppf_pair_mlp_bf16_decode_sel_batch", pc.device, 1, C.byref(item), feat.shape[1], dims, len(self.ppffcs) - 1,
+                      self.out_dim, tr_num_bins, rot_num_bins, ok=(_lib.EUNSUPPORTED,))
+        else:
+            rc = call("cppf_pair_mlp_decode_sel", pc.device, pc, pc_normal, feat, idxs, idxs.dtype == torch.int64,
+                      self._packed_weights(pc.device), pc.shape[0], feat.shape[1], dims, len(self.ppffcs) - 1, P, self.out_dim, tr_num_bins,
+                      rot_num_bins, u_rot, sel, n_sel, max_sel, heads, scratch(ws), ok=(_lib.EUNSUPPORTED,))
         if rc == _lib.EUNSUPPORTED:
             # architecture / bin counts outside the fused kernel: the logits of the selected pairs + cppf_decode_rot, rows
             # scattered back.  The count is read on the host (one sync; not capturable -- the pose pipelines run such
@@ -695,7 +750,9 @@ class PPFEncoder(_DeviceWeights, nn.Module):
     def _packed_weights(self, device):
         """Lane-ordered weight image for the HIP kernels, rebuilt when a parameter changes.  The standard architecture
         packs on the device (cppf_pair_mlp_pack_device: a training loop changes the weights every step and never
-        leaves the stream); other stacks pack on the host."""
+        leaves the stream); other stacks pack on the host.  Under precision "bf16": the bf16 image (its own buffer and key)."""
+        if self.precision == "bf16":
+            return self._packed_weights_bf16(device)
         key = self._param_key(device)
         if self._packed is not None and self._packed_key == key:
             return self._packed
@@ -732,6 +789,37 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         if dev.type == "cuda":
             self._image_rebuilt(dev)
         return self._packed
+
+    def _packed_weights_bf16(self, device):
+        """_packed_weights for the bf16 image (cppf_pair_mlp_bf16_pack_device on a HIP device, the host pack elsewhere): an
+        int32 tensor of cppf_pair_mlp_bf16_packed_bytes() / 4 words, rebuilt in place when a parameter changes, with the same ordering
+        against readers on other streams as the fp32 image"""
+        key = self._param_key(device)
+        if self._packed_bf16 is not None and self._packed_bf16_key == key:
+            return self._packed_bf16
+        dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
+        F_, n_res = (self.ppffcs[0] - 4) // 2, len(self.ppffcs) - 1
+        n = int(_lib.lib().cppf_pair_mlp_bf16_packed_bytes(F_, dims, n_res, self.out_dim)) // 4
+        if n == 0:
+            raise _lib.CppfError(f"no bf16 kernel for ppffcs={self.ppffcs}, out_dim={self.out_dim} (there is no fall-back to fp32)")
+        dev = torch.device(device)
+        old = self._packed_bf16 if self._packed_bf16 is not None and self._packed_bf16.device == dev and self._packed_bf16.numel() == n else None
+        if dev.type == "cuda":
+            flat, offs_c = self._flat_params(dev)
+            packed = old if old is not None else torch.empty(n, dtype=torch.int32, device=dev)
+            if old is not None:
+                self._image_rebuild_begins(dev)
+            call("cppf_pair_mlp_bf16_pack_device", dev, flat, offs_c, F_, dims, n_res, self.out_dim, packed)
+        else:
+            sd = {k: v.detach().float().cpu().numpy() for k, v in self.state_dict().items()}
+            params, offs = flatten_state_dict(sd, self.ppffcs)
+            image = np.zeros(n, np.int32)
+            call("cppf_pair_mlp_bf16_pack", None, params, offs, F_, dims, n_res, self.out_dim, image)
+            packed = torch.from_numpy(image)
+        self._packed_bf16, self._packed_bf16_key = packed, key
+        if dev.type == "cuda":
+            self._image_rebuilt(dev)
+        return packed
 
 
 def flatten_state_dict(sd, ppffcs):
@@ -781,6 +869,9 @@ def forward_decode_batch(items, tr_num_bins=32, rot_num_bins=36, tables_out=None
         enc = it["encoder"]
         if enc.ppffcs != enc0.ppffcs or enc.out_dim != enc0.out_dim:
             raise ValueError("the encoders of one launch must share an architecture")
+        if enc.precision != enc0.precision:
+            raise _lib.CppfError(f"the encoders of one launch must share a precision: item 0 is {enc0.precision!r}, item {i} is "
+                                 f"{enc.precision!r} (PPFEncoder.set_precision)")
         idxs = enc._as_index_tensor(it["idxs"], dev)
         pc, nrm, feat = enc._check_inputs(it["pc"], it["pc_normal"], it["feat"])
         if pc.device != dev:
@@ -799,7 +890,7 @@ def forward_decode_batch(items, tr_num_bins=32, rot_num_bins=36, tables_out=None
              idx_is_i64=idxs.dtype == torch.int64)
         keep.append((idxs, pc, nrm, feat, ws, packed, u_tr, u_rot))
         outs.append((outputs, heads))
-    call("cppf_pair_mlp_decode_batch", dev, len(items), arr, items[0]["feat"].shape[1], dims, len(enc0.ppffcs) - 1, enc0.out_dim,
+    call("cppf_pair_mlp_bf16_decode_batch" if enc0.precision == "bf16" else "cppf_pair_mlp_decode_batch", dev, len(items), arr, items[0]["feat"].shape[1], dims, len(enc0.ppffcs) - 1, enc0.out_dim,
          tr_num_bins, rot_num_bins)
     if tables_out is not None:      # the per-point tables this pass left (a batched second pass reuses them: cppf_pose_tail_batch)
         tables_out[:] = [k[4] for k in keep]

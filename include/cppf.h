@@ -164,6 +164,8 @@ int cppf_counts_argmax_select(const int32_t* counts, int n, const double* sphere
  *   counts   device i32[2][n_sphere] (inside tail0); chunk_counts i32[ceil(n_pairs / 1024)] (inside tail0); ticket u32 (inside tail0)
  *   heads    device f32[n_pairs,8]: rows of the survivors are written by launch 4 (second_pass = 1), or hold every pair's heads
  *            from an all-heads first pass (second_pass = 0)
+ *            second_pass = 2: second pass on a bf16 image (`packed` from cppf_pair_mlp_bf16_pack*, launch 4 =
+ *            cppf_pair_mlp_bf16_decode_sel_batch); a batch that mixes 1 and 2 is CPPF_EINVAL
  *   mlp_workspace  the per-point table the first pass (cppf_pair_mlp_decode / _batch) left for this object
  * Common to the batch: the pair-encoder architecture (standard fused one only), n_rots, the sphere bins (unit vectors with a monotone y
  * column: fibonacci_sphere; sphere_sorted_by_y = +1 descending / -1 ascending), thr = cos(angle_tol), max_rot_pairs (:277-280). */
@@ -453,6 +455,36 @@ int cppf_pair_mlp_decode_sel(const float* pc, const float* nrm, const float* fea
                              const float* packed, int64_t N, int F, const int* dims, int n_res, int64_t P, int out_dim,
                              int tr_bins, int rot_bins, const float* u_rot, const int32_t* sel, const int32_t* n_sel_dev,
                              int64_t max_sel, float* heads, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * bf16 pair encoder (opt-in; additive, ABI version unchanged).  The same kernel structure with the hidden layers on
+ * v_mfma_f32_16x16x32_bf16 / _16x16x16_bf16: layer 0 (per-point tables, PPF inputs) stays fp32 exactly as above; after it every
+ * product is bf16 x bf16 -- weights rounded to nearest even once by the packer, activations as they enter a layer -- and every
+ * accumulation, bias and residual add is fp32 (the residual of layer 1 is the unrounded fp32 value).  Logits are fp32 and the decode
+ * is the fp32 entry points' own arithmetic on them.  DESIGN.md "bf16 pair encoder" states the numerics; results are deterministic but
+ * NOT those of the fp32 entry points.  Standard architecture only (dims = {84, 32, 32, 16}, F = 40, out_dim <= 144): anything else is
+ * CPPF_EUNSUPPORTED -- there is no generic bf16 kernel and no fall-back to fp32.
+ *   cppf_pair_mlp_bf16_packed_bytes   size of the weight image in BYTES (0: architecture not served)
+ *   cppf_pair_mlp_bf16_pack / _pack_device   params / offs as cppf_pair_mlp_pack / cppf_pair_mlp_pack_device; the image holds bf16
+ *                                     weights for every layer after layer 0, the layer-0 section and all biases in fp32
+ *   cppf_pair_mlp_bf16_forward        logits f32[P,out_dim], any out_dim <= 144; workspace as cppf_pair_mlp_workspace_bytes()
+ *   cppf_pair_mlp_bf16_decode_batch / _decode_sel_batch   cppf_pair_mlp_decode_batch / _decode_sel_batch with item.packed pointing at a
+ *                                     bf16 image: up to 8 lists, the geometry of cppf_pair_mlp_batch_plan, CPPF_EUNSUPPORTED for other
+ *                                     architectures and bin counts, CPPF_EWORKSPACE for a short workspace; a list with n_pairs == 0 is
+ *                                     skipped; the sel pass reuses the table its first pass left.  One list is the batch of one.
+ * ------------------------------------------------------------------------------------------- */
+size_t cppf_pair_mlp_bf16_packed_bytes(int F, const int* dims, int n_res, int out_dim);
+int cppf_pair_mlp_bf16_pack(const float* params, const int64_t* offs, int F, const int* dims, int n_res, int out_dim,
+                            void* packed_host);
+int cppf_pair_mlp_bf16_pack_device(const float* params, const int64_t* offs, int F, const int* dims, int n_res, int out_dim,
+                                   void* packed_device, void* stream);
+int cppf_pair_mlp_bf16_forward(const float* pc, const float* nrm, const float* feat, const void* idxs, int idx_is_i64,
+                               const void* packed, int64_t N, int F, const int* dims, int n_res, int64_t P, int out_dim,
+                               float* out, void* workspace, size_t workspace_bytes, void* stream);
+int cppf_pair_mlp_bf16_decode_batch(int n_items, const CppfPairMlpItem* items_host, int F, const int* dims, int n_res, int out_dim,
+                                    int tr_bins, int rot_bins, void* stream);
+int cppf_pair_mlp_bf16_decode_sel_batch(int n_items, const CppfPairMlpItem* items_host, int F, const int* dims, int n_res, int out_dim,
+                                        int tr_bins, int rot_bins, void* stream);
 
 #ifdef CPPF_DEBUG_ENTRY
 /* Profiling aid, compiled only with -DCPPF_DEBUG_ENTRY (not in the shipped library): the PPF + gather + MFMA chain of the
