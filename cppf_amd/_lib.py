@@ -69,6 +69,15 @@ _SIGS = {
                                              sz, vp]),
     "cppf_pair_mlp_bf16_decode_batch": (C.c_int, [i32, vp, i32, C.POINTER(C.c_int), i32, i32, i32, i32, vp]),
     "cppf_pair_mlp_bf16_decode_sel_batch": (C.c_int, [i32, vp, i32, C.POINTER(C.c_int), i32, i32, i32, i32, vp]),
+    # bf16 point encoder (csrc/sprin_bf16.hip): image in bytes, the other arguments as the fp32 entries'
+    "cppf_point_encoder_bf16_packed_bytes": (sz, [C.POINTER(C.c_int), i32, i32, i32, i32, i32, i32]),
+    "cppf_point_encoder_bf16_pack": (C.c_int, [vp, C.POINTER(C.c_int), i32, i32, i32, i32, i32, i32, vp]),
+    "cppf_point_encoder_bf16_pack_device": (C.c_int, [vp, C.POINTER(C.c_int), i32, i32, i32, i32, i32, i32, vp, vp]),
+    "cppf_point_encoder_bf16_forward": (C.c_int, [vp, vp, vp, i32, i32, vp, C.POINTER(C.c_int), i32, i32, i32, i32, i32, i32,
+                                                  vp, vp, sz, vp]),
+    "cppf_point_encoder_bf16_forward_dyn": (C.c_int, [vp, vp, vp, i32, vp, i32, vp, C.POINTER(C.c_int), i32, i32, i32, i32, i32, i32,
+                                                      vp, vp, sz, vp]),
+    "cppf_point_encoder_bf16_forward_batch": (C.c_int, [i32, vp, i32, C.POINTER(C.c_int), i32, i32, i32, i32, i32, i32, vp]),
     "cppf_decode_center": (C.c_int, [vp, i64, i32, i32, f32, f32, vp, vp, vp]),
     "cppf_decode_rot": (C.c_int, [vp, i64, i32, i32, i32, i32, vp, vp, vp]),
     "cppf_reduce_workspace_bytes": (sz, []),

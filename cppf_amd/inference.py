@@ -202,9 +202,10 @@ class _GraphCache:
             entry = None
             if self.use_graph and not eager:
                 entry = self.entries.get(form)
-                # the pair encoders' precision is part of the key whatever `check_weights` says (another kernel, another image): after
+                # the pair and point encoders' precision is part of the key whatever `check_weights` says (another kernel, another image): after
                 # a switch the entry is dropped before the images are looked at, so the new key holds the new precision's addresses
-                precision = tuple(p.encoder.precision for p in members)
+                precision = tuple((p.encoder.precision, None if p.point_encoder is None else p.point_encoder.precision)
+                                  for p in members)
                 if entry is not None and entry[1][2] != precision:
                     self.entries.pop(form, None)
                     entry = None
@@ -436,9 +437,10 @@ class CenterPipeline(_Captured):
         the images of its encoders -- BatchPoseRunner, once per batch -- only needs to know whether an image MOVED since capture)"""
         enc, penc = self.encoder, self.point_encoder
         image = enc._current_image()               # (of the encoder's current precision: each keeps its own buffer)
-        if image is None or (penc is not None and getattr(penc, "_packed", None) is None):
+        pimage = None if penc is None else penc._current_image()
+        if image is None or (penc is not None and pimage is None):
             return self._weight_images()
-        return (image.data_ptr(),) if penc is None else (image.data_ptr(), penc._packed[0].data_ptr())
+        return (image.data_ptr(),) if penc is None else (image.data_ptr(), pimage[0].data_ptr())
 
     def run(self, check_weights=True):
         """check_weights: how far the encoders' weight images are looked at before the run (_GraphCache._images)"""

@@ -237,9 +237,58 @@ class PointEncoder(_DeviceWeights, nn.Module):
             self.aggrs.append(GlobalInfoProp(out_dim, out_dim // 4))
         self._packed = None
         self._packed_key = None
+        self._packed_bf16 = None
+        self._packed_bf16_key = None
+
+    # ------------------------------------------------------------------ precision (this package)
+    @property
+    def precision(self):
+        """"fp32" (the default: bit for bit the oracle's arithmetic) or "bf16" (set_precision)"""
+        return self.__dict__.get("_cppf_precision", "fp32")
+
+    def set_precision(self, precision):
+        """Choose the arithmetic of the inference kernels.  "fp32": csrc/sprin.hip, exact fp32 MFMAs.  "bf16": csrc/sprin_bf16.hip --
+        gather, rifeat, layer 1 of the kernel-MLP and every LayerNorm in fp32 as before, layers 2..5 as bf16 x bf16 products
+        accumulated in fp32; the contraction, the outnet and GlobalInfoProp are the fp32 code.  bf16 is inference
+        only (the backward stays fp32: a bf16 encoder asked for gradients raises CppfError) and serves the architecture the fp32
+        kernel serves (no fall-back to fp32).  Each precision keeps its own weight image; captured pipelines capture again after a
+        switch.  Returns self."""
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
+        if precision == "bf16" and not self._std_shape():
+            raise _lib.CppfError(f"no bf16 kernel for PointEncoder(k={self.k}, spfcs={self.spfcs}, out_dim={self.out_dim}, "
+                                 f"num_nbr_feats={self.num_nbr_feats}): csrc/sprin_bf16.hip covers spfcs=[32,64,32,32], out_dim=32, "
+                                 "num_nbr_feats=2, k<=64 (train.py:34); there is no fall-back to fp32")
+        self.__dict__["_cppf_precision"] = precision
+        return self
+
+    def _std_shape(self):
+        return (self.spfcs == [32, 64, 32, 32] and self.out_dim == 32 and self.num_nbr_feats == 2 and self.k <= 64
+                and all(sc.layer_norm is not None for sc in self.spconvs))
+
+    def _current_image(self):
+        """the cached (image, desc) of the current precision as it is now (None before its first pack)"""
+        return self._packed_bf16 if self.precision == "bf16" else self._packed
+
+    def _entry(self, name):
+        """the C entry point of the current precision: cppf_point_encoder_<name> or cppf_point_encoder_bf16_<name>"""
+        return f"cppf_point_encoder_bf16_{name}" if self.precision == "bf16" else f"cppf_point_encoder_{name}"
+
+    def _refuse_gradients(self, *inputs):
+        if torch.is_grad_enabled() and (self.training or any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs)
+                                        or any(p.requires_grad for p in _params_of(self))):
+            raise _lib.CppfError("PointEncoder with precision 'bf16' is inference only (the backward kernels are fp32): call it in "
+                                 "eval mode under torch.no_grad() (or with parameters and inputs that need no gradient), or "
+                                 "set_precision('fp32') to train")
 
     # ------------------------------------------------------------------ reference signatures
     def forward(self, pc, pc_normal, dist=None):
+        if self.precision == "bf16":
+            self._refuse_gradients(pc, pc_normal)
+            with torch.no_grad():
+                pc2, nrm2 = self._check_inputs(pc, pc_normal)
+                d2 = None if dist is None else self._check_dist(dist, pc2)
+                return self._forward_device(pc2, nrm2, self.neighbours(pc2, d2)).reshape(*pc.shape[:-1], -1)
         if self._needs_graph(pc):
             if self._has_device_backward(pc, pc_normal):
                 pc2, nrm2 = self._check_inputs(pc, pc_normal)
@@ -256,6 +305,11 @@ class PointEncoder(_DeviceWeights, nn.Module):
         return self._forward_device(pc2, nrm2, self.neighbours(pc2, dist)).reshape(*pc.shape[:-1], -1)
 
     def forward_nbrs(self, pc, pc_normal, nbrs_idx):
+        if self.precision == "bf16":
+            self._refuse_gradients(pc, pc_normal)
+            with torch.no_grad():
+                pc2, nrm2 = self._check_inputs(pc, pc_normal)
+                return self._forward_device(pc2, nrm2, self._check_nbrs(nbrs_idx, pc2)).reshape(*pc.shape[:-1], -1)
         if self._needs_graph(pc):
             if self._has_device_backward(pc, pc_normal):
                 pc2, nrm2 = self._check_inputs(pc, pc_normal)
@@ -289,13 +343,14 @@ class PointEncoder(_DeviceWeights, nn.Module):
                        "point_encoder")
         args = (pc, nrm, nbrs, N, k, packed, hid, len(desc["hidden"]), desc["rank"], desc["n_nbr_feats"], desc["n_out"], desc["n_glob"],
                 self.num_layers, out)
-        if keep_contraction is not None:   # training: the backward reuses the per-point contraction
+        if keep_contraction is not None:   # training (fp32 only): the backward reuses the per-point contraction
             rc = call("cppf_point_encoder_forward_train", pc.device, *args, keep_contraction, scratch(ws), ok=(_lib.EUNSUPPORTED,))
         else:
-            rc = call("cppf_point_encoder_forward", pc.device, *args, scratch(ws), ok=(_lib.EUNSUPPORTED,))
+            rc = call(self._entry("forward"), pc.device, *args, scratch(ws), ok=(_lib.EUNSUPPORTED,))
         if rc == _lib.EUNSUPPORTED:
-            raise _lib.CppfError(f"no device kernel for PointEncoder(k={self.k}, spfcs={self.spfcs}, out_dim={self.out_dim}): "
-                                 "csrc/sprin.hip covers spfcs=[32,64,32,32], out_dim=32, k<=64 (train.py:34)")
+            raise _lib.CppfError(f"no device kernel ({self.precision}) for PointEncoder(k={self.k}, spfcs={self.spfcs}, "
+                                 f"out_dim={self.out_dim}): csrc/sprin.hip and csrc/sprin_bf16.hip cover spfcs=[32,64,32,32], "
+                                 "out_dim=32, k<=64 (train.py:34)")
         return out
 
     # ------------------------------------------------------------------ internals
@@ -370,6 +425,10 @@ class PointEncoder(_DeviceWeights, nn.Module):
         return canon(dist, torch.float32, pc2.device, "dist").reshape(pc2.shape[0], pc2.shape[0])
 
     def _packed_weights(self, device):
+        """(weight image, desc) for the HIP kernels of the current precision, rebuilt when a parameter changes (each precision its
+        own buffer and key)"""
+        if self.precision == "bf16":
+            return self._packed_weights_bf16(device)
         key = self._param_key(device)
         if self._packed is not None and self._packed_key == key:
             return self._packed
@@ -410,6 +469,53 @@ class PointEncoder(_DeviceWeights, nn.Module):
             self._image_rebuilt(dev)
         return self._packed
 
+    def _packed_weights_bf16(self, device):
+        """_packed_weights for the bf16 image: an int32 tensor of cppf_point_encoder_bf16_packed_bytes() / 4 words (the natural
+        block verbatim, then per layer the fp32 layer 1, the bf16 layers 2..5 and the fp32 vectors), rebuilt in place when a
+        parameter changes, with the same ordering against readers on other streams as the fp32 image.  On a HIP device the
+        one-layer encoder packs there (cppf_point_encoder_bf16_pack_device); deeper ones and the host pack on the host."""
+        key = self._param_key(device)
+        if self._packed_bf16 is not None and self._packed_bf16_key == key:
+            return self._packed_bf16
+        if not self._std_shape():
+            raise _lib.CppfError(f"no bf16 kernel for PointEncoder(k={self.k}, spfcs={self.spfcs}, out_dim={self.out_dim}) "
+                                 "(there is no fall-back to fp32)")
+        dev = torch.device(device)
+        n_glob = self.out_dim // 4
+        desc = dict(hidden=list(self.spfcs), rank=32, n_nbr_feats=2, n_out=32, n_glob=n_glob, num_layers=self.num_layers)
+        hid = (C.c_int * 4)(*self.spfcs)
+        shape = (hid, 4, 32, 2, 32, n_glob, self.num_layers)
+        n = int(_lib.lib().cppf_point_encoder_bf16_packed_bytes(*shape)) // 4
+        if n == 0:
+            raise _lib.CppfError(f"no bf16 kernel for PointEncoder(spfcs={self.spfcs}, out_dim={self.out_dim}) (there is no fall-back "
+                                 "to fp32)")
+        old = self._packed_bf16[0] if self._packed_bf16 is not None else None
+        if old is not None and (old.device != dev or old.numel() != n):
+            old = None
+        if dev.type == "cuda" and self.num_layers == 1:
+            nat = torch.cat([(p.detach().t() if tr else p.detach()).reshape(-1).float()
+                             for p, tr in zip(self._ordered_params(), self._ordered_transposed())]).to(dev).contiguous()
+            packed = old if old is not None else torch.empty(n, dtype=torch.int32, device=dev)
+            if old is not None:
+                self._image_rebuild_begins(dev)
+            call("cppf_point_encoder_bf16_pack_device", dev, nat, *shape, packed)
+        else:
+            sd = {k: v.detach().float().cpu().numpy() for k, v in self.state_dict().items()}
+            natural, _ = pack_point_encoder(sd, self.num_layers)
+            image = np.zeros(n, np.int32)
+            call("cppf_point_encoder_bf16_pack", None, natural, *shape, image)
+            if old is not None:
+                packed = old
+                if dev.type == "cuda":
+                    self._image_rebuild_begins(dev)
+                packed.copy_(torch.from_numpy(image))
+            else:
+                packed = torch.from_numpy(image).to(dev)
+        self._packed_bf16, self._packed_bf16_key = (packed, desc), key
+        if dev.type == "cuda":
+            self._image_rebuilt(dev)
+        return self._packed_bf16
+
     def forward_dyn(self, pc, pc_normal, n_dev, out=None, nbrs=None, nbrs_ready=False):
         """Shape-polymorphic forward for captured chains (cppf_knn_dyn + cppf_point_encoder_forward_dyn): pc / pc_normal are
         capacity-sized f32[n_cap,3] device tensors, `n_dev` a device i32 tensor whose first element is the number of valid
@@ -417,6 +523,8 @@ class PointEncoder(_DeviceWeights, nn.Module):
         nbrs_ready: `nbrs` already holds the k-neighbour sets of the cloud (cppf_knn's output for the same k, e.g. left by
         cppf_frame_cloud_dyn, which fits the normals on them): the search is not repeated."""
         require_cuda()
+        if self.precision == "bf16":
+            self._refuse_gradients(pc, pc_normal)
         n_cap = pc.shape[0]
         packed, desc = self._packed_weights(pc.device)
         hid = (C.c_int * len(desc["hidden"]))(*desc["hidden"])
@@ -430,11 +538,12 @@ class PointEncoder(_DeviceWeights, nn.Module):
                        "point_encoder")
         if not nbrs_ready:
             call("cppf_knn_dyn", pc.device, pc, n_cap, n_dev, self.k, nbrs)
-        rc = call("cppf_point_encoder_forward_dyn", pc.device, pc, pc_normal, nbrs, n_cap, n_dev, self.k, packed, hid, len(desc["hidden"]),
+        rc = call(self._entry("forward_dyn"), pc.device, pc, pc_normal, nbrs, n_cap, n_dev, self.k, packed, hid, len(desc["hidden"]),
                   desc["rank"], desc["n_nbr_feats"], desc["n_out"], desc["n_glob"], self.num_layers, out, scratch(ws),
                   ok=(_lib.EUNSUPPORTED,))
         if rc == _lib.EUNSUPPORTED:
-            raise _lib.CppfError(f"no device kernel for PointEncoder(k={self.k}, spfcs={self.spfcs}, out_dim={self.out_dim})")
+            raise _lib.CppfError(f"no device kernel ({self.precision}) for PointEncoder(k={self.k}, spfcs={self.spfcs}, "
+                                 f"out_dim={self.out_dim})")
         return out
 
 
@@ -442,9 +551,17 @@ def point_encoder_forward_batch(members):
     """The point encoders of a chain's members in three launches (cppf_point_encoder_forward_batch) instead of three each.
     members: dicts(encoder, pc, nrm, n_dev, out, nbrs[, nbrs_ready]) as PointEncoder.forward_dyn takes them, 1..8 of them, encoders
     of the one-layer standard form with the same k (instances of different categories carry different weights).  -> [out per
-    member], bit-equal to forward_dyn member by member; None when the members do not qualify (the caller then loops forward_dyn)."""
+    member], bit-equal to forward_dyn member by member; None when the members do not qualify (the caller then loops forward_dyn).
+    The members share a precision (PointEncoder.set_precision): a mixed batch raises CppfError, and so does a bf16 batch the bf16
+    kernel does not serve (no fall-back to fp32)."""
     require_cuda()
     e0 = members[0]["encoder"]
+    for i, m in enumerate(members):
+        if m["encoder"].precision != e0.precision:
+            raise _lib.CppfError(f"the point encoders of one launch must share a precision: member 0 is {e0.precision!r}, member {i} "
+                                 f"is {m['encoder'].precision!r} (PointEncoder.set_precision)")
+        if e0.precision == "bf16":
+            m["encoder"]._refuse_gradients(m["pc"], m["nrm"])
     if not 1 <= len(members) <= 8 or any(m["encoder"].num_layers != 1 or m["encoder"].k != e0.k or m["encoder"].spfcs != e0.spfcs
                                          or m["encoder"].out_dim != e0.out_dim or m["encoder"].num_nbr_feats != e0.num_nbr_feats
                                          for m in members):
@@ -462,8 +579,11 @@ def point_encoder_forward_batch(members):
              n_cap=n_cap, nbrs_ready=bool(m.get("nbrs_ready")))
         keep.append((packed, ws))
     hid = (C.c_int * len(desc["hidden"]))(*desc["hidden"])
-    rc = call("cppf_point_encoder_forward_batch", dev, len(members), arr, e0.k, hid, len(desc["hidden"]), desc["rank"],
+    rc = call(e0._entry("forward_batch"), dev, len(members), arr, e0.k, hid, len(desc["hidden"]), desc["rank"],
               desc["n_nbr_feats"], desc["n_out"], desc["n_glob"], 1, ok=(_lib.EUNSUPPORTED,))
+    if rc == _lib.EUNSUPPORTED and e0.precision == "bf16":
+        raise _lib.CppfError(f"no bf16 device kernel for PointEncoder(k={e0.k}, spfcs={e0.spfcs}, out_dim={e0.out_dim}) (there is no "
+                             "fall-back to fp32)")
     return None if rc == _lib.EUNSUPPORTED else [m["out"] for m in members]
 
 

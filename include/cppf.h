@@ -486,6 +486,41 @@ int cppf_pair_mlp_bf16_decode_batch(int n_items, const CppfPairMlpItem* items_ho
 int cppf_pair_mlp_bf16_decode_sel_batch(int n_items, const CppfPairMlpItem* items_host, int F, const int* dims, int n_res, int out_dim,
                                         int tr_bins, int rot_bins, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * bf16 point encoder (opt-in; additive, ABI version unchanged).  The SPRIN convolution of cppf_point_encoder_forward with layers
+ * 2..5 of its per-neighbour kernel-MLP on v_mfma_f32_16x16x32_bf16: gather, rifeat and layer 1 (6 -> 32) stay fp32 exactly as above,
+ * the four LayerNorms stay fp32 on the fp32 accumulators; the input of every later layer is bf(relu(LayerNorm(.))), its weights are
+ * rounded to nearest even once by the packer, every product is bf16 x bf16 and every sum fp32 on the bias seed.  The last layer's
+ * output is fp32 and not rounded; the rank contraction, the outnet, its LayerNorm and GlobalInfoProp are the fp32 entry points' own
+ * arithmetic on it.  DESIGN.md 3.5a states the numerics; results are deterministic but NOT those of the fp32 entry points.
+ * Serves what the fp32 kernel serves (hidden = {32,64,32,32}, rank 32, n_out 32, n_nbr_feats 2, k <= 64, any num_layers; the batch
+ * entry one-layer encoders): anything else is CPPF_EUNSUPPORTED -- there is no generic bf16 kernel and no fall-back to fp32.
+ *   cppf_point_encoder_bf16_packed_bytes   size of the weight image in BYTES (0: architecture not served)
+ *   cppf_point_encoder_bf16_pack / _pack_device   `natural` as cppf_point_encoder_pack / _pack_device take it (host / device; the
+ *                                     device form serves any num_layers); the image is the natural block verbatim followed per
+ *                                     layer by 3 840 words: layer 1 and all bias / gamma / beta vectors in fp32, layers 2..5 in bf16
+ *                                     (csrc/sprin_layout_bf16.h)
+ *   cppf_point_encoder_bf16_forward / _forward_dyn / _forward_batch   arguments, workspace (cppf_point_encoder_workspace_bytes) and
+ *                                     return codes of cppf_point_encoder_forward / _forward_dyn / _forward_batch, with `packed`
+ *                                     (CppfPointEncItem.packed) pointing at a bf16 image: CPPF_EINVAL for null pointers,
+ *                                     CPPF_EUNSUPPORTED for another architecture or k > 64, CPPF_EWORKSPACE for a short workspace;
+ *                                     n_points == 0 is a no-op
+ * ------------------------------------------------------------------------------------------- */
+size_t cppf_point_encoder_bf16_packed_bytes(const int32_t* hidden, int n_hidden, int rank, int n_nbr_feats, int n_out, int n_glob,
+                                            int num_layers);
+int cppf_point_encoder_bf16_pack(const float* natural /*host*/, const int32_t* hidden, int n_hidden, int rank, int n_nbr_feats,
+                                 int n_out, int n_glob, int num_layers, void* packed_host);
+int cppf_point_encoder_bf16_pack_device(const float* natural /*device*/, const int32_t* hidden, int n_hidden, int rank, int n_nbr_feats,
+                                        int n_out, int n_glob, int num_layers, void* packed_device, void* stream);
+int cppf_point_encoder_bf16_forward(const float* pc, const float* nrm, const int32_t* nbrs, int n_points, int k, const void* packed,
+                                    const int32_t* hidden, int n_hidden, int rank, int n_nbr_feats, int n_out, int n_glob,
+                                    int num_layers, float* out, void* workspace, size_t workspace_bytes, void* stream);
+int cppf_point_encoder_bf16_forward_dyn(const float* pc, const float* nrm, const int32_t* nbrs, int n_cap, const int32_t* n_dev, int k,
+                                        const void* packed, const int32_t* hidden, int n_hidden, int rank, int n_nbr_feats, int n_out,
+                                        int n_glob, int num_layers, float* out, void* workspace, size_t workspace_bytes, void* stream);
+int cppf_point_encoder_bf16_forward_batch(int n_items, const CppfPointEncItem* items_host, int k, const int32_t* hidden, int n_hidden,
+                                          int rank, int n_nbr_feats, int n_out, int n_glob, int num_layers, void* stream);
+
 #ifdef CPPF_DEBUG_ENTRY
 /* Profiling aid, compiled only with -DCPPF_DEBUG_ENTRY (not in the shipped library): the PPF + gather + MFMA chain of the
  * standard architecture with no epilogue (isolates the matrix pipeline when reading rocprof counters).
