@@ -103,6 +103,9 @@ _SIGS = {
     "cppf_grid_setup": (C.c_int, [vp, i64, f32, vp, vp, vp]),
     "cppf_raster_workspace_bytes": (sz, [i64, i32, i32, i64]),
     "cppf_raster_depth": (C.c_int, [vp, i64, vp, i64, vp, C.c_double, C.c_double, i32, i32, C.c_double, i32, vp, i64, i32, vp, sz, vp]),
+    "cppf_raster_instances_workspace_bytes": (sz, [i32, i64, i32, i32, i32, i64]),
+    "cppf_raster_instances": (C.c_int, [vp, vp, vp, vp, i32, vp, vp, i32, C.c_double, C.c_double, i32, i32, C.c_double, i32, vp, vp, i64,
+                                        i32, vp, sz, vp]),
     "cppf_depth_points_workspace_bytes": (sz, [i32, i32]),
     "cppf_depth_points": (C.c_int, [vp, i32, i32, vp, vp, vp, vp, vp, sz, vp]),
     "cppf_surface_sample_workspace_bytes": (sz, [i32, i64]),

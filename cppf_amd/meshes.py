@@ -5,7 +5,10 @@ A mesh (an OBJ file, `load_obj`) is centred, scaled and posed at random in front
 dataset's point cloud (cppf_depth_points).  The cloud is moved back to the object frame, jittered, voxel-deduplicated, given PCA
 normals and pairs, and the vote targets are computed (`MeshViewSampler.sample`).  Everything after the host draws runs on the
 device; a sample reads two counts back (the rendered points, the points after deduplication), the reference reads the same
-sizes on its host."""
+sizes on its host.
+
+`render_instances` renders several posed meshes into one depth image with an instance label per pixel (cppf_raster_instances);
+cppf_amd/mesh_frames.py builds frames with ground truth on it."""
 import os
 
 import numpy as np
@@ -138,6 +141,92 @@ def render_depth(vertices, faces, pose, cull=True, fx=FX, fy=FY, width=WIDTH, he
     else:
         _render(mesh, pose, out, cull, fx, fy, znear)
     return out
+
+
+class _MeshSet:
+    """several meshes on the device in the form cppf_raster_instances reads: vertices and faces concatenated (face indices local
+    to their mesh), the host offset tables, and the bin-list capacity the renders of the set have needed so far"""
+
+    def __init__(self, meshes, dev):
+        vs, fs = [], []
+        for k, m in enumerate(meshes):
+            v, f = (m.v, m.f) if isinstance(m, _Mesh) else m
+            if isinstance(v, torch.Tensor):                          # (device tensors included: the caller's own form)
+                vs.append(canon(v, torch.float64, v.device, f"meshes[{k}] vertices", tail=(3,)).to(dev))
+                fs.append(canon(f, torch.int32, f.device, f"meshes[{k}] faces", tail=(3,)).to(dev))
+            else:
+                vs.append(torch.as_tensor(np.ascontiguousarray(v, np.float64).reshape(-1, 3)).to(dev))
+                fs.append(torch.as_tensor(np.ascontiguousarray(f, np.int32).reshape(-1, 3)).to(dev))
+        if not vs:
+            raise ValueError("no meshes")
+        self.n = len(vs)
+        self.vert_off = np.concatenate([[0], np.cumsum([v.shape[0] for v in vs])]).astype(np.int64)
+        self.face_off = np.concatenate([[0], np.cumsum([f.shape[0] for f in fs])]).astype(np.int64)
+        self.v = torch.cat(vs).contiguous()
+        self.f = torch.cat(fs).contiguous()
+        self.bins = {}                                               # (W, H) -> capacity
+
+
+def _instanced_faces(ms, inst_mesh):
+    """the faces all instances draw together (an entry that names no mesh of the set counts nothing: the call refuses it)"""
+    known = (inst_mesh >= 0) & (inst_mesh < ms.n)
+    return int((ms.face_off[1:] - ms.face_off[:-1])[inst_mesh[known]].sum())
+
+
+def _raster_instances(ms, inst_mesh, mvs, depth, labels, bins, cull, fx, fy, znear, ok=()):
+    H, W = depth.shape
+    K, Q = int(inst_mesh.shape[0]), _instanced_faces(ms, inst_mesh)
+    nbytes = _lib.lib().cppf_raster_instances_workspace_bytes(K, max(Q, 1), ms.n, W, H, bins)
+    if nbytes == 0:
+        raise ValueError(f"render of {K} instances with {Q} faces at {W}x{H}: outside the rasteriser's limits (include/cppf.h)")
+    ws = workspace(nbytes, depth.device, "raster_instances")
+    rc = call("cppf_raster_instances", depth.device, ms.v, ms.f, ms.vert_off, ms.face_off, ms.n, inst_mesh, mvs, K, fx, fy, W, H, znear,
+              bool(cull), depth, labels, bins, True, scratch(ws), ok=ok)
+    return rc, ws
+
+
+def render_instances(meshes, inst_mesh, model_views, cull=True, fx=FX, fy=FY, width=WIDTH, height=HEIGHT, znear=ZNEAR, device=None,
+                     max_bin_entries=None, out=None):
+    """Several posed meshes in ONE depth image with the instance that owns each pixel (include/cppf.h: cppf_raster_instances;
+    one binned pass over all instances' triangles): (depth f32[height, width], labels i32[height, width]) device tensors.
+    meshes: a list of (vertices f64[V,3], faces i32[F,3]) pairs (numpy or tensors) or a set loaded before (`mesh_set`);
+    inst_mesh i32[K]: the mesh each instance draws; model_views f64[K,4,4] (or [K,3,4]): each instance's model-view matrix, as
+    render_depth takes its one.  A pixel keeps the nearest fragment of all instances and the index of the instance it came from
+    (equal depth: the lowest index); background: depth 0, label -1.  max_bin_entries: a fixed bin-list capacity (a render that
+    needs more raises CppfError); None sizes it by itself and repeats a render that needed more once.  out: (depth, labels)
+    tensors to render into."""
+    require_cuda()
+    dev = device or torch.device("cuda", 0)
+    ms = meshes if isinstance(meshes, _MeshSet) else _MeshSet(meshes, dev)
+    inst = np.ascontiguousarray(np.asarray(inst_mesh).reshape(-1), np.int32)
+    mvs = np.asarray(model_views, np.float64)
+    if mvs.ndim != 3 or mvs.shape[0] != inst.shape[0] or mvs.shape[1] not in (3, 4) or mvs.shape[2] != 4:
+        raise ValueError(f"model_views must be [K,4,4] or [K,3,4] with one matrix per instance, got {mvs.shape} for {inst.shape[0]}")
+    mvs = np.ascontiguousarray(mvs[:, :3, :])
+    if out is None:
+        depth = torch.empty((height, width), dtype=torch.float32, device=dev)
+        labels = torch.empty((height, width), dtype=torch.int32, device=dev)
+    else:
+        depth = canon(out[0], torch.float32, dev, "out depth", tail=(height, width))
+        labels = canon(out[1], torch.int32, dev, "out labels", tail=(height, width))
+        if depth is not out[0] or labels is not out[1]:
+            raise ValueError("out: contiguous f32 / i32 [height, width] tensors on the device")
+    if max_bin_entries is not None:
+        _raster_instances(ms, inst, mvs, depth, labels, int(max_bin_entries), cull, fx, fy, znear)
+        return depth, labels
+    bins = max(ms.bins.get((width, height), 0), default_bin_entries(_instanced_faces(ms, inst), width, height))
+    rc, ws = _raster_instances(ms, inst, mvs, depth, labels, bins, cull, fx, fy, znear, ok=(_lib.ECAPACITY,))
+    if rc == _lib.ECAPACITY:                                         # the status words hold the entries needed
+        bins = int(min(int(ws[:8].view(torch.int32)[1].item()) * 5 // 4 + 1024, 0x7FFFFFFF))
+        _raster_instances(ms, inst, mvs, depth, labels, bins, cull, fx, fy, znear)
+    ms.bins[(width, height)] = bins
+    return depth, labels
+
+
+def mesh_set(meshes, device=None):
+    """meshes ((vertices, faces) pairs) uploaded once for many render_instances calls"""
+    require_cuda()
+    return _MeshSet(meshes, device or torch.device("cuda", 0))
 
 
 def depth_points(depth, intrinsics=DATASET_K):

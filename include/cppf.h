@@ -943,11 +943,35 @@ int cppf_segment_instance(const int32_t* point_idxs, const uint8_t* surv_mask, i
  *   and the dataset's x/z negation give pts = (X, -Y, -Z) device f64[H*W,3].  u, v are the INTEGER pixel coordinates while the
  *   render samples pixel centres: the dataset's half-pixel shift, kept.  pix device i32[H*W] = r*W + c, count device i32[1].
  *   H*W <= 8192 * 1024; workspace >= cppf_depth_points_workspace_bytes(H, W).
+ *
+ * cppf_raster_instances: K posed instances of several meshes in ONE depth image, with the instance that won each pixel -- the
+ *   multi-object frames of cppf_amd/mesh_frames.py.  One binned pass over all instances' triangles.
+ *   verts device f64[V,3] and faces device i32[F,3] of all meshes, concatenated; face indices are LOCAL to their mesh.
+ *   mesh_vert_off_host / mesh_face_off_host HOST i64[n_meshes+1] (first entry 0, every mesh with >= 1 vertex and >= 1 face),
+ *   inst_mesh_host HOST i32[K] = the mesh each instance draws (a mesh may be drawn many times), model_views_host HOST f64[K,12] =
+ *   rows 0..2 of each instance's model-view matrix, as cppf_raster_depth takes its one.  The call copies the four host tables
+ *   into its workspace before it returns.  fx .. sync, workspace and stream: cppf_raster_depth's.
+ *   Definition: steps 1-7 above apply unchanged to every (instance, face) with that instance's matrix.  A pixel keeps the MINIMUM
+ *   depth over all fragments of all instances, and labels (device i32[H,W]) the index of the instance that produced it; on equal
+ *   depth the LOWEST instance index wins, so neither image depends on the order of execution.  Background: depth 0.0f, label -1.
+ *   Hence depth = the element-wise minimum over covered pixels of the K cppf_raster_depth renders, labels = the first arg-min,
+ *   and K = 1 gives cppf_raster_depth's image bit for bit (both entry points run the same device functions).
+ *   Failure: a face index outside its mesh's vertex range -> CPPF_EINVAL, a bin list that is too small -> CPPF_ECAPACITY, both
+ *   through the status words as above; every depth pixel is then NaN and every label -1.  An inst_mesh entry outside
+ *   [0, n_meshes), an offset table that does not start at 0 or does not increase, or K < 1 returns CPPF_EINVAL from the host
+ *   before anything is launched.
+ *   Limits: 1 <= K <= 65536; Q = the sum over the instances of faces(inst_mesh[k]) <= 2^28; W, H <= 8192; max_bin_entries
+ *   <= 2^31 - 1.  Workspace: cppf_raster_instances_workspace_bytes(K, Q, n_meshes, W, H, max_bin_entries), status words first.
  * ------------------------------------------------------------------------------------------- */
 size_t cppf_raster_workspace_bytes(int64_t n_faces, int W, int H, int64_t max_bin_entries);
 int cppf_raster_depth(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const double* model_view_host,
                       double fx, double fy, int W, int H, double znear, int cull_back, float* depth, int64_t max_bin_entries, int sync,
                       void* workspace, size_t workspace_bytes, void* stream);
+size_t cppf_raster_instances_workspace_bytes(int n_instances, int64_t n_inst_faces, int n_meshes, int W, int H, int64_t max_bin_entries);
+int cppf_raster_instances(const double* verts, const int32_t* faces, const int64_t* mesh_vert_off_host, const int64_t* mesh_face_off_host,
+                          int n_meshes, const int32_t* inst_mesh_host, const double* model_views_host, int n_instances, double fx,
+                          double fy, int W, int H, double znear, int cull_back, float* depth, int32_t* labels, int64_t max_bin_entries,
+                          int sync, void* workspace, size_t workspace_bytes, void* stream);
 size_t cppf_depth_points_workspace_bytes(int H, int W);
 int cppf_depth_points(const float* depth, int H, int W, const double* kinv_host, double* pts, int32_t* pix, int32_t* count,
                       void* workspace, size_t workspace_bytes, void* stream);

@@ -1,0 +1,157 @@
+#!/usr/bin/env python3
+"""End-to-end accuracy on occluded input with a known answer: frames of several posed meshes (cppf_amd.mesh_frames.MeshFrameSampler:
+one cppf_raster_instances render per frame, instance labels, ground truth) -> FrameRunner -> 3D-IoU AP and degree / cm AP by the
+device evaluation path (evaluation.compute_degree_cm_mAP(device=...)).  Prints the two tables and the milliseconds per frame and
+writes the record to profiles/mesh_frames_eval.json (--out).  No accuracy threshold is applied anywhere: the figure is reported.
+
+Meshes: --meshes CATEGORY=DIR|NAMES (repeatable; what scripts/train_meshes.py takes), or --procedural for the procedural
+bottles / cans / cameras built from tests/mesh_ref.py.  Networks: --weights CATEGORY=FILE (training.save_weights's format), or
+--train-steps N to train each category on its meshes first (training.train_on_meshes).
+
+    python scripts/eval_mesh_frames.py --procedural --train-steps 3000 --train-pairs 200000 --frames 60 --objects 4
+    python scripts/eval_mesh_frames.py --meshes bottle=ShapeNetCore.v2/02876657 --weights bottle=bottle.npz --frames 200
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from cppf_amd import evaluation as E                   # noqa: E402
+from cppf_amd import mesh_frames as MF                 # noqa: E402
+from cppf_amd import meshes as M                       # noqa: E402
+from cppf_amd import training                          # noqa: E402
+from cppf_amd.config import CATEGORIES                 # noqa: E402
+from cppf_amd.frames import FrameRunner                # noqa: E402
+
+
+def _procedural(tmp):
+    """OBJ files of procedural stand-ins, scaled to a unit bounding-box diagonal like ShapeNet's model_normalized.obj"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import mesh_ref as R
+    shapes = {"bottle": [R.necked_cylinder(0.15, 0.40 + 0.03 * k, neck=0.35 + 0.05 * k, n_lon=48) for k in range(4)],
+              "can": [R.necked_cylinder(0.2, 0.28 + 0.03 * k, neck=0.95, n_lon=48) for k in range(4)],
+              "camera": [R.box(0.30 + 0.02 * k, 0.2, 0.12 + 0.02 * k)[:2] for k in range(4)]}
+    out = {}
+    for cat, ms in shapes.items():
+        out[cat] = []
+        for k, (v, f) in enumerate(ms):
+            p = os.path.join(tmp, f"{cat}{k}.obj")
+            open(p, "w").write(R.to_obj(v / np.linalg.norm(v.max(0) - v.min(0)), f))
+            out[cat].append(p)
+    return out
+
+
+def _pairs(items, what):
+    out = {}
+    for it in items or []:
+        if "=" not in it:
+            sys.exit(f"--{what} takes CATEGORY=PATH, got {it!r}")
+        cat, path = it.split("=", 1)
+        out[cat] = path
+    return out
+
+
+def _tables(iou_aps, pose_aps, names, cats, deg, sh, rec):
+    """print the two AP tables (per category and the mean over the categories that were drawn) and put them into `rec`"""
+    ids = [names.index(c) for c in cats]
+    rows = cats + ["mean"]
+    print(f"{'3D IoU AP':12s}" + "".join(f"{'IoU' + str(t):>9s}" for t in (25, 50, 75)))
+    for c in rows:
+        r = iou_aps[names.index(c)] if c != "mean" else iou_aps[ids].mean(0)
+        rec["iou_ap"][c] = {f"iou{t}": float(r[t]) for t in (25, 50, 75)}
+        print(f"{c:12s}" + "".join(f"{100 * r[t]:9.1f}" for t in (25, 50, 75)))
+    combos = [(0, 0), (1, 0), (1, 1), (2, 2)]
+    print(f"{'pose AP':12s}" + "".join(f"{str(deg[d]) + 'deg' + str(sh[s]) + 'cm':>11s}" for d, s in combos))
+    for c in rows:
+        r = pose_aps[names.index(c)] if c != "mean" else pose_aps[ids].mean(0)
+        rec["pose_ap"][c] = {f"{deg[d]}deg_{sh[s]}cm": float(r[d, s]) for d, s in combos}
+        print(f"{c:12s}" + "".join(f"{100 * r[d, s]:11.1f}" for d, s in combos))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--meshes", action="append", help="CATEGORY=directory of OBJ files or names file (repeatable)")
+    ap.add_argument("--shapenet-root", default=None)
+    ap.add_argument("--procedural", action="store_true", help="procedural bottle / can / camera meshes instead of --meshes")
+    ap.add_argument("--weights", action="append", help="CATEGORY=weights file (repeatable)")
+    ap.add_argument("--train-steps", type=int, default=0, help="train each category without --weights for N steps first")
+    ap.add_argument("--train-pairs", type=int, default=60000, help="pairs per training step (train_on_meshes' n_pairs)")
+    ap.add_argument("--frames", type=int, default=50)
+    ap.add_argument("--objects", type=int, default=4)
+    ap.add_argument("--min-pixels", type=int, default=400, help="instances with fewer visible pixels get no mask (unmatched ground truth)")
+    ap.add_argument("--n-pairs", type=int, default=100000)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_frames_eval.json"))
+    args = ap.parse_args()
+    dev = torch.device("cuda", 0)
+    tmp = tempfile.TemporaryDirectory()
+    if args.procedural:
+        cat_paths = _procedural(tmp.name)
+    else:
+        cat_paths = {c: M.mesh_paths(p, args.shapenet_root) for c, p in _pairs(args.meshes, "meshes").items()}
+    if not cat_paths or not all(cat_paths.values()):
+        sys.exit("no meshes: --meshes CATEGORY=DIR (repeatable) or --procedural")
+    for c in cat_paths:
+        if c not in CATEGORIES:
+            sys.exit(f"category {c!r} has no built-in config")
+    weights = _pairs(args.weights, "weights")
+    encs, pencs, trained = {}, {}, {}
+    for c, paths in cat_paths.items():
+        if c in weights:
+            pencs[c], encs[c] = training.load_weights(weights[c], CATEGORIES[c], dev)
+        elif args.train_steps > 0:
+            t0 = time.perf_counter()
+            pencs[c], encs[c], losses = training.train_on_meshes(c, paths, dev, steps=args.train_steps, n_pairs=args.train_pairs,
+                                                                     seed=args.seed)
+            torch.cuda.synchronize()
+            trained[c] = dict(steps=args.train_steps, pairs=args.train_pairs, seconds=time.perf_counter() - t0, final_loss=float(losses[-1]))
+            print(f"{c}: trained {args.train_steps} steps on {len(paths)} meshes in {trained[c]['seconds']:.1f} s, loss {losses[-1]:.4f}")
+        else:
+            sys.exit(f"category {c}: --weights {c}=FILE or --train-steps N")
+    sampler = MF.MeshFrameSampler(cat_paths, args.objects, device=dev, seed=args.seed)
+    runner = FrameRunner(encs, pencs, dev, intrinsics=MF.frame_intrinsics(), n_pairs=args.n_pairs)
+    results, ms, n_inst, n_gt, n_none = [], [], 0, 0, 0
+    for i in range(args.frames):
+        fr = sampler.sample()
+        inst = fr.instances(args.min_pixels)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        poses = runner.run(fr.depth_mm, inst, seed=i) if inst else []        # (ends in the frame's read-back)
+        ms.append((time.perf_counter() - t0) * 1e3)
+        ok = lambda p: all(np.all(np.isfinite(p[k])) for k in ("T", "R", "scale")) and p["scale_norm"] > 0
+        poses = [p if p is not None and ok(p) else None for p in poses]       # (a pose that is no pose makes no prediction)
+        results.append(fr.record(poses, min_pixels=args.min_pixels))
+        n_inst += len(inst)
+        n_gt += len(fr.categories)
+        n_none += sum(p is None for p in poses)
+    deg, sh = [5, 10, 15], [5, 10, 15]
+    iou = [float(t) for t in np.round(np.linspace(0, 1, 101), 2)]
+    names = sampler.synset_names
+    t0 = time.perf_counter()
+    iou_aps, pose_aps, _, _ = E.compute_degree_cm_mAP(results, names, None, deg, sh, iou, 0.1, True, device=dev)
+    eval_s = time.perf_counter() - t0
+    steady = ms[min(3, len(ms) - 1):]                                         # the first frames capture their chains
+    rec = dict(device=torch.cuda.get_device_name(0), frames=args.frames, objects_per_frame=args.objects, min_pixels=args.min_pixels,
+               n_pairs=args.n_pairs, seed=args.seed, categories={c: len(p) for c, p in cat_paths.items()},
+               procedural=bool(args.procedural), trained=trained, weights=weights, ground_truths=n_gt, instances_run=n_inst,
+               instances_skipped_by_the_frame_path=n_none, ms_per_frame_median=float(np.median(steady)),
+               ms_per_frame_mean=float(np.mean(steady)), evaluation_seconds=eval_s, iou_ap={}, pose_ap={})
+    print(f"{args.frames} frames, {n_gt} ground truths, {n_inst} instances with >= {args.min_pixels} pixels, {n_none} skipped by the frame "
+          f"path; {rec['ms_per_frame_median']:.2f} ms per frame (median after the first 3), evaluation {eval_s:.2f} s")
+    _tables(iou_aps, pose_aps, names, list(cat_paths), deg, sh, rec)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(rec, fh, indent=1)
+        fh.write("\n")
+    tmp.cleanup()
+
+
+if __name__ == "__main__":
+    main()
