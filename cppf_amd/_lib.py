@@ -100,6 +100,10 @@ _SIGS = {
     "cppf_scene_proposals": (C.c_int, [vp, i32, i32, i32, vp, i32, f32, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),
     "cppf_segment_instance_workspace_bytes": (sz, [i64, i64]),
     "cppf_segment_instance": (C.c_int, [vp, vp, i64, i64, i32, vp, vp, vp, vp, sz, vp]),
+    # all proposals of a scene in one pass (csrc/scene_multi.hip)
+    "cppf_backvote_multi": (C.c_int, [vp, vp, vp, vp, f32, i64, i32, i32, i32, i32, vp, i32, f32, vp, vp, vp]),
+    "cppf_segment_instances_workspace_bytes": (sz, [i64, i64, i32]),
+    "cppf_segment_instances": (C.c_int, [vp, vp, i64, i64, i32, i32, vp, vp, i64, vp, vp, sz, vp]),
     "cppf_grid_setup": (C.c_int, [vp, i64, f32, vp, vp, vp]),
     "cppf_raster_workspace_bytes": (sz, [i64, i32, i32, i64]),
     "cppf_raster_depth": (C.c_int, [vp, i64, vp, i64, vp, C.c_double, C.c_double, i32, i32, C.c_double, i32, vp, i64, i32, vp, sz, vp]),

@@ -897,6 +897,36 @@ int cppf_segment_instance(const int32_t* point_idxs, const uint8_t* surv_mask, i
                           void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The per-proposal stage of a scene for ALL proposals in one pass over the pair list (csrc/scene_multi.hip; additive, ABI version
+ * unchanged).  What K calls of cppf_backvote_ws + cppf_segment_instance compute, with the pair list, the pairs' points and the
+ * pairs' frames read once instead of K times.
+ *
+ * cppf_backvote_multi: the back-vote of models/voting.py:74-112 at n_centers (1..32) centres.  Bit k of surv_bits[p] equals, bit
+ *   for bit, the mask cppf_backvote_ws writes for pair p at centers[k] (always adaptive, bounds [0, dim-1), the first passing
+ *   rotation in index order decides, degenerate pairs give 0); bits >= n_centers are 0.  centers device f32[n_centers,3];
+ *   surv_bits device u32[n_ppfs], cleared by the call and filled with integer OR atomics: the same words on every run.
+ *   vote_workspace: as for cppf_backvote_ws (may be NULL).  CPPF_EINVAL: n_centers outside 1..32, n_rots outside 1..CPPF_MAX_ROTS,
+ *   a dim < 1, a null pointer, n_ppfs < 0 or n_ppfs >= 2^27 (a queue entry packs the pair with the 5 bits of k).  n_ppfs == 0
+ *   returns 0 and launches nothing.
+ *
+ * cppf_segment_instances: cppf_segment_instance on every bit.  point_masks device u8[n_centers,n_points]: row k is the point_mask
+ *   of bit k.  The kept pairs of proposal k (positions in the pair list, in pair order) are pairs_out[offsets[k] .. offsets[k+1]);
+ *   offsets device i32[n_centers+1] always holds the true prefix sums.  pairs_out device i32[capacity]: when offsets[n_centers] >
+ *   capacity nothing is written at or beyond `capacity` and the call returns 0 -- the caller reads offsets and repeats the call
+ *   with a buffer of offsets[n_centers] entries.  The endpoint counts are integer atomics into a [n_centers,n_points] table in ONE
+ *   pass over the pair list (pairs (i, i) count twice); the results are the same on every run.  Bits >= n_centers of surv_bits are
+ *   ignored.  CPPF_EINVAL: n_centers outside 1..32, n_points outside 1..2^31-1, negative sizes, null pointers; CPPF_EUNSUPPORTED:
+ *   n_pairs n_centers > 2^31-1 (the offsets are int32); workspace >= cppf_segment_instances_workspace_bytes().
+ * ------------------------------------------------------------------------------------------- */
+int cppf_backvote_multi(const float* points, const float* outputs, const int32_t* point_idxs, const float* corner, float res,
+                        int64_t n_ppfs, int n_rots, int gx, int gy, int gz, const float* centers, int n_centers, float tol,
+                        uint32_t* surv_bits, const void* vote_workspace, void* stream);
+size_t cppf_segment_instances_workspace_bytes(int64_t n_points, int64_t n_pairs, int n_centers);
+int cppf_segment_instances(const int32_t* point_idxs, const uint32_t* surv_bits, int64_t n_pairs, int64_t n_points, int n_centers,
+                           int min_contrib, uint8_t* point_masks, int32_t* pairs_out, int64_t capacity, int32_t* offsets,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Training views (utils/dataset.py:103-207, csrc/raster.hip): the pyrender `RenderFlags.DEPTH_ONLY` render of one mesh through
  * the dataset's PinholeCamera (:108-138), and the covered pixels as the dataset's point cloud.  Parity with pyrender is UNPINNED
  * (pyrender and its 24-bit depth buffer are not part of the project); the definition below is, to the operation, and

@@ -10,6 +10,13 @@ bottles / cans / cameras built from tests/mesh_ref.py.  Networks: --weights CATE
 
     python scripts/eval_mesh_frames.py --procedural --train-steps 3000 --train-pairs 200000 --frames 60 --objects 4
     python scripts/eval_mesh_frames.py --meshes bottle=ShapeNetCore.v2/02876657 --weights bottle=bottle.npz --frames 200
+
+--mask-free (opt-in; the default run above is unchanged): no instance masks.  Per frame and per category, scene_poses.scene_frame runs
+that category's networks on the WHOLE depth image and every proposal becomes a prediction with the category's class id, scored by its
+smoothed peak's height above its box edges.  The APs go to profiles/scene_poses_eval.json (--out) as a first figure, with no
+threshold attached.
+
+    python scripts/eval_mesh_frames.py --procedural --train-steps 3000 --train-pairs 200000 --frames 20 --objects 4 --mask-free
 """
 import argparse
 import json
@@ -75,6 +82,46 @@ def _tables(iou_aps, pose_aps, names, cats, deg, sh, rec):
         print(f"{c:12s}" + "".join(f"{100 * r[d, s]:11.1f}" for d, s in combos))
 
 
+def _mask_free_record(fr, preds):
+    """MeshFrame.record's dict with the proposals as predictions.  preds: [(class id, pose dict, score)]"""
+    K, n = len(fr.categories), len(preds)
+    RTs = np.tile(np.eye(4), (n, 1, 1))
+    scales = np.ones((n, 3))
+    for i, (_, p, _) in enumerate(preds):
+        RTs[i, :3, :3] = np.asarray(p["R"], np.float64) * float(p["scale_norm"])
+        RTs[i, :3, 3] = np.asarray(p["T"], np.float64)
+        scales[i] = np.asarray(p["scale"], np.float64) / float(p["scale_norm"])
+    rec = fr.record([None] * len(fr.visible(1)), min_pixels=1)             # the ground-truth half, no predictions
+    rec.update(pred_class_ids=np.array([c for c, _, _ in preds], np.int32).reshape(n), pred_RTs=RTs, pred_scales=scales,
+               pred_scores=np.array([s for _, _, s in preds], np.float64).reshape(n))
+    assert rec["gt_class_ids"].shape[0] == K
+    return rec
+
+
+def _mask_free(args, sampler, encs, pencs, dev):
+    """the frames through scene_frame per category -> (result records, ms per frame, proposals, ground truths)"""
+    from cppf_amd.scene_poses import scene_frame
+    names = sampler.synset_names
+    results, ms, n_prop, n_gt = [], [], 0, 0
+    for i in range(args.frames):
+        fr = sampler.sample()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        preds = []
+        for c in sampler.categories:
+            out = scene_frame(fr.depth_mm, fr.intrinsics, encs[c], pencs[c], CATEGORIES[c], n_pairs=args.scene_pairs, seed=i,
+                              thresh=args.thresh, max_proposals=args.max_proposals)
+            for p in out["poses"]:
+                if all(np.all(np.isfinite(p[k])) for k in ("T", "R", "scale")) and p["scale_norm"] > 0:
+                    preds.append((names.index(c), p, p["diff"]))
+        ms.append((time.perf_counter() - t0) * 1e3)
+        preds = sorted(preds, key=lambda t: -t[2])[:20]                  # (the evaluation's match tables hold 20 predictions per image)
+        results.append(_mask_free_record(fr, preds))
+        n_prop += len(preds)
+        n_gt += len(fr.categories)
+    return results, ms, n_prop, n_gt
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", action="append", help="CATEGORY=directory of OBJ files or names file (repeatable)")
@@ -88,8 +135,15 @@ def main():
     ap.add_argument("--min-pixels", type=int, default=400, help="instances with fewer visible pixels get no mask (unmatched ground truth)")
     ap.add_argument("--n-pairs", type=int, default=100000)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_frames_eval.json"))
+    ap.add_argument("--mask-free", action="store_true", help="no masks: scene_frame per category on the whole image (see above)")
+    ap.add_argument("--scene-pairs", type=int, default=1_000_000, help="--mask-free: pairs drawn over the whole frame")
+    ap.add_argument("--thresh", type=float, default=50.0, help="--mask-free: the proposal loop's threshold")
+    ap.add_argument("--max-proposals", type=int, default=6, help="--mask-free: proposals per category and frame (the 20 best-scored "
+                    "predictions of a frame are evaluated)")
+    ap.add_argument("--out", default=None, help="default profiles/mesh_frames_eval.json (profiles/scene_poses_eval.json with --mask-free)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "scene_poses_eval.json" if args.mask_free else "mesh_frames_eval.json")
     dev = torch.device("cuda", 0)
     tmp = tempfile.TemporaryDirectory()
     if args.procedural:
@@ -116,6 +170,24 @@ def main():
         else:
             sys.exit(f"category {c}: --weights {c}=FILE or --train-steps N")
     sampler = MF.MeshFrameSampler(cat_paths, args.objects, device=dev, seed=args.seed)
+    if args.mask_free:
+        results, ms, n_prop, n_gt = _mask_free(args, sampler, encs, pencs, dev)
+        deg, sh = [5, 10, 15], [5, 10, 15]
+        iou = [float(t) for t in np.round(np.linspace(0, 1, 101), 2)]
+        iou_aps, pose_aps, _, _ = E.compute_degree_cm_mAP(results, sampler.synset_names, None, deg, sh, iou, 0.1, True, device=dev)
+        rec = dict(device=torch.cuda.get_device_name(0), mode="mask-free: scene_frame per category on the whole depth image", frames=args.frames,
+                   objects_per_frame=args.objects, scene_pairs=args.scene_pairs, thresh=args.thresh, max_proposals=args.max_proposals, seed=args.seed,
+                   categories={c: len(p) for c, p in cat_paths.items()}, procedural=bool(args.procedural), trained=trained, weights=weights,
+                   ground_truths=n_gt, proposals=n_prop, ms_per_frame_median=float(np.median(ms[min(1, len(ms) - 1):])), iou_ap={}, pose_ap={},
+                   note="a first figure: no threshold is attached to these APs")
+        print(f"{args.frames} frames, {n_gt} ground truths, {n_prop} proposals; {rec['ms_per_frame_median']:.1f} ms per frame (all categories)")
+        _tables(iou_aps, pose_aps, sampler.synset_names, list(cat_paths), deg, sh, rec)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(rec, fh, indent=1)
+            fh.write("\n")
+        tmp.cleanup()
+        return
     runner = FrameRunner(encs, pencs, dev, intrinsics=MF.frame_intrinsics(), n_pairs=args.n_pairs)
     results, ms, n_inst, n_gt, n_none = [], [], 0, 0, 0
     for i in range(args.frames):
