@@ -123,6 +123,9 @@ _SIGS = {
     "cppf_pose_eval_pairs": (C.c_int, [vp, vp, i64, vp, vp, vp, i64, vp, vp, i64, vp, vp, vp, sz, vp]),
     "cppf_pose_eval_match_iou": (C.c_int, [vp, vp, vp, vp, i32, vp, i32, i64, i64, i64, vp, vp, vp]),
     "cppf_pose_eval_match_pose": (C.c_int, [vp, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, i64, i64, i64, vp, vp, vp]),
+    # greedy 3D box NMS, all (image, class) groups in one call (csrc/box_nms.hip); the group table is a host array
+    "cppf_box_nms_workspace_bytes": (sz, [i64, i32]),
+    "cppf_box_nms_batch": (C.c_int, [vp, vp, vp, i64, vp, i32, C.c_double, vp, vp, vp, vp, sz, vp]),
     "cppf_knn": (C.c_int, [vp, vp, i32, i32, vp, vp]),
     "cppf_frame_cloud_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "cppf_frame_cloud_dyn": (C.c_int, [vp, i32, vp, i32, i32, i32, i32, vp, C.c_double, C.c_double, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),

@@ -1,0 +1,105 @@
+"""Mask-free frame detections: one depth frame in, ONE list of detections of all categories out.
+
+cppf_amd.scene_poses returns, per category network, every proposal of a scene; each network also votes on every other category's
+points, and nothing filters what it proposes.  This module pools the categories' proposals and runs the
+reference's scene-level post-processing on them -- the greedy 3D non-maximum suppression of sunrgbd/eval.py:13-35,116-145 per class,
+on the device (evaluation.nms_3d -> cppf_box_nms_batch, all categories in one call):
+
+  frame_detections   depth frame -> scene_frame per category (the dense cloud and its normals computed once per distinct
+                     (res, knn)) -> pool_detections
+  pool_detections    scene_poses / scene_frame dicts, one per category -> detections, per-category NMS, optionally a second,
+                     cross-category pass over the survivors
+"""
+from collections import OrderedDict
+
+import numpy as np
+
+from . import evaluation as E
+
+
+def _finite(p):
+    return all(np.all(np.isfinite(np.asarray(p[k], np.float64))) for k in ("T", "R", "scale")) and np.isfinite(p["scale_norm"]) \
+        and p["scale_norm"] > 0
+
+
+def pool_detections(outs, names, cfgs=None, nms_thresh=0.3, cross_category=False, score="diff", device=None):
+    """outs: scene_poses / scene_frame dicts, one per category, in the order of `names` (the categories' names); cfgs: their configs
+    (kept beside the detections for callers; nothing here reads them).
+    Every finite proposal with scale_norm > 0 becomes a detection dict:
+      class_name, category (index into names), RT f64[4,4] (rotation * scale_norm, translation) and scales f64[3] (scale /
+      scale_norm) -- the pair inference.nocs_result writes --, score (p["diff"], the smoothed peak's height above its box edge, which
+      scripts/eval_mesh_frames.py ranks by; score="cnt": the smoothed peak itself), pose (the pose dict, its point_mask over THAT
+      category's cloud) and proposal (its index in that category's list).
+    NMS (evaluation.nms_3d, thresh = nms_thresh, boxes = (RT, extents p["scale"])) runs per category, all categories in one call: the
+    reference's rule.  nms_thresh=None: no suppression.  device: where it runs (None: the host path).
+    cross_category=True: a second pass over the survivors of all categories pooled as ONE group.  Scores of different networks are
+    vote-peak heights of different networks on different clouds; they are NOT calibrated against each other, so which of two
+    coincident detections of different categories survives says which network voted harder, not which is right.
+    Returns dict(detections=[...] in descending score order (equal scores: the higher pooled index first, NMS' tie rule),
+    kept_per_category {name: n}, suppressed {name: n} (both passes), proposals_per_category {name: n}, result=dict(pred_class_ids
+    i32[n] = category + 1 (0 is the background of a synset list ["BG"] + names), pred_RTs, pred_scales, pred_scores) as
+    evaluation.compute_degree_cm_mAP reads them, cfgs)."""
+    names = list(names)
+    if len(outs) != len(names):
+        raise ValueError(f"{len(outs)} outputs for {len(names)} category names")
+    if score not in ("diff", "cnt"):
+        raise ValueError(f"score must be 'diff' or 'cnt', got {score!r}")
+    dets = []
+    for c, out in enumerate(outs):
+        for k, p in enumerate(out["poses"]):
+            if p is None or not _finite(p) or not np.isfinite(p[score]):
+                continue
+            RT = np.eye(4)
+            RT[:3, :3] = np.asarray(p["R"], np.float64) * float(p["scale_norm"])
+            RT[:3, 3] = np.asarray(p["T"], np.float64)
+            dets.append(dict(class_name=names[c], category=c, RT=RT, scales=np.asarray(p["scale"], np.float64) / float(p["scale_norm"]),
+                             score=float(p[score]), pose=p, proposal=k))
+    n = len(dets)
+    cat = np.array([d["category"] for d in dets], np.int64).reshape(n)
+    scores = np.array([d["score"] for d in dets], np.float64).reshape(n)
+    RTs = np.stack([d["RT"] for d in dets]) if n else np.zeros((0, 4, 4))
+    extents = np.stack([np.asarray(d["pose"]["scale"], np.float64) for d in dets]) if n else np.zeros((0, 3))
+    keep = np.arange(n)
+    if nms_thresh is not None and n:
+        keep = np.concatenate(E.nms_3d(RTs, extents, scores, nms_thresh, groups=cat, device=device) + [np.zeros(0, np.int64)])
+        if cross_category and len(keep):
+            keep = np.sort(keep)
+            (again,) = E.nms_3d(RTs[keep], extents[keep], scores[keep], nms_thresh, device=device)
+            keep = keep[again]
+    keep = np.sort(keep.astype(np.int64))
+    keep = keep[np.argsort(scores[keep], kind="stable")[::-1]]
+    kept = [dets[i] for i in keep]
+    per_cat = lambda idx: OrderedDict((nm, int((cat[idx] == c).sum())) for c, nm in enumerate(names))
+    total, left = per_cat(np.arange(n)), per_cat(keep)
+    result = dict(pred_class_ids=(cat[keep] + 1).astype(np.int32), pred_RTs=RTs[keep].reshape(-1, 4, 4),
+                  pred_scales=(np.stack([d["scales"] for d in kept]) if kept else np.zeros((0, 3))), pred_scores=scores[keep])
+    return dict(detections=kept, kept_per_category=left, suppressed=OrderedDict((nm, total[nm] - left[nm]) for nm in names),
+                proposals_per_category=total, result=result, cfgs=cfgs)
+
+
+def frame_detections(depth, intrinsics, networks, n_pairs=5_000_000, seed=0, jitter=None, nms_thresh=0.3, cross_category=False,
+                     score="diff", **scene_kw):
+    """One depth frame with no instance masks -> the detections of all categories (pool_detections' dict, plus outs: the categories'
+    scene_frame dicts).
+    networks: an ordered mapping name -> (point_encoder, encoder, cfg), modules on one HIP device, in either precision (what the
+    encoders are set to is what runs).  scene_frame runs once per category with the same `seed` (and jitter); the dense cloud and its
+    normals are computed once per distinct (cfg.res, cfg.knn) and shared (scene_frame's cloud=: the same bits as without sharing).
+    The NMS runs on the networks' device.  scene_kw: scene_poses' options (thresh, max_proposals, ...)."""
+    from .scene_poses import frame_cloud, scene_frame
+    if not networks:
+        raise ValueError("frame_detections needs at least one category network")
+    names, outs, cfgs, clouds, dev = [], [], [], {}, None
+    for name, (point_encoder, encoder, cfg) in networks.items():
+        key = (float(cfg.res), int(cfg.knn))
+        if key not in clouds:
+            clouds[key] = frame_cloud(depth, intrinsics, cfg, jitter)
+        out = scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=n_pairs, seed=seed, jitter=jitter, cloud=clouds[key],
+                          **scene_kw)
+        dev = out["pc"].device
+        names.append(name); outs.append(out); cfgs.append(cfg)
+    res = pool_detections(outs, names, cfgs, nms_thresh, cross_category, score, device=dev)
+    res["outs"] = outs
+    return res
+
+
+__all__ = ["pool_detections", "frame_detections"]

@@ -19,6 +19,10 @@ The implementation is this repository's own:
 * no plots are drawn (the reference's figures are a side effect; the AP tables it pickles next to them are written when
   `log_dir` is given).
 
+nms_3d / nms_results are the scene-level post-processing of `sunrgbd/eval.py:13-35,110-145`: greedy 3D non-maximum suppression per
+(image, class) over the same oriented-box IoU, on the host (the checker) or on the device (csrc/box_nms.hip, include/cppf.h
+"Box NMS"; pinned on the reference's own pick lists, tests/golden/make_golden_nms.py -> nms_cases.npz).
+
 Parity is pinned on outputs of the reference's own functions for seeded synthetic results (tests/golden/
 make_golden_eval.py -> eval_map.npz; tests/test_evaluation.py)."""
 import math
@@ -610,6 +614,149 @@ def _map_on_device(final_results, synset_names, log_dir, degree_thresholds, shif
     if log_dir:
         _write_tables(log_dir, iou_list, deg_list, sh_list, iou_3d_aps, pose_aps, use_matches_for_pose)
     return iou_3d_aps, pose_aps, pose_pred_matches, pose_gt_matches
+
+
+# ------------------------------------------------------------------------------------------------ sunrgbd/eval.py: 3D NMS
+NMS_GROUP_CAP = 1024      # boxes of one group on the device: include/cppf.h CPPF_BOX_NMS_GROUP_CAP
+
+
+def _nms_valid(RTs, scales, scores):
+    """the boxes NMS takes: everything finite (sunrgbd/eval.py:121), the last row [0 0 0 1] and a regular rotation block
+    (_check_poses' criteria), every extent positive"""
+    n = len(RTs)
+    if n == 0:
+        return np.zeros(0, bool)
+    ok = np.isfinite(RTs).all((1, 2)) & np.isfinite(scales).all(1) & np.isfinite(scores)
+    ok &= (RTs[:, 3] == np.array([0.0, 0.0, 0.0, 1.0])).all(1)
+    safe = np.where(ok[:, None, None], RTs, np.eye(4)[None])
+    det = np.linalg.det(safe[:, :3, :3])
+    with np.errstate(divide="ignore", over="ignore", invalid="ignore"):
+        ok &= (np.abs(det) > 1e-12 * np.linalg.norm(safe[:, :3, :3], axis=1).prod(1)) & np.isfinite(1.0 / det)
+        ok &= (scales > 0).all(1)
+    return ok
+
+
+def _nms_greedy_host(RTs, scales, scores, thresh):
+    """sunrgbd/eval.py:21-35 on one group: indices in pick order.  Ties: the higher index first (a stable ascending argsort read
+    from the end); an IoU that is NaN suppresses nothing."""
+    order = np.argsort(scores, kind="stable")[::-1]
+    alive = np.ones(len(order), bool)
+    pick = []
+    for a, i in enumerate(order):
+        if not alive[a]:
+            continue
+        pick.append(int(i))
+        for b in range(a + 1, len(order)):
+            if alive[b]:
+                j = order[b]
+                lo, hi = (i, j) if i < j else (j, i)             # the pair as the device forms it: the lower index is box 1
+                if compute_3d_iou(RTs[lo], RTs[hi], scales[lo], scales[hi], False, None, None) > thresh:
+                    alive[b] = False
+    return np.asarray(pick, dtype=np.int64)
+
+
+def _nms_on_device(dev, RTs, scales, scores, group_off, thresh):
+    """cppf_box_nms_batch on host arrays already in group order: one upload, one call, one read-back -> (pick i32[n], n_pick i32[G])"""
+    import torch
+    from . import _lib
+    from ._torch_util import call, require_cuda, scratch, workspace
+    require_cuda()
+    dev = torch.device(dev)
+    n, G = len(RTs), len(group_off) - 1
+    if n == 0 or G == 0:
+        return np.zeros(0, np.int32), np.zeros(G, np.int32)
+    buf = torch.from_numpy(np.concatenate([RTs.reshape(-1), scales.reshape(-1), scores.reshape(-1)]).astype(np.float64)).to(dev)
+    res = torch.empty(n + G, dtype=torch.int32, device=dev)
+    ws = workspace(_lib.lib().cppf_box_nms_workspace_bytes(n, G), dev, "box_nms")
+    call("cppf_box_nms_batch", dev, buf[:16 * n], buf[16 * n:19 * n], buf[19 * n:], n, np.ascontiguousarray(group_off, np.int32), G,
+         float(thresh), res[:n], res[n:], None, scratch(ws))
+    out = res.cpu().numpy()                                      # the one read-back
+    return out[:n], out[n:]
+
+
+def nms_3d(RTs, scales, scores, thresh=0.3, groups=None, device=None):
+    """Greedy 3D non-maximum suppression over oriented boxes (sunrgbd/eval.py:13-35): within a group the boxes are visited by
+    descending score, a box that is not suppressed is picked and suppresses every later box whose IoU with it is strictly greater
+    than `thresh`.  The IoU is compute_3d_iou(RT_i, RT_j, scales_i, scales_j, up_sym=False, ...) with the lower index as box 1: the
+    rotation block may carry an isotropic scale (normalised by cbrt(det)), `scales` are the extents along the normalised axes.
+
+    RTs [n,4,4], scales [n,3], scores [n]; groups: None (one group) or int [n], the group of every box, 0 <= id (e.g. one id per
+    (image, class)).  Returns a list of int64 index arrays in pick order, one per group (max id + 1 of them; [one] for None); the
+    indices refer to the arguments as given.
+    Dropped before anything else, and never picked: a box with a non-finite RT, scale or score (sunrgbd/eval.py:121), with a last
+    row other than [0 0 0 1] or a singular rotation block (_check_poses), or with a non-positive extent.
+    Equal scores: the higher index goes first (a stable ascending argsort read from the end; the reference's np.argsort leaves ties
+    open).  A NaN IoU suppresses nothing.
+    device=None: numpy, the checker.  A HIP device: one cppf_box_nms_batch call for all groups and one read-back (csrc/box_nms.hip;
+    at most NMS_GROUP_CAP valid boxes per group there)."""
+    RTs = np.asarray(RTs, dtype=np.float64).reshape(-1, 4, 4)
+    scales = np.asarray(scales, dtype=np.float64).reshape(-1, 3)
+    scores = np.asarray(scores, dtype=np.float64).reshape(-1)
+    n = len(RTs)
+    if len(scales) != n or len(scores) != n:
+        raise ValueError(f"nms_3d: {n} poses, {len(scales)} scales and {len(scores)} scores")
+    if groups is None:
+        gid, G = np.zeros(n, np.int64), 1
+    else:
+        gid = np.asarray(groups).astype(np.int64).reshape(-1)
+        if len(gid) != n or (n and gid.min() < 0):
+            raise ValueError("nms_3d: groups holds one non-negative id per box")
+        G = int(gid.max()) + 1 if n else 0
+    valid = np.where(_nms_valid(RTs, scales, scores))[0]
+    sel = valid[np.argsort(gid[valid], kind="stable")]           # group order; a group's boxes stay in index order
+    group_off = np.zeros(G + 1, np.int64)
+    np.cumsum(np.bincount(gid[sel], minlength=G), out=group_off[1:])
+    if device is None:
+        return [sel[a:b][_nms_greedy_host(RTs[sel[a:b]], scales[sel[a:b]], scores[sel[a:b]], thresh)] if b > a else np.zeros(0, np.int64)
+                for a, b in zip(group_off[:-1], group_off[1:])]
+    if G and np.diff(group_off).max() > NMS_GROUP_CAP:
+        raise ValueError(f"nms_3d: a group of {int(np.diff(group_off).max())} boxes; the device path takes at most {NMS_GROUP_CAP} per "
+                         "group (device=None has no cap)")
+    pick, n_pick = _nms_on_device(device, RTs[sel], scales[sel], scores[sel], group_off, thresh)
+    return [sel[a:b][pick[a:a + k]].astype(np.int64) for a, b, k in zip(group_off[:-1], group_off[1:], n_pick)]
+
+
+_NMS_PRED_KEYS = ("pred_class_ids", "pred_RTs", "pred_scales", "pred_scores", "pred_bboxes")
+
+
+def nms_results(final_results, thresh=0.3, device=None):
+    """sunrgbd/eval.py:110-145 for a list of result dicts in compute_degree_cm_mAP's format: every image's predictions go through
+    nms_3d class by class; the kept ones are written class by class (ascending id), each class in pick order, with pred_class_ids,
+    pred_RTs, pred_scales, pred_scores and -- where present -- pred_bboxes kept in step.  The boxes are the ones the metric scores:
+    extents pred_scales * cbrt(det pred_RTs[:3,:3]) (_unit_scale).  All (image, class) groups of the list are one nms_3d call (one
+    device call when `device` is given).  Returns new dicts (the other keys shared); the input is not modified."""
+    RTs, scales, scores, gid, where = [], [], [], [], []
+    n_groups = 0
+    for img, res in enumerate(final_results):
+        cls = np.asarray(res["pred_class_ids"]).reshape(-1)
+        k = len(cls)
+        if k == 0:
+            continue
+        rt = np.asarray(res["pred_RTs"], dtype=np.float64).reshape(-1, 4, 4)
+        sc = np.asarray(res["pred_scales"], dtype=np.float64).reshape(-1, 3)
+        s = np.asarray(res["pred_scores"], dtype=np.float64).reshape(-1)
+        if len(rt) != k or len(sc) != k or len(s) != k:
+            raise ValueError(f"image {img}: one class id, pose, scale and score per prediction")
+        with np.errstate(invalid="ignore"):
+            sc = sc * np.cbrt(np.linalg.det(np.where(np.isfinite(rt), rt, 0.0)[:, :3, :3]))[:, None]
+        classes, inv = np.unique(cls, return_inverse=True)
+        RTs.append(rt); scales.append(sc); scores.append(s); gid.append(n_groups + inv.reshape(-1))
+        where.append((img, len(classes)))
+        n_groups += len(classes)
+    picks = []
+    if RTs:
+        picks = nms_3d(np.concatenate(RTs), np.concatenate(scales), np.concatenate(scores), thresh, np.concatenate(gid), device)
+    out = [dict(res) for res in final_results]
+    g, first = 0, 0
+    for img, n_cls in where:
+        res = final_results[img]
+        keep = np.concatenate([picks[g + c] for c in range(n_cls)]).astype(np.int64) - first
+        for key in _NMS_PRED_KEYS:
+            if key in res:
+                out[img][key] = np.asarray(res[key])[keep]
+        g += n_cls
+        first += len(np.asarray(res["pred_class_ids"]).reshape(-1))
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ nocs/eval.py

@@ -186,20 +186,29 @@ def scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, *, angle_tol=1.5,
     return out
 
 
-def scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=5_000_000, seed=0, jitter=None, **kw):
+def frame_cloud(depth, intrinsics, cfg, jitter=None):
+    """the dense cloud of a whole frame and its normals, (hi f32[N,3], hi_nrm f32[N,3]) device tensors: frames.instance_cloud with
+    every pixel in the mask.  A function of (depth, intrinsics, cfg.res, cfg.knn, jitter) alone, so categories whose configs agree in
+    (res, knn) can share it (scene_frame's cloud=)."""
+    from .frames import instance_cloud
+    d = np.asarray(depth) if not isinstance(depth, torch.Tensor) else depth
+    return instance_cloud(depth, intrinsics, np.ones(tuple(d.shape), bool), cfg, jitter)
+
+
+def scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=5_000_000, seed=0, jitter=None, cloud=None, **kw):
     """One depth frame with NO instance masks -> scene_poses' dict: zero_shot_frame's pre-processing (nocs/zero_shot.ipynb cells 3-6:
     the cloud de-duplicated at res, the sparse cloud at 4 res, SPRIN features on the dense cloud, frames.draw_pairs(seed, 0, ...) --
     whose uniforms feed the bin decode -- and the "indistinguishable" pair filter), then scene_poses with the bin-head encoder.
-    depth [H,W] in millimetres (numpy uint16 or device); jitter: f32[n_pixels,3] standard-normal draws (None: none); kw:
-    scene_poses' options.  Adds hi_pc / hi_normals, indices, pc / normals, feat, idx, n_pairs (after the filter)."""
-    from .frames import draw_pairs, instance_cloud
+    depth [H,W] in millimetres (numpy uint16 or device); jitter: f32[n_pixels,3] standard-normal draws (None: none); cloud: the
+    (hi, hi_nrm) pair frame_cloud returned for this depth, intrinsics, jitter and a config with the same (res, knn) -- it replaces the
+    back-projection, the de-duplication and the normals (None: they are computed here: the same bits); kw: scene_poses' options.
+    Adds hi_pc / hi_normals, indices, pc / normals, feat, idx, n_pairs (after the filter)."""
+    from .frames import draw_pairs
     from .utils.util import sparse_quantize
     check_encoder(encoder, cfg)
     check_args(kw.get("max_proposals", 32), kw.get("thresh", 50), kw.get("margin", 10), kw.get("max_iters"))
     require_cuda()
-    d = np.asarray(depth) if not isinstance(depth, torch.Tensor) else depth
-    ones = np.ones(tuple(d.shape), bool)
-    hi, hi_nrm = instance_cloud(depth, intrinsics, ones, cfg, jitter)
+    hi, hi_nrm = frame_cloud(depth, intrinsics, cfg, jitter) if cloud is None else cloud
     if hi.shape[0] == 0:
         raise ValueError("the depth frame has no valid pixels")
     _, ind = sparse_quantize(hi, return_index=True, quantization_size=4 * cfg.res)
@@ -226,4 +235,4 @@ def _kept_positions(pc, nrm, idx):
     return pos.long()
 
 
-__all__ = ["scene_poses", "scene_frame", "backvote_multi", "segment_instances", "check_encoder", "check_args"]
+__all__ = ["scene_poses", "scene_frame", "frame_cloud", "backvote_multi", "segment_instances", "check_encoder", "check_args"]

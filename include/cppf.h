@@ -1122,6 +1122,38 @@ int cppf_pose_eval_match_pose(const double* err, const int32_t* pred_off, const 
                               const int32_t* keep_pred, const int32_t* keep_gt, int64_t n_pred, int64_t n_gt, int64_t n_pairs,
                               int32_t* pred_match, int32_t* gt_match, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Box NMS (sunrgbd/eval.py:13-35, csrc/box_nms.hip): greedy 3D non-maximum suppression over oriented boxes, every (image, class)
+ * group of a result set in one call -- a memset and two launches, no host synchronisation.  Host side and checker:
+ * cppf_amd/evaluation.py nms_3d.
+ *
+ * cppf_box_nms_batch: RT device f64[n,4,4] and scales device f64[n,3] in the form cppf_pose_eval_pairs reads (the rotation block
+ *   may carry an isotropic scale, it is normalised by cbrt(det); the last row is not read), scores device f64[n].  group_off_host
+ *   HOST i32[G+1], group_off[0] = 0, non-decreasing, group_off[G] = n: group g is the boxes [group_off[g], group_off[g+1]) -- one
+ *   (image, class) set.  Empty groups are legal anywhere.
+ *   Outputs: pick device i32[n]: the kept boxes of group g at pick[group_off[g] ..] in pick order, as indices WITHIN the group; the
+ *   rest of the group's slots hold -1.  n_pick device i32[G].  iou_out NULL or device f64[sum_g m_g (m_g - 1) / 2]: every group's
+ *   IoU upper triangle row by row (i < j), the groups in order -- there so that the IoUs can be pinned.
+ *   THE RULE (sunrgbd/eval.py:21-35): the boxes of a group are visited by descending score; a visited box that is not suppressed is
+ *   picked, and suppresses every later box whose IoU with it is STRICTLY greater than thresh (compared in fp64).
+ *   TIE RULE: of boxes with EQUAL scores the one with the HIGHER index goes first -- what a stable ascending argsort read from the
+ *   end gives.  (The reference's np.argsort leaves ties unspecified; they are this project's rule, pinned on nms_3d's host path.)
+ *   An IoU that is NaN compares false and suppresses nothing (the reference's iou_3d returns 0 on an exception).
+ *   The IoU of boxes i < j is the one cppf_pose_eval_pairs returns for the pair (i, j) with the same arrays on both sides and no
+ *   sweep, bit for bit (csrc/pose_eval_box.h is shared).  Degenerate boxes (non-finite entries, a singular rotation block,
+ *   non-positive extents, NaN scores) are the caller's duty, as there; nms_3d drops them before the upload.
+ *   Returns CPPF_EINVAL for null pointers (iou_out aside), negative sizes, a table that decreases, does not start at 0 or does not
+ *   end at n_boxes; CPPF_EUNSUPPORTED for a group of more than CPPF_BOX_NMS_GROUP_CAP boxes or more than 2^31 - 1 pairs in one call;
+ *   CPPF_EWORKSPACE for a workspace below cppf_box_nms_workspace_bytes(n_boxes, n_groups) (the group, pair and word offset tables,
+ *   uploaded inside the call, and the bit matrices: m rows of ceil(m / 64) 64-bit words per group, cleared by the call).
+ *   n_boxes == 0 or n_groups == 0 returns 0 and launches nothing (no output is written).
+ * ------------------------------------------------------------------------------------------- */
+#define CPPF_BOX_NMS_GROUP_CAP 1024
+size_t cppf_box_nms_workspace_bytes(int64_t n_boxes, int n_groups);
+int cppf_box_nms_batch(const double* RT, const double* scales, const double* scores, int64_t n_boxes, const int32_t* group_off_host,
+                       int n_groups, double thresh, int32_t* pick, int32_t* n_pick, double* iou_out, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

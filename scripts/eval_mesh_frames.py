@@ -17,6 +17,14 @@ smoothed peak's height above its box edges.  The APs go to profiles/scene_poses_
 threshold attached.
 
     python scripts/eval_mesh_frames.py --procedural --train-steps 3000 --train-pairs 200000 --frames 20 --objects 4 --mask-free
+
+--mask-free --nms T [--cross-category]: the frames go through cppf_amd.detections.frame_detections instead -- the same proposals, then
+the reference's scene-level post-processing (sunrgbd/eval.py: greedy 3D box NMS per class at IoU threshold T, on the device), and with
+--cross-category a second pass over the survivors of all categories.  The cut to the 20 best-scored predictions happens after the
+suppression.  The record (profiles/scene_detections_eval.json) holds the APs without NMS, with it per category and cross-category from
+the same frames and seeds, and the proposals kept / suppressed per category.  Again a first figure, no threshold.
+
+    python scripts/eval_mesh_frames.py --procedural --train-steps 3000 --train-pairs 200000 --frames 20 --objects 4 --mask-free --nms 0.3 --cross-category
 """
 import argparse
 import json
@@ -122,6 +130,42 @@ def _mask_free(args, sampler, encs, pencs, dev):
     return results, ms, n_prop, n_gt
 
 
+def _detections(args, sampler, encs, pencs, dev):
+    """--mask-free with --nms / --cross-category: every frame once through detections.frame_detections (no suppression: the
+    categories' proposals), then pooled three ways from those same proposals -- unfiltered (the run without --nms), NMS per category,
+    and, with --cross-category, the second pass over the survivors.  The cut to the 20 best-scored predictions of a frame (the
+    evaluation's match tables hold 20) happens after the suppression.  -> ({variant: records}, ms per frame (the proposals and the
+    per-category NMS), {variant: {category: [kept, suppressed]}}, proposals, ground truths)"""
+    from collections import OrderedDict
+    from cppf_amd.detections import frame_detections, pool_detections
+    names = sampler.synset_names
+    cats = list(sampler.categories)
+    variants = ["no_nms", "nms_per_category"] + (["nms_cross_category"] if args.cross_category else [])
+    results = {v: [] for v in variants}
+    counts = {v: {c: [0, 0] for c in cats} for v in variants}
+    ms, n_prop, n_gt = [], 0, 0
+    for i in range(args.frames):
+        fr = sampler.sample()
+        nets = OrderedDict((c, (pencs[c], encs[c], CATEGORIES[c])) for c in cats)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = frame_detections(fr.depth_mm, fr.intrinsics, nets, n_pairs=args.scene_pairs, seed=i, nms_thresh=args.nms,
+                               thresh=args.thresh, max_proposals=args.max_proposals)
+        ms.append((time.perf_counter() - t0) * 1e3)
+        pooled = dict(no_nms=pool_detections(res["outs"], cats, None, nms_thresh=None), nms_per_category=res)
+        if args.cross_category:
+            pooled["nms_cross_category"] = pool_detections(res["outs"], cats, None, nms_thresh=args.nms, cross_category=True, device=dev)
+        for v in variants:
+            dets = pooled[v]["detections"][:20]
+            results[v].append(_mask_free_record(fr, [(names.index(d["class_name"]), d["pose"], d["score"]) for d in dets]))
+            for c in cats:
+                counts[v][c][0] += pooled[v]["kept_per_category"][c]
+                counts[v][c][1] += pooled[v]["suppressed"][c]
+        n_prop += len(pooled["no_nms"]["detections"])
+        n_gt += len(fr.categories)
+    return results, ms, counts, n_prop, n_gt
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", action="append", help="CATEGORY=directory of OBJ files or names file (repeatable)")
@@ -140,10 +184,20 @@ def main():
     ap.add_argument("--thresh", type=float, default=50.0, help="--mask-free: the proposal loop's threshold")
     ap.add_argument("--max-proposals", type=int, default=6, help="--mask-free: proposals per category and frame (the 20 best-scored "
                     "predictions of a frame are evaluated)")
-    ap.add_argument("--out", default=None, help="default profiles/mesh_frames_eval.json (profiles/scene_poses_eval.json with --mask-free)")
+    ap.add_argument("--nms", type=float, default=None, metavar="T", help="--mask-free: the frames go through detections.frame_detections "
+                    "with 3D box NMS per category at IoU threshold T (the reference's 0.3); AP with and without it from the same frames")
+    ap.add_argument("--cross-category", action="store_true", help="--mask-free --nms: also a second NMS pass over the survivors of "
+                    "all categories (scores of different networks are not calibrated against each other)")
+    ap.add_argument("--out", default=None, help="default profiles/mesh_frames_eval.json (profiles/scene_poses_eval.json with --mask-free, "
+                    "profiles/scene_detections_eval.json with --nms)")
     args = ap.parse_args()
+    if args.cross_category and args.nms is None:
+        args.nms = 0.3
+    if args.nms is not None and not args.mask_free:
+        sys.exit("--nms / --cross-category belong to --mask-free")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "scene_poses_eval.json" if args.mask_free else "mesh_frames_eval.json")
+        args.out = os.path.join(ROOT, "profiles", "scene_detections_eval.json" if args.nms is not None else
+                                ("scene_poses_eval.json" if args.mask_free else "mesh_frames_eval.json"))
     dev = torch.device("cuda", 0)
     tmp = tempfile.TemporaryDirectory()
     if args.procedural:
@@ -170,6 +224,31 @@ def main():
         else:
             sys.exit(f"category {c}: --weights {c}=FILE or --train-steps N")
     sampler = MF.MeshFrameSampler(cat_paths, args.objects, device=dev, seed=args.seed)
+    if args.mask_free and args.nms is not None:
+        results, ms, counts, n_prop, n_gt = _detections(args, sampler, encs, pencs, dev)
+        deg, sh = [5, 10, 15], [5, 10, 15]
+        iou = [float(t) for t in np.round(np.linspace(0, 1, 101), 2)]
+        rec = dict(device=torch.cuda.get_device_name(0), mode="mask-free: detections.frame_detections on the whole depth image; the same "
+                   "proposals pooled without NMS, with NMS per category" + (" and with the cross-category pass" if args.cross_category else ""),
+                   frames=args.frames, objects_per_frame=args.objects, scene_pairs=args.scene_pairs, thresh=args.thresh,
+                   max_proposals=args.max_proposals, nms_thresh=args.nms, seed=args.seed, categories={c: len(p) for c, p in cat_paths.items()},
+                   procedural=bool(args.procedural), trained=trained, weights=weights, ground_truths=n_gt, proposals=n_prop,
+                   ms_per_frame_median=float(np.median(ms[min(1, len(ms) - 1):])), variants={},
+                   note="a first figure: no threshold is attached to these APs")
+        print(f"{args.frames} frames, {n_gt} ground truths, {n_prop} proposals; {rec['ms_per_frame_median']:.1f} ms per frame (all categories, NMS included)")
+        for v, recs in results.items():
+            iou_aps, pose_aps, _, _ = E.compute_degree_cm_mAP(recs, sampler.synset_names, None, deg, sh, iou, 0.1, True, device=dev)
+            one = dict(evaluated_predictions=int(sum(len(r["pred_class_ids"]) for r in recs)),
+                       kept_suppressed_per_category={c: dict(kept=k, suppressed=s_) for c, (k, s_) in counts[v].items()}, iou_ap={}, pose_ap={})
+            print(f"--- {v}: " + ", ".join(f"{c} kept {k} suppressed {s_}" for c, (k, s_) in counts[v].items()))
+            _tables(iou_aps, pose_aps, sampler.synset_names, list(cat_paths), deg, sh, one)
+            rec["variants"][v] = one
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(rec, fh, indent=1)
+            fh.write("\n")
+        tmp.cleanup()
+        return
     if args.mask_free:
         results, ms, n_prop, n_gt = _mask_free(args, sampler, encs, pencs, dev)
         deg, sh = [5, 10, 15], [5, 10, 15]
