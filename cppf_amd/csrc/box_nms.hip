@@ -21,7 +21,8 @@
 #include "pose_eval_box.h"
 
 #define NMS_CAP 1024               // boxes of one group (CPPF_BOX_NMS_GROUP_CAP): 16 words per row, one per lane of a quarter wavefront
-#define NMS_WORDS (NMS_CAP / 64)
+#define NMS_WORDS (NMS_CAP / 64)   // (tested: groups of 960, 961, 1023 and 1024 boxes, the refusal at 1025 and one call of 3000
+                                   // groups -- tests/test_gpu_limits.py)
 #define NMS_MAX_BLOCKS 2048        // nms_over_kernel's grid: 131 072 lanes, a single group of 513 boxes or more enters the stride loop
 #define NMS_MAX_PAIRS 0x7fffffffll
 

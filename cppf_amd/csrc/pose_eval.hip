@@ -23,7 +23,8 @@
 #define PE_SYM 20              // rotations of the up-symmetry sweep (utils/util.py:200-209)
 #define PE_SCAN_THREADS 1024
 #define PE_MATCH_THREADS 256
-#define PE_MAX_BLOCKS 8192
+#define PE_MAX_BLOCKS 8192     // x PE_LANES = 524 288 work items per trip of the stride loop (tested: 540 000 items, and a swept
+                               // pair whose 20 items cross the trip boundary -- tests/test_gpu_limits.py)
 #define PE_GROUP_CAP 32        // predictions / ground truths of one group (CPPF_POSE_EVAL_GROUP_CAP)
 
 static_assert(PE_GROUP_CAP == CPPF_POSE_EVAL_GROUP_CAP, "the claimed set is one u32");

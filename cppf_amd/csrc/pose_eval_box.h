@@ -90,7 +90,8 @@ __device__ __forceinline__ double pe_flux(const double* p, int m, double d)
 }
 
 // evaluation.box_intersection_volume: the faces of box A clipped by box B's closed half-spaces (+tol), then the faces of box B
-// clipped by box A's open ones (-tol).  buf: the lane's two polygon buffers, PE_MAXV * 3 * PE_LANES doubles apart.
+// clipped by box A's open ones (-tol); a half-space facing against the clipped face's normal is open either way.
+// buf: the lane's two polygon buffers, PE_MAXV * 3 * PE_LANES doubles apart.
 __device__ __forceinline__ double pe_volume(PeFrame A, PeFrame B, double* buf)
 {
     const double scale = fmax(fmax(fmax(A.h[0], A.h[1]), A.h[2]), fmax(fmax(B.h[0], B.h[1]), B.h[2]));
@@ -131,7 +132,11 @@ __device__ __forceinline__ double pe_volume(PeFrame A, PeFrame B, double* buf)
                         const double n0 = s2 * B.U[0][k2], n1 = s2 * B.U[1][k2], n2 = s2 * B.U[2][k2];
                         const double c0 = B.c[0] + sh2 * B.U[0][k2], c1 = B.c[1] + sh2 * B.U[1][k2], c2 = B.c[2] + sh2 * B.U[2][k2];
                         const double d2 = (n0 * c0 + n1 * c1) + n2 * c2;
-                        m = pe_clip(buf + cur * (PE_MAXV * 3 * PE_LANES), buf + (cur ^ 1) * (PE_MAXV * 3 * PE_LANES), m, n0, n1, n2, d2, tol);
+                        // a half-space that faces against this face's normal is open in both directions: boxes that touch from
+                        // opposite sides of a plane share no volume, their common face is no face of the intersection
+                        const bool against = (n[0] * n0 + n[1] * n1) + n[2] * n2 < 0.0;
+                        m = pe_clip(buf + cur * (PE_MAXV * 3 * PE_LANES), buf + (cur ^ 1) * (PE_MAXV * 3 * PE_LANES), m, n0, n1, n2, d2,
+                                    against ? -fabs(tol) : tol);
                         cur ^= 1;
                     }
                 }

@@ -27,7 +27,8 @@
 #define RS_TILE 16                    // screen tiles of 16 x 16 pixels: one 256-lane workgroup each
 #define RS_THREADS 256
 #define RS_MAX_DIM 8192               // W, H <= 8192
-#define RS_MAX_INST 65536             // instances of one cppf_raster_instances call
+#define RS_MAX_INST 65536             // instances of one cppf_raster_instances call (tested: 3100, four per lane of the scan,
+                                      // and the refusal at 65 537 -- tests/test_gpu_limits.py)
 
 static inline size_t rs_align(size_t b) { return (b + 255) & ~(size_t)255; }
 

@@ -10,8 +10,9 @@
 #define SCN_TILE 8                    // proposals: the max table holds one (value, first index) per 8^3 cells
 #define SCN_TILE_CELLS (SCN_TILE * SCN_TILE * SCN_TILE)
 #define SCN_LOOP_THREADS 1024
-#define SCN_MAX_RADIUS 32
-#define SCN_MAX_MARGIN 64             // an edge slice holds <= 2 * margin <= 128 cells: numpy's pairwise_sum base case
+#define SCN_MAX_RADIUS 32             // (tested at 0, 31 and 32; 33 is refused -- tests/test_gpu_limits.py)
+#define SCN_MAX_MARGIN 64             // an edge slice holds <= 2 * margin <= 128 cells: numpy's pairwise_sum base case (tested at
+                                      // 1 and 64 on a 140 x 137 x 131 grid -- tests/test_gpu_limits.py)
 
 struct GaussWeights { double w[2 * SCN_MAX_RADIUS + 1]; };
 struct TileMax { float v; int32_t i; };
@@ -314,6 +315,7 @@ __global__ __launch_bounds__(256) void pair_filter_kernel(const float* __restric
     }
 }
 
+// at most 16 384 workgroups of 256 lanes (tested: 4 194 304 + 333 pairs, every lane on its second trip or in the ragged tail)
 static int grid_blocks(int64_t n) { return (int)((n + 255) / 256 < 16384 ? ((n + 255) / 256 > 0 ? (n + 255) / 256 : 1) : 16384); }
 
 extern "C" int cppf_pair_filter_distinct(const float* pc, const float* nrm, const void* point_idxs, int idx_is_i64, int64_t n_points,

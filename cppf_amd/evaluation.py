@@ -97,7 +97,9 @@ def _flux(poly, n, d):
 def box_intersection_volume(c1, U1, h1, c2, U2, h2):
     """volume of the intersection of two oriented boxes: V = 1/3 * sum over the faces of the intersection polytope of
     (n . x) * area.  Those faces are the faces of box 1 clipped by box 2 and vice versa; a face the two boxes share
-    (coincident planes) is counted once: box 1's faces are clipped by closed half-spaces, box 2's by open ones."""
+    (coincident planes) is counted once: box 1's faces are clipped by closed half-spaces, box 2's by open ones.  A half-space
+    whose normal points against the face's own normal is open for both boxes: two boxes that touch from opposite sides of a
+    plane share no volume, and the face they share is a face of neither's intersection (counted once it would add d * area)."""
     f1, f2 = _faces(c1, U1, h1), _faces(c2, U2, h2)
     scale = float(max(h1.max(), h2.max()))
     tol = 1e-9 * scale
@@ -106,7 +108,8 @@ def box_intersection_volume(c1, U1, h1, c2, U2, h2):
         for n, d, quad in mine:
             poly = quad
             for n2, d2, _ in other:
-                poly = _clip(poly, n2, d2, t)
+                against = (n[0] * n2[0] + n[1] * n2[1]) + n[2] * n2[2] < 0.0
+                poly = _clip(poly, n2, d2, -tol if against else t)
                 if len(poly) < 3:
                     break
             total += _flux(poly, n, d)

@@ -880,7 +880,8 @@ int cppf_estimate_normals(const float* pc, const int32_t* nbrs, int64_t n_points
  *   (surv_mask device u8[n_pairs], cppf_backvote* at the proposal's centre): point_mask[n] = (n is an endpoint of more than
  *   min_contrib survivors, pairs (i, i) counting twice), then the survivors with either endpoint in the mask, in pair order:
  *   pairs_out device i32[n_pairs] (positions in the pair list), count device i32[1].  Integer atomics: the same result on every
- *   run.  point_idxs device i32[n_pairs,2]; workspace >= cppf_segment_instance_workspace_bytes().
+ *   run.  point_idxs device i32[n_pairs,2]; workspace >= cppf_segment_instance_workspace_bytes().  An endpoint outside
+ *   [0, n_points) is not counted and is in no instance; the pair's other endpoint counts as usual.
  * ------------------------------------------------------------------------------------------- */
 int cppf_pair_filter_distinct(const float* pc, const float* nrm, const void* point_idxs, int idx_is_i64, int64_t n_points,
                               int64_t n_pairs, uint8_t* keep, void* stream);

@@ -92,8 +92,9 @@ def raster_ref(vertices, faces, model, fx=M.FX, fy=M.FY, W=M.WIDTH, H=M.HEIGHT, 
     return depth
 
 
-def ray_cast(vertices, faces, model, fx=M.FX, fy=M.FY, W=M.WIDTH, H=M.HEIGHT, cull=True, chunk=4096):
-    """fp64 Moller-Trumbore through every pixel centre: depth f64[H,W] (0 = miss).  Front face: CCW seen from the camera."""
+def ray_cast(vertices, faces, model, fx=M.FX, fy=M.FY, W=M.WIDTH, H=M.HEIGHT, cull=True, chunk=4096, pixels=None):
+    """fp64 Moller-Trumbore through every pixel centre: depth f64[H,W] (0 = miss).  Front face: CCW seen from the camera.
+    pixels: flat indices (row * W + column) -> the depths of those pixels only, as a vector"""
     m = np.asarray(model, np.float64)
     v = np.asarray(vertices, np.float64) @ m[:3, :3].T + m[:3, 3]
     tri = v[np.asarray(faces)]
@@ -105,7 +106,9 @@ def ray_cast(vertices, faces, model, fx=M.FX, fy=M.FY, W=M.WIDTH, H=M.HEIGHT, cu
     ndx = 2 * (cc.ravel() + 0.5) / W - 1
     ndy = 2 * (H - rr.ravel() - 0.5) / H - 1
     dirs = np.stack([ndx / (2 * fx / W), ndy / (2 * fy / H), -np.ones_like(ndx)], -1)
-    out = np.zeros(W * H)
+    if pixels is not None:
+        dirs = dirs[np.asarray(pixels)]
+    out = np.zeros(dirs.shape[0])
     for s in range(0, dirs.shape[0], chunk):
         dv = dirs[s:s + chunk]
         p = np.cross(dv[:, None, :], e2[None])
@@ -120,11 +123,12 @@ def ray_cast(vertices, faces, model, fx=M.FX, fy=M.FY, W=M.WIDTH, H=M.HEIGHT, cu
         hit = (np.abs(det) > 1e-300) & (u >= 0) & (w >= 0) & (u + w <= 1) & (t > 0)
         t = np.where(hit, t, np.inf).min(1)
         out[s:s + chunk] = np.where(np.isinf(t), 0, t)
-    return out.reshape(H, W)
+    return out.reshape(H, W) if pixels is None else out
 
 
-def edge_distance(vertices, faces, model, fx=M.FX, fy=M.FY, W=M.WIDTH, H=M.HEIGHT):
-    """per pixel centre, the distance in pixels to the nearest projected triangle edge (fp64; no clipping)"""
+def edge_distance(vertices, faces, model, fx=M.FX, fy=M.FY, W=M.WIDTH, H=M.HEIGHT, pixels=None):
+    """per pixel centre, the distance in pixels to the nearest projected triangle edge (fp64; no clipping).
+    pixels: flat indices (row * W + column) -> the distances of those pixels only, as a vector"""
     m = np.asarray(model, np.float64)
     v = np.asarray(vertices, np.float64) @ m[:3, :3].T + m[:3, 3]
     d = -v[:, 2]
@@ -136,6 +140,8 @@ def edge_distance(vertices, faces, model, fx=M.FX, fy=M.FY, W=M.WIDTH, H=M.HEIGH
     b = np.concatenate([s[f[:, 1]], s[f[:, 2]], s[f[:, 0]]])
     cc, rr = np.meshgrid(np.arange(W) + 0.5, np.arange(H) + 0.5)
     P = np.stack([cc.ravel(), rr.ravel()], -1)
+    if pixels is not None:
+        P = P[np.asarray(pixels)]
     best = np.full(P.shape[0], np.inf)
     ab = b - a
     L2 = np.maximum((ab * ab).sum(-1), 1e-300)
@@ -144,7 +150,7 @@ def edge_distance(vertices, faces, model, fx=M.FX, fy=M.FY, W=M.WIDTH, H=M.HEIGH
         t = np.clip((ap * ab[None, k:k + 256]).sum(-1) / L2[None, k:k + 256], 0, 1)
         dd = np.linalg.norm(ap - t[..., None] * ab[None, k:k + 256], axis=-1)
         best = np.minimum(best, dd.min(1))
-    return best.reshape(H, W)
+    return best.reshape(H, W) if pixels is None else best
 
 
 # ------------------------------------------------------------------------------------------------------------- meshes

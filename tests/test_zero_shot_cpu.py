@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import limits_cases as LC  # noqa: E402
 import zero_shot_ref as Z  # noqa: E402
 
 from cppf_amd import zero_shot  # noqa: E402
@@ -56,6 +57,30 @@ def test_smooth_equals_scipy(sigma):
     for shape in [(1, 1, 1), (1, 2, 3), (2, 9, 1), (3, 5, 9), (9, 9, 9), (17, 4, 6)]:
         g = (rng.random(shape) * 300).astype(np.float32)
         assert Z.smooth(g, sigma).tobytes() == ndi.gaussian_filter(g, sigma=sigma).tobytes(), shape
+
+
+@pytest.mark.parametrize("sigma,truncate,radius", LC.SMOOTH_PARAMS)
+def test_smooth_equals_scipy_at_the_radius_limits(sigma, truncate, radius):
+    """radius 0, 31 and 32 (csrc/scene.hip SCN_MAX_RADIUS) on the grids of tests/test_gpu_limits.py: lines shorter than the radius
+    included, where scipy's reflection repeats"""
+    ndi = pytest.importorskip("scipy.ndimage")
+    assert (Z.gaussian_weights(sigma, truncate).shape[0] - 1) // 2 == radius
+    for shape in LC.SMOOTH_GRIDS:
+        g = LC.smooth_grid_case(shape)
+        assert Z.smooth(g, sigma, truncate).tobytes() == ndi.gaussian_filter(g, sigma=sigma, truncate=truncate).tobytes(), shape
+
+
+def test_restatement_equals_notebook_cell9_at_margin_64_and_1(golden):
+    """tests/golden/zero_shot_margins.npz: the notebook's cell 9 with its margin set to the documented limits, on the grids of
+    tests/limits_cases.py (edge slices of 128 cells -- the whole of np.mean's base case -- and boxes clipped at both ends)"""
+    g = golden("zero_shot_margins.npz")
+    for name, sm in (("peaks", LC.margin_grid_smoothed()), ("thin", Z.smooth(LC.smooth_grid_case((33, 7, 70))))):
+        for margin in (64, 1):
+            key = f"{name}.m{margin}"
+            loc, val, diff, _ = Z.proposals(sm, float(g[f"{key}.thresh"]), margin, max_proposals=64, max_iters=64)
+            k = _dedupe(g[f"{key}.loc"], g[f"{key}.diff"])
+            assert len(k) >= 2 and np.array_equal(loc, g[f"{key}.loc"][k]), key
+            assert val.tobytes() == g[f"{key}.value"][k].tobytes() and diff.tobytes() == g[f"{key}.diff"][k].tobytes(), key
 
 
 def test_np_mean_order():

@@ -114,23 +114,31 @@ def world(loc, corner, res):
 
 
 def distinct_mask(pc, nrm, idx):
-    """cell 6: True for the pairs kept (not 'indistinguishable'), float32 throughout"""
+    """cell 6: True for the pairs kept (not 'indistinguishable'), float32 throughout.  Defined where the notebook is not
+    (include/cppf.h cppf_pair_filter_distinct): a pair with an endpoint outside [0, n_points) is dropped."""
     pc, nrm = np.asarray(pc, _f), np.asarray(nrm, _f)
+    idx = np.asarray(idx, np.int64)
+    ok = ((idx >= 0) & (idx < pc.shape[0])).all(1)
+    idx = np.where(ok[:, None], idx, 0)
     n1, n2 = nrm[idx[:, 0]], nrm[idx[:, 1]]
     ab = pc[idx[:, 0]] - pc[idx[:, 1]]
     ab /= (np.linalg.norm(ab, axis=-1, keepdims=True) + 1e-7)
     ppf = np.stack([np.sum(n1 * n2, -1), np.sum(ab * n1, -1), np.sum(ab * n2, -1)], -1)
     mask = (np.abs(ppf[:, 0]) > 0.9) & (np.abs(ppf[:, 1]) < 0.1) & (np.abs(ppf[:, 2]) < 0.1)
-    return ~mask
+    return ~mask & ok
 
 
 def segment(idx, surv_mask, n_points, min_contrib=12):
-    """cell 11's unsupervised segmentation: (point mask bool[N], positions i64[M] of the kept pairs in the full list)"""
+    """cell 11's unsupervised segmentation: (point mask bool[N], positions i64[M] of the kept pairs in the full list).  Defined
+    where the notebook is not (include/cppf.h cppf_segment_instance): an endpoint outside [0, n_points) is not counted and is in
+    no instance; the pair's other endpoint counts as usual."""
     idx = np.asarray(idx, np.int64)
     pos = np.nonzero(surv_mask)[0]
-    cnt = np.bincount(idx[pos].reshape(-1), minlength=n_points)
+    ends = idx[pos]
+    ok = (ends >= 0) & (ends < n_points)
+    cnt = np.bincount(ends[ok], minlength=n_points)
     pm = cnt > min_contrib
-    keep = pm[idx[pos, 0]] | pm[idx[pos, 1]]
+    keep = (ok & pm[np.where(ok, ends, 0)]).any(1)
     return pm, pos[keep]
 
 
