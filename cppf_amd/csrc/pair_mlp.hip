@@ -170,14 +170,7 @@ __global__ __launch_bounds__(256) void point_proj_batch_kernel(ProjBatch B)
     if ((int64_t)blockIdx.x * PROJ_PPB >= B.N[i]) return;
     point_proj_body(B.feat[i], B.packed[i], B.table[i], B.N[i]);
 }
-// The same launch for the bf16 encoder (pair_mlp_bf16.hip): its image keeps the fp32 layer-0 section at OFF_WPT / OFF_BPT, so the
-// tables of both precisions come from this one kernel.
-__attribute__((visibility("hidden"))) int pair_point_proj_batch(const ProjBatch& PJ, unsigned blocks, int n_items, hipStream_t st)
-{
-    hipLaunchKernelGGL(point_proj_batch_kernel, dim3(blocks, (unsigned)n_items), dim3(256), 0, st, PJ);
-    CPPF_CHECK_LAUNCH();
-    return 0;
-}
+// (the bf16 image keeps the fp32 layer-0 section at OFF_WPT / OFF_BPT, so the tables of both precisions come from these kernels)
 
 // The kernel's body for workgroup `wg` of the `n_wg` that share the pair list of `A` (one launch = one list: wg = blockIdx.x of
 // gridDim.x; a batched launch = several lists, each with its own workgroups: pair_mlp_batch_kernel).
@@ -666,29 +659,88 @@ extern "C" size_t cppf_pair_mlp_workspace_bytes(int64_t N, int F, const int* dim
     return is_std(F, dims, n_res, out_dim) ? (size_t)N * PROJ_COLS * sizeof(float) : 0;
 }
 
+// the standard architecture with the bin counts and the width the fused decode is written for
+static bool is_std_decode(int F, const int* dims, int n_res, int out_dim, int tr_bins, int rot_bins)
+{
+    return is_std(F, dims, n_res, out_dim) && tr_bins == 32 && rot_bins == 36 && out_dim == 141;
+}
+
+// The launch geometry of cppf_pair_mlp_decode_batch for lists of n_pairs[i] pairs: workgroups in proportion to the lists' tiles, at
+// least one each, as many in all as one list alone would get (wg_begin[n + 1]); with 1, 2, 4 or 8 lists within 10 % of each other
+// and a grid of at least 8 the XCD-aware form (per_xcd = 8 / n > 0, the grid rounded down to a multiple of 8).
+static void batch_plan(int n_items, const int64_t* n_pairs, int* wg_begin, int* per_xcd, int* grid)
+{
+    int64_t tiles_all = 0, tmin = INT64_MAX, tmax = 0;
+    for (int i = 0; i < n_items; ++i) {
+        const int64_t tiles = (n_pairs[i] + 15) / 16;
+        tiles_all += tiles;
+        tmin = tiles < tmin ? tiles : tmin; tmax = tiles > tmax ? tiles : tmax;
+    }
+    const int total = mlp_grid(tiles_all * 16) < n_items ? n_items : mlp_grid(tiles_all * 16);
+    int given = 0;
+    for (int i = 0; i < n_items; ++i) {
+        const int64_t tiles = (n_pairs[i] + 15) / 16;
+        int w = (int)((tiles * total + tiles_all - 1) / tiles_all);
+        const int left = total - given - (n_items - 1 - i);
+        if (w > left) w = left;
+        if (w < 1) w = 1;
+        wg_begin[i] = given;
+        given += w;
+    }
+    wg_begin[n_items] = given;
+    *per_xcd = 0;
+    if (8 % n_items == 0 && tmax * 10 <= tmin * 11 && given >= 8) {
+        *per_xcd = 8 / n_items;
+        given = given / 8 * 8;
+    }
+    *grid = given;
+}
+
+// ---- the fp32 kernels as a PairVariant (pair_mlp_common.h); the attribute once per kernel
+#define STD_LDS_BYTES ((STD_LDS + 128) * sizeof(float))
 template <bool LOGITS, bool DECODE, bool HEADS, bool SEL = false>
-static int launch_std(MlpArgs& A, int64_t N, void* workspace, size_t workspace_bytes, hipStream_t st)
+static int launch_kernel(const MlpArgs& A, size_t lds, hipStream_t st)
+{
+    static bool attr_done = false;
+    if (!attr_done) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_mlp_kernel<LOGITS, DECODE, HEADS, SEL>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+        attr_done = true;
+    }
+    hipLaunchKernelGGL((pair_mlp_kernel<LOGITS, DECODE, HEADS, SEL>), dim3(mlp_grid(A.P)), dim3(MLP_THREADS), lds, st, A);
+    CPPF_CHECK_LAUNCH();
+    return 0;
+}
+static int launch_batch(const MlpBatch& B, bool heads, bool sel, unsigned grid, size_t lds, hipStream_t st);
+static const PairVariant PAIR_FP32 = {STD_LDS_BYTES, launch_kernel<true, false, false>, launch_batch, /* skip_empty */ false};
+
+// The checks of the MFMA path and the per-point table of one cloud (`project` false: the SEL pass reuses the table its first pass
+// left in the same workspace)
+static int std_table(MlpArgs& A, int64_t N, void* workspace, size_t workspace_bytes, bool project, hipStream_t st)
 {
     if (N < 1) return CPPF_EINVAL;
     if (N >= (1ll << 23) || A.P >= (1ll << 27)) return CPPF_EUNSUPPORTED;   // 32-bit byte offsets inside the kernel
     if (!workspace || workspace_bytes < (size_t)N * PROJ_COLS * sizeof(float)) return CPPF_EWORKSPACE;
     float* table = static_cast<float*>(workspace);
-    if (!SEL) {   // (the SEL pass reuses the table the first pass left in the same workspace)
+    if (project) {
         hipLaunchKernelGGL(point_proj_kernel, dim3((unsigned)((N + PROJ_PPB - 1) / PROJ_PPB)), dim3(256), 0, st, A.feat, A.packed, table, N);
         CPPF_CHECK_LAUNCH();
     }
     A.table = table;
-    static bool attr_done = false;
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&pair_mlp_kernel<LOGITS, DECODE, HEADS, SEL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (STD_LDS + 128) * sizeof(float));
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((pair_mlp_kernel<LOGITS, DECODE, HEADS, SEL>), dim3(mlp_grid(A.P)), dim3(MLP_THREADS),
-                       (STD_LDS + 128) * sizeof(float), st, A);
-    CPPF_CHECK_LAUNCH();
     return 0;
+}
+int pair_std_forward(const PairVariant& V, MlpArgs& A, int64_t N, void* workspace, size_t workspace_bytes, hipStream_t st)
+{
+    const int rc = std_table(A, N, workspace, workspace_bytes, true, st);
+    return rc != 0 ? rc : V.launch_logits(A, V.lds_bytes, st);
+}
+// the fp32 single-list entries: pair_mlp_kernel, not the batch of one
+template <bool LOGITS, bool DECODE, bool HEADS, bool SEL = false>
+static int launch_std(MlpArgs& A, int64_t N, void* workspace, size_t workspace_bytes, hipStream_t st)
+{
+    const int rc = std_table(A, N, workspace, workspace_bytes, !SEL, st);
+    return rc != 0 ? rc : launch_kernel<LOGITS, DECODE, HEADS, SEL>(A, STD_LDS_BYTES, st);
 }
 
 extern "C" int cppf_pair_mlp_forward(const float* pc, const float* nrm, const float* feat, const void* idxs,
@@ -704,7 +756,7 @@ extern "C" int cppf_pair_mlp_forward(const float* pc, const float* nrm, const fl
         MlpArgs A = {};
         A.pc = pc; A.nrm = nrm; A.feat = feat; A.idxs = idxs; A.packed = packed; A.out = out; A.P = P;
         A.out_dim = out_dim; A.idx64 = idx_is_i64;
-        return launch_std<true, false, false>(A, N, workspace, workspace_bytes, st);
+        return pair_std_forward(PAIR_FP32, A, N, workspace, workspace_bytes, st);
     }
     if (!gen_ok(F, dims, n_res, out_dim)) return CPPF_EUNSUPPORTED;
     GenArgs G = {};
@@ -733,7 +785,7 @@ extern "C" int cppf_pair_mlp_decode(const float* pc, const float* nrm, const flo
                                     void* workspace, size_t workspace_bytes, void* stream)
 {
     if (P < 0 || !dims) return CPPF_EINVAL;
-    if (!is_std(F, dims, n_res, out_dim) || tr_bins != 32 || rot_bins != 36 || out_dim != 141) return CPPF_EUNSUPPORTED;
+    if (!is_std_decode(F, dims, n_res, out_dim, tr_bins, rot_bins)) return CPPF_EUNSUPPORTED;
     if (P == 0) return 0;
     if (!pc || !nrm || !feat || !idxs || !packed || !u_tr || !outputs) return CPPF_EINVAL;
     if ((heads != nullptr) != (u_rot != nullptr)) return CPPF_EINVAL;
@@ -757,79 +809,104 @@ extern "C" int cppf_pair_mlp_batch_plan(int n_items, const int64_t* n_pairs, int
     return 0;
 }
 
-extern "C" int cppf_pair_mlp_decode_batch(int n_items, const CppfPairMlpItem* items, int F, const int* dims, int n_res, int out_dim,
-                                          int tr_bins, int rot_bins, void* stream)
+static int launch_batch(const MlpBatch& B, bool heads, bool sel, unsigned grid, size_t lds, hipStream_t st)
 {
-    if (n_items < 1 || n_items > MLP_BATCH_MAX || !items || !dims) return CPPF_EINVAL;
-    if (!is_std(F, dims, n_res, out_dim) || tr_bins != 32 || rot_bins != 36 || out_dim != 141) return CPPF_EUNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    MlpBatch B = {};
-    B.n = n_items;
-    const bool heads = items[0].heads != nullptr;
-    int64_t n_pairs[MLP_BATCH_MAX];
-    int given = 0;
-    for (int i = 0; i < n_items; ++i) {
-        const CppfPairMlpItem& it = items[i];
-        n_pairs[i] = it.n_pairs;
-        if (it.n_pairs < 1 || it.n_points < 1) return CPPF_EINVAL;
-        if (!it.pc || !it.nrm || !it.feat || !it.idxs || !it.packed || !it.u_tr || !it.outputs) return CPPF_EINVAL;
-        if ((it.heads != nullptr) != heads || (it.heads != nullptr) != (it.u_rot != nullptr)) return CPPF_EINVAL;
-        if (it.n_points >= (1ll << 23) || it.n_pairs >= (1ll << 27)) return CPPF_EUNSUPPORTED;
-        if (!it.workspace || it.workspace_bytes < (size_t)it.n_points * PROJ_COLS * sizeof(float)) return CPPF_EWORKSPACE;
-    }
-    batch_plan(n_items, n_pairs, B.wg_begin, &B.per_xcd, &given);
-    ProjBatch PJ = {};
-    int64_t proj_blocks = 1;
-    for (int i = 0; i < n_items; ++i) {
-        const CppfPairMlpItem& it = items[i];
-        float* table = static_cast<float*>(it.workspace);
-        PJ.feat[i] = it.feat; PJ.packed[i] = it.packed; PJ.table[i] = table; PJ.N[i] = it.n_points;
-        const int64_t nb = (it.n_points + PROJ_PPB - 1) / PROJ_PPB;
-        proj_blocks = nb > proj_blocks ? nb : proj_blocks;
-        MlpArgs& A = B.item[i];
-        A.pc = it.pc; A.nrm = it.nrm; A.feat = it.feat; A.idxs = it.idxs; A.packed = it.packed; A.P = it.n_pairs; A.out_dim = out_dim;
-        A.idx64 = it.idx_is_i64; A.u_tr = it.u_tr; A.u_rot = it.u_rot; A.outputs = it.outputs; A.heads = it.heads;
-        A.vr0 = it.vr0; A.vr1 = it.vr1; A.table = table;
-    }
-    // the per-point projections of all lists in ONE launch (round 5: n launches of ~5 us each in front of the pair kernel before)
-    hipLaunchKernelGGL(point_proj_batch_kernel, dim3((unsigned)proj_blocks, (unsigned)n_items), dim3(256), 0, st, PJ);
-    CPPF_CHECK_LAUNCH();
-    static bool attr_done[2] = {false, false};
-    const void* fn = heads ? reinterpret_cast<const void*>(&pair_mlp_batch_kernel<true>) : reinterpret_cast<const void*>(&pair_mlp_batch_kernel<false>);
-    if (!attr_done[heads]) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (STD_LDS + 128) * sizeof(float));
+    static bool attr_done[3] = {false, false, false};
+    const int v = sel ? 2 : heads;
+    const void* fn = v == 1 ? reinterpret_cast<const void*>(&pair_mlp_batch_kernel<true>)
+                   : v == 0 ? reinterpret_cast<const void*>(&pair_mlp_batch_kernel<false>) : reinterpret_cast<const void*>(&pair_mlp_batch_kernel<true, true>);
+    if (!attr_done[v]) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
-        attr_done[heads] = true;
+        attr_done[v] = true;
     }
-    if (heads) hipLaunchKernelGGL((pair_mlp_batch_kernel<true>), dim3((unsigned)given), dim3(MLP_THREADS), (STD_LDS + 128) * sizeof(float), st, B);
-    else hipLaunchKernelGGL((pair_mlp_batch_kernel<false>), dim3((unsigned)given), dim3(MLP_THREADS), (STD_LDS + 128) * sizeof(float), st, B);
+    if (v == 1) hipLaunchKernelGGL((pair_mlp_batch_kernel<true>), dim3(grid), dim3(MLP_THREADS), lds, st, B);
+    else if (v == 0) hipLaunchKernelGGL((pair_mlp_batch_kernel<false>), dim3(grid), dim3(MLP_THREADS), lds, st, B);
+    else hipLaunchKernelGGL((pair_mlp_batch_kernel<true, true>), dim3(grid), dim3(MLP_THREADS), lds, st, B);
     CPPF_CHECK_LAUNCH();
     return 0;
 }
 
-// The second pass (cppf_pair_mlp_decode_sel) for several pair lists in ONE launch: workgroups [w_i, w_{i+1}) work on list i's
-// survivors; every list's per-point table is the one its first pass left in item.workspace.  Items with max_sel == 0 are skipped.
-extern "C" int cppf_pair_mlp_decode_sel_batch(int n_items, const CppfPairMlpItem* items, int F, const int* dims, int n_res, int out_dim,
-                                              int tr_bins, int rot_bins, void* stream)
+// ---- the item contract of the two batch entries, once for both encoders
+static int item_limits(const CppfPairMlpItem& it)   // 32-bit byte offsets inside the kernels
+{
+    return it.n_points >= (1ll << 23) || it.n_pairs >= (1ll << 27) ? CPPF_EUNSUPPORTED : 0;
+}
+static int item_workspace(const CppfPairMlpItem& it)
+{
+    return !it.workspace || it.workspace_bytes < (size_t)it.n_points * PROJ_COLS * sizeof(float) ? CPPF_EWORKSPACE : 0;
+}
+// what both passes hand to the kernel; the first pass adds u_tr / outputs / vote ranges, the second sel / n_sel
+static MlpArgs item_args(const CppfPairMlpItem& it, int out_dim, int64_t P)
+{
+    MlpArgs A = {};
+    A.pc = it.pc; A.nrm = it.nrm; A.feat = it.feat; A.idxs = it.idxs; A.packed = it.packed; A.P = P; A.out_dim = out_dim;
+    A.idx64 = it.idx_is_i64; A.u_rot = it.u_rot; A.heads = it.heads; A.table = static_cast<const float*>(it.workspace);
+    return A;
+}
+
+int pair_decode_batch(const PairVariant& V, int n_items, const CppfPairMlpItem* items, int F, const int* dims, int n_res, int out_dim,
+                      int tr_bins, int rot_bins, hipStream_t st)
 {
     if (n_items < 1 || n_items > MLP_BATCH_MAX || !items || !dims) return CPPF_EINVAL;
-    if (!is_std(F, dims, n_res, out_dim) || tr_bins != 32 || rot_bins != 36 || out_dim != 141) return CPPF_EUNSUPPORTED;
+    if (!is_std_decode(F, dims, n_res, out_dim, tr_bins, rot_bins)) return CPPF_EUNSUPPORTED;
+    MlpBatch B = {};
+    const CppfPairMlpItem* live[MLP_BATCH_MAX];
+    for (int i = 0; i < n_items; ++i) {
+        if (V.skip_empty) {   // (n_pairs == 0: nothing to do for that list, the launch serves the others)
+            if (items[i].n_pairs < 0) return CPPF_EINVAL;
+            if (items[i].n_pairs == 0) continue;
+        }
+        live[B.n++] = &items[i];
+    }
+    if (B.n == 0) return 0;
+    const bool heads = live[0]->heads != nullptr;
+    ProjBatch PJ = {};
+    int64_t n_pairs[MLP_BATCH_MAX], proj_blocks = 1;
+    for (int i = 0; i < B.n; ++i) {
+        const CppfPairMlpItem& it = *live[i];
+        if (it.n_pairs < 1 || it.n_points < 1) return CPPF_EINVAL;
+        if (!it.pc || !it.nrm || !it.feat || !it.idxs || !it.packed || !it.u_tr || !it.outputs) return CPPF_EINVAL;
+        if ((it.heads != nullptr) != heads || (it.heads != nullptr) != (it.u_rot != nullptr)) return CPPF_EINVAL;
+        if (int rc = item_limits(it)) return rc;
+        if (int rc = item_workspace(it)) return rc;
+        n_pairs[i] = it.n_pairs;
+        PJ.feat[i] = it.feat; PJ.packed[i] = it.packed; PJ.table[i] = static_cast<float*>(it.workspace); PJ.N[i] = it.n_points;
+        const int64_t nb = (it.n_points + PROJ_PPB - 1) / PROJ_PPB;
+        proj_blocks = nb > proj_blocks ? nb : proj_blocks;
+        MlpArgs& A = B.item[i] = item_args(it, out_dim, it.n_pairs);
+        A.u_tr = it.u_tr; A.outputs = it.outputs; A.vr0 = it.vr0; A.vr1 = it.vr1;
+    }
+    int given = 0;
+    batch_plan(B.n, n_pairs, B.wg_begin, &B.per_xcd, &given);
+    // the per-point projections of all lists in ONE launch (n launches of ~5 us each in front of the pair kernel otherwise)
+    hipLaunchKernelGGL(point_proj_batch_kernel, dim3((unsigned)proj_blocks, (unsigned)B.n), dim3(256), 0, st, PJ);
+    CPPF_CHECK_LAUNCH();
+    return V.launch_batch(B, heads, false, (unsigned)given, V.lds_bytes, st);
+}
+
+// The second pass (cppf_pair_mlp_decode_sel) for several pair lists in ONE launch: workgroups [w_i, w_{i+1}) work on list i's
+// survivors; every list's per-point table is the one its first pass left in item.workspace.  Items with n_pairs == 0 or
+// max_sel == 0 are skipped.
+int pair_decode_sel_batch(const PairVariant& V, int n_items, const CppfPairMlpItem* items, int F, const int* dims, int n_res, int out_dim,
+                          int tr_bins, int rot_bins, hipStream_t st)
+{
+    if (n_items < 1 || n_items > MLP_BATCH_MAX || !items || !dims) return CPPF_EINVAL;
+    if (!is_std_decode(F, dims, n_res, out_dim, tr_bins, rot_bins)) return CPPF_EUNSUPPORTED;
     MlpBatch B = {};
     int given = 0;
     for (int i = 0; i < n_items; ++i) {
         const CppfPairMlpItem& it = items[i];
         if (it.n_pairs < 0 || it.max_sel < 0) return CPPF_EINVAL;
         if (it.n_pairs == 0 || it.max_sel == 0) continue;
-        if (it.n_pairs >= (1ll << 27) || it.n_points >= (1ll << 23)) return CPPF_EUNSUPPORTED;
+        if (int rc = item_limits(it)) return rc;
+        if (it.n_points < 1) return CPPF_EINVAL;
         if (!it.pc || !it.nrm || !it.feat || !it.idxs || !it.packed || !it.u_rot || !it.sel || !it.n_sel_dev || !it.heads) return CPPF_EINVAL;
-        if (!it.workspace || it.workspace_bytes < (size_t)it.n_points * PROJ_COLS * sizeof(float)) return CPPF_EWORKSPACE;
-        MlpArgs& A = B.item[B.n];
-        A.pc = it.pc; A.nrm = it.nrm; A.feat = it.feat; A.idxs = it.idxs; A.packed = it.packed; A.out_dim = out_dim;
-        A.P = it.max_sel < it.n_pairs ? it.max_sel : it.n_pairs;
-        A.idx64 = it.idx_is_i64; A.u_rot = it.u_rot; A.heads = it.heads; A.sel = it.sel; A.n_sel = it.n_sel_dev;
-        A.table = static_cast<const float*>(it.workspace);
+        if (int rc = item_workspace(it)) return rc;
+        MlpArgs& A = B.item[B.n] = item_args(it, out_dim, it.max_sel < it.n_pairs ? it.max_sel : it.n_pairs);
+        A.sel = it.sel; A.n_sel = it.n_sel_dev;
         B.wg_begin[B.n] = given;
-        // (a launch cannot know the survivor counts: every list gets the workgroups of its capacity, at most a quarter of the chip's
+        // (a launch cannot know the survivor counts: every list gets the workgroups of its capacity, at most half of the chip's
         // round when several lists share it; surplus workgroups exit at once)
         int w = mlp_grid(A.P);
         const int cap = mlp_grid(1ll << 26) / (n_items > 1 ? 2 : 1);
@@ -839,17 +916,18 @@ extern "C" int cppf_pair_mlp_decode_sel_batch(int n_items, const CppfPairMlpItem
     }
     if (B.n == 0) return 0;
     B.wg_begin[B.n] = given;
-    static bool attr_done = false;
-    const void* fn = reinterpret_cast<const void*>(&pair_mlp_batch_kernel<true, true>);
-    if (!attr_done) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (STD_LDS + 128) * sizeof(float));
-        if (e != hipSuccess) return (int)e;
-        attr_done = true;
-    }
-    hipLaunchKernelGGL((pair_mlp_batch_kernel<true, true>), dim3((unsigned)given), dim3(MLP_THREADS), (STD_LDS + 128) * sizeof(float),
-                       (hipStream_t)stream, B);
-    CPPF_CHECK_LAUNCH();
-    return 0;
+    return V.launch_batch(B, true, true, (unsigned)given, V.lds_bytes, st);
+}
+
+extern "C" int cppf_pair_mlp_decode_batch(int n_items, const CppfPairMlpItem* items, int F, const int* dims, int n_res, int out_dim,
+                                          int tr_bins, int rot_bins, void* stream)
+{
+    return pair_decode_batch(PAIR_FP32, n_items, items, F, dims, n_res, out_dim, tr_bins, rot_bins, (hipStream_t)stream);
+}
+extern "C" int cppf_pair_mlp_decode_sel_batch(int n_items, const CppfPairMlpItem* items, int F, const int* dims, int n_res, int out_dim,
+                                              int tr_bins, int rot_bins, void* stream)
+{
+    return pair_decode_sel_batch(PAIR_FP32, n_items, items, F, dims, n_res, out_dim, tr_bins, rot_bins, (hipStream_t)stream);
 }
 
 extern "C" int cppf_pair_mlp_decode_sel(const float* pc, const float* nrm, const float* feat, const void* idxs,
@@ -859,7 +937,7 @@ extern "C" int cppf_pair_mlp_decode_sel(const float* pc, const float* nrm, const
                                         void* workspace, size_t workspace_bytes, void* stream)
 {
     if (P < 0 || max_sel < 0 || !dims) return CPPF_EINVAL;
-    if (!is_std(F, dims, n_res, out_dim) || tr_bins != 32 || rot_bins != 36 || out_dim != 141) return CPPF_EUNSUPPORTED;
+    if (!is_std_decode(F, dims, n_res, out_dim, tr_bins, rot_bins)) return CPPF_EUNSUPPORTED;
     if (P == 0 || max_sel == 0) return 0;
     if (P >= (1ll << 27)) return CPPF_EUNSUPPORTED;   // rows come from sel[] and range over the whole pair list: 32-bit offsets
     if (!pc || !nrm || !feat || !idxs || !packed || !u_rot || !sel || !n_sel_dev || !heads) return CPPF_EINVAL;

@@ -25,11 +25,6 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
 
-static bool is_std_decode(int F, const int* dims, int n_res, int out_dim, int tr_bins, int rot_bins)
-{
-    return is_std(F, dims, n_res, out_dim) && tr_bins == 32 && rot_bins == 36 && out_dim == 141;
-}
-
 extern "C" size_t cppf_pair_mlp_bf16_packed_bytes(int F, const int* dims, int n_res, int out_dim)
 {
     if (!dims) return 0;
@@ -317,114 +312,44 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_WAVES_PER_SIMD) void pair_mlp_bf16
 }
 
 // ----------------------------------------------------------------------------- entry points
-#define BF16_LDS_BYTES ((BF16_LDS + 128) * sizeof(float))
+// the bf16 kernels as a PairVariant: everything else on the host side is pair_mlp.hip's shared code (pair_mlp_common.h)
+static int launch_logits(const MlpArgs& A, size_t lds, hipStream_t st)
+{
+    hipLaunchKernelGGL((pair_mlp_bf16_kernel<true, false, false>), dim3(mlp_grid(A.P)), dim3(MLP_THREADS), lds, st, A);
+    CPPF_CHECK_LAUNCH();
+    return 0;
+}
+static int launch_batch(const MlpBatch& B, bool heads, bool sel, unsigned grid, size_t lds, hipStream_t st)
+{
+    if (!sel && heads) hipLaunchKernelGGL((pair_mlp_bf16_batch_kernel<true>), dim3(grid), dim3(MLP_THREADS), lds, st, B);
+    else if (!sel) hipLaunchKernelGGL((pair_mlp_bf16_batch_kernel<false>), dim3(grid), dim3(MLP_THREADS), lds, st, B);
+    else hipLaunchKernelGGL((pair_mlp_bf16_batch_kernel<true, true>), dim3(grid), dim3(MLP_THREADS), lds, st, B);
+    CPPF_CHECK_LAUNCH();
+    return 0;
+}
+static const PairVariant PAIR_BF16 = {(BF16_LDS + 128) * sizeof(float), launch_logits, launch_batch, /* skip_empty */ true};
 
 extern "C" int cppf_pair_mlp_bf16_forward(const float* pc, const float* nrm, const float* feat, const void* idxs, int idx_is_i64,
                                           const void* packed, int64_t N, int F, const int* dims, int n_res, int64_t P, int out_dim,
                                           float* out, void* workspace, size_t workspace_bytes, void* stream)
 {
     if (P < 0 || !dims) return CPPF_EINVAL;
-    if (!is_std(F, dims, n_res, out_dim)) return CPPF_EUNSUPPORTED;
+    if (!is_std(F, dims, n_res, out_dim)) return CPPF_EUNSUPPORTED;   // (no generic bf16 kernel)
     if (P == 0) return 0;
-    if (!pc || !nrm || !feat || !idxs || !packed || !out || N < 1) return CPPF_EINVAL;
-    if (N >= (1ll << 23) || P >= (1ll << 27)) return CPPF_EUNSUPPORTED;   // 32-bit byte offsets inside the kernel
-    if (!workspace || workspace_bytes < (size_t)N * PROJ_COLS * sizeof(float)) return CPPF_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    float* table = static_cast<float*>(workspace);
-    ProjBatch PJ = {};
-    PJ.feat[0] = feat; PJ.packed[0] = static_cast<const float*>(packed); PJ.table[0] = table; PJ.N[0] = N;
-    const int rc = pair_point_proj_batch(PJ, (unsigned)((N + PROJ_PPB - 1) / PROJ_PPB), 1, st);
-    if (rc != 0) return rc;
+    if (!pc || !nrm || !feat || !idxs || !packed || !out) return CPPF_EINVAL;
     MlpArgs A = {};
     A.pc = pc; A.nrm = nrm; A.feat = feat; A.idxs = idxs; A.packed = static_cast<const float*>(packed); A.out = out; A.P = P;
-    A.out_dim = out_dim; A.idx64 = idx_is_i64; A.table = table;
-    hipLaunchKernelGGL((pair_mlp_bf16_kernel<true, false, false>), dim3(mlp_grid(P)), dim3(MLP_THREADS), BF16_LDS_BYTES, st, A);
-    CPPF_CHECK_LAUNCH();
-    return 0;
+    A.out_dim = out_dim; A.idx64 = idx_is_i64;
+    return pair_std_forward(PAIR_BF16, A, N, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int cppf_pair_mlp_bf16_decode_batch(int n_items, const CppfPairMlpItem* items, int F, const int* dims, int n_res, int out_dim,
                                                int tr_bins, int rot_bins, void* stream)
 {
-    if (n_items < 1 || n_items > MLP_BATCH_MAX || !items || !dims) return CPPF_EINVAL;
-    if (!is_std_decode(F, dims, n_res, out_dim, tr_bins, rot_bins)) return CPPF_EUNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    // (P = 0: nothing to do for that list; the launch serves the others)
-    MlpBatch B = {};
-    ProjBatch PJ = {};
-    const CppfPairMlpItem* live[MLP_BATCH_MAX];
-    int64_t n_pairs[MLP_BATCH_MAX];
-    for (int i = 0; i < n_items; ++i) {
-        const CppfPairMlpItem& it = items[i];
-        if (it.n_pairs < 0) return CPPF_EINVAL;
-        if (it.n_pairs == 0) continue;
-        n_pairs[B.n] = it.n_pairs;
-        live[B.n++] = &it;
-    }
-    if (B.n == 0) return 0;
-    const bool heads = live[0]->heads != nullptr;
-    int64_t proj_blocks = 1;
-    for (int i = 0; i < B.n; ++i) {
-        const CppfPairMlpItem& it = *live[i];
-        if (it.n_points < 1) return CPPF_EINVAL;
-        if (!it.pc || !it.nrm || !it.feat || !it.idxs || !it.packed || !it.u_tr || !it.outputs) return CPPF_EINVAL;
-        if ((it.heads != nullptr) != heads || (it.heads != nullptr) != (it.u_rot != nullptr)) return CPPF_EINVAL;
-        if (it.n_points >= (1ll << 23) || it.n_pairs >= (1ll << 27)) return CPPF_EUNSUPPORTED;
-        if (!it.workspace || it.workspace_bytes < (size_t)it.n_points * PROJ_COLS * sizeof(float)) return CPPF_EWORKSPACE;
-        float* table = static_cast<float*>(it.workspace);
-        PJ.feat[i] = it.feat; PJ.packed[i] = it.packed; PJ.table[i] = table; PJ.N[i] = it.n_points;
-        const int64_t nb = (it.n_points + PROJ_PPB - 1) / PROJ_PPB;
-        proj_blocks = nb > proj_blocks ? nb : proj_blocks;
-        MlpArgs& A = B.item[i];
-        A.pc = it.pc; A.nrm = it.nrm; A.feat = it.feat; A.idxs = it.idxs; A.packed = it.packed; A.P = it.n_pairs; A.out_dim = out_dim;
-        A.idx64 = it.idx_is_i64; A.u_tr = it.u_tr; A.u_rot = it.u_rot; A.outputs = it.outputs; A.heads = it.heads;
-        A.vr0 = it.vr0; A.vr1 = it.vr1; A.table = table;
-    }
-    int given = 0;
-    batch_plan(B.n, n_pairs, B.wg_begin, &B.per_xcd, &given);
-    const int rc = pair_point_proj_batch(PJ, (unsigned)proj_blocks, B.n, st);
-    if (rc != 0) return rc;
-    if (heads) hipLaunchKernelGGL((pair_mlp_bf16_batch_kernel<true>), dim3((unsigned)given), dim3(MLP_THREADS), BF16_LDS_BYTES, st, B);
-    else hipLaunchKernelGGL((pair_mlp_bf16_batch_kernel<false>), dim3((unsigned)given), dim3(MLP_THREADS), BF16_LDS_BYTES, st, B);
-    CPPF_CHECK_LAUNCH();
-    return 0;
+    return pair_decode_batch(PAIR_BF16, n_items, items, F, dims, n_res, out_dim, tr_bins, rot_bins, (hipStream_t)stream);
 }
-
-// The second pass for several pair lists in ONE launch (pair_mlp.hip: cppf_pair_mlp_decode_sel_batch, same contracts): every list's
-// per-point table is the one its first pass left in item.workspace.  Items with n_pairs == 0 or max_sel == 0 are skipped.
 extern "C" int cppf_pair_mlp_bf16_decode_sel_batch(int n_items, const CppfPairMlpItem* items, int F, const int* dims, int n_res,
                                                    int out_dim, int tr_bins, int rot_bins, void* stream)
 {
-    if (n_items < 1 || n_items > MLP_BATCH_MAX || !items || !dims) return CPPF_EINVAL;
-    if (!is_std_decode(F, dims, n_res, out_dim, tr_bins, rot_bins)) return CPPF_EUNSUPPORTED;
-    MlpBatch B = {};
-    int given = 0;
-    for (int i = 0; i < n_items; ++i) {
-        const CppfPairMlpItem& it = items[i];
-        if (it.n_pairs < 0 || it.max_sel < 0) return CPPF_EINVAL;
-        if (it.n_pairs == 0 || it.max_sel == 0) continue;
-        if (it.n_pairs >= (1ll << 27) || it.n_points >= (1ll << 23)) return CPPF_EUNSUPPORTED;
-        if (it.n_points < 1) return CPPF_EINVAL;
-        if (!it.pc || !it.nrm || !it.feat || !it.idxs || !it.packed || !it.u_rot || !it.sel || !it.n_sel_dev || !it.heads) return CPPF_EINVAL;
-        if (!it.workspace || it.workspace_bytes < (size_t)it.n_points * PROJ_COLS * sizeof(float)) return CPPF_EWORKSPACE;
-        MlpArgs& A = B.item[B.n];
-        A.pc = it.pc; A.nrm = it.nrm; A.feat = it.feat; A.idxs = it.idxs; A.packed = it.packed; A.out_dim = out_dim;
-        A.P = it.max_sel < it.n_pairs ? it.max_sel : it.n_pairs;
-        A.idx64 = it.idx_is_i64; A.u_rot = it.u_rot; A.heads = it.heads; A.sel = it.sel; A.n_sel = it.n_sel_dev;
-        A.table = static_cast<const float*>(it.workspace);
-        B.wg_begin[B.n] = given;
-        // (a launch cannot know the survivor counts: every list gets the workgroups of its capacity, at most half of the chip's
-        // round when several lists share it; surplus workgroups exit at once)
-        int w = mlp_grid(A.P);
-        const int cap = mlp_grid(1ll << 26) / (n_items > 1 ? 2 : 1);
-        if (w > cap) w = cap;
-        given += w;
-        ++B.n;
-    }
-    if (B.n == 0) return 0;
-    B.wg_begin[B.n] = given;
-    hipLaunchKernelGGL((pair_mlp_bf16_batch_kernel<true, true>), dim3((unsigned)given), dim3(MLP_THREADS), BF16_LDS_BYTES,
-                       (hipStream_t)stream, B);
-    CPPF_CHECK_LAUNCH();
-    return 0;
+    return pair_decode_sel_batch(PAIR_BF16, n_items, items, F, dims, n_res, out_dim, tr_bins, rot_bins, (hipStream_t)stream);
 }

@@ -1,6 +1,8 @@
 // What the fp32 pair encoder (pair_mlp.hip) and the bf16 one (pair_mlp_bf16.hip) share: the argument blocks of their kernels, the PPF
-// construction, the addressing helpers of the tile loop, the two in-register samplers, the decode of the heads and the launch
-// geometry.  Device functions only (every one force-inlined): each file instantiates its own kernels.
+// construction, the addressing helpers of the tile loop, the two in-register samplers, the decode of the heads, the launch
+// geometry and the host path of the entry points.  The device functions are all force-inlined: each file instantiates its own
+// kernels, and the host side of both goes through pair_mlp.hip's pair_std_forward / pair_decode_batch / pair_decode_sel_batch with a
+// PairVariant that names the kernels to launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -155,7 +157,7 @@ struct MlpArgs {
 
 // Addresses inside the tile loop are a uniform base (SGPR pair) + an unsigned 32-bit byte offset (one VGPR): the
 // `global_load v, v_off, s[base]` form.  64-bit pointer arithmetic per lane (v_lshl_add_u64, v_lshlrev_b64 ...) was ~50 VALU
-// per tile on the pipe the fp32 MFMAs share.  Hence the limits of the MFMA path: N < 2^23 points, P < 2^27 pairs (launch_std).
+// per tile on the pipe the fp32 MFMAs share.  Hence the limits of the MFMA path: N < 2^23 points, P < 2^27 pairs (std_table, item_limits).
 template <typename T>
 __device__ __forceinline__ const T& at_off(const void* base, unsigned byte_off)
 {
@@ -175,7 +177,7 @@ __device__ __forceinline__ f3 ld3o(const float* __restrict__ base, int i)
 }
 
 // slot of the launch -> row of the pair arrays (identity unless SEL)
-// (slots, tiles and pair counts are 32-bit inside the kernel -- P < 2^27, launch_std -- : 64-bit compares and selects were a
+// (slots, tiles and pair counts are 32-bit inside the kernel -- P < 2^27, item_limits -- : 64-bit compares and selects were a
 //  dozen instructions per tile)
 template <bool SEL>
 __device__ __forceinline__ unsigned pair_row(const MlpArgs& A, int slot, int Pn)
@@ -220,8 +222,6 @@ __device__ __forceinline__ float ppf_from(f3 pa, f3 pb, f3 na, f3 nb, int g)
 #define PROJ_PPB 8
 // the projections of several clouds in one launch (cppf_pair_mlp_decode_batch): cloud blockIdx.y; as wide as the largest needs
 struct ProjBatch { const float* feat[8]; const float* packed[8]; float* table[8]; int64_t N[8]; };
-// (pair_mlp.hip) launches point_proj_batch_kernel: `blocks` = blocks of PROJ_PPB points the largest cloud needs
-__attribute__((visibility("hidden"))) int pair_point_proj_batch(const ProjBatch& PJ, unsigned blocks, int n_items, hipStream_t st);
 
 #define MLP_BATCH_MAX 8
 struct MlpBatch {
@@ -243,33 +243,25 @@ static int mlp_grid(int64_t P)
     return (int)nb;
 }
 
-// The launch geometry of cppf_pair_mlp_decode_batch for lists of n_pairs[i] pairs: workgroups in proportion to the lists' tiles, at
-// least one each, as many in all as one list alone would get (wg_begin[n + 1]); with 1, 2, 4 or 8 lists within 10 % of each other
-// and a grid of at least 8 the XCD-aware form (per_xcd = 8 / n > 0, the grid rounded down to a multiple of 8).
-static void batch_plan(int n_items, const int64_t* n_pairs, int* wg_begin, int* per_xcd, int* grid)
-{
-    int64_t tiles_all = 0, tmin = INT64_MAX, tmax = 0;
-    for (int i = 0; i < n_items; ++i) {
-        const int64_t tiles = (n_pairs[i] + 15) / 16;
-        tiles_all += tiles;
-        tmin = tiles < tmin ? tiles : tmin; tmax = tiles > tmax ? tiles : tmax;
-    }
-    const int total = mlp_grid(tiles_all * 16) < n_items ? n_items : mlp_grid(tiles_all * 16);
-    int given = 0;
-    for (int i = 0; i < n_items; ++i) {
-        const int64_t tiles = (n_pairs[i] + 15) / 16;
-        int w = (int)((tiles * total + tiles_all - 1) / tiles_all);
-        const int left = total - given - (n_items - 1 - i);
-        if (w > left) w = left;
-        if (w < 1) w = 1;
-        wg_begin[i] = given;
-        given += w;
-    }
-    wg_begin[n_items] = given;
-    *per_xcd = 0;
-    if (8 % n_items == 0 && tmax * 10 <= tmin * 11 && given >= 8) {
-        *per_xcd = 8 / n_items;
-        given = given / 8 * 8;
-    }
-    *grid = given;
-}
+// ---- host path.  What differs between the two encoders once a call is known to be for the standard architecture: the kernels (each
+// file launches its own) and one rule.  Everything else -- the item contract, the MlpArgs / ProjBatch fills, the per-point tables,
+// the launch geometry, the survivor capacity, the 2^23 / 2^27 limits -- is the three bodies below, defined once in pair_mlp.hip.
+struct PairVariant {
+    size_t lds_bytes;   // dynamic LDS of the variant's pair kernels
+    // the logits kernel on mlp_grid(A.P) workgroups
+    int (*launch_logits)(const MlpArgs& A, size_t lds, hipStream_t st);
+    // the batch kernel <heads, sel> on `grid` workgroups (sel: the second pass, always with heads), with whatever function
+    // attribute the kernel needs for `lds`
+    int (*launch_batch)(const MlpBatch& B, bool heads, bool sel, unsigned grid, size_t lds, hipStream_t st);
+    // a list with n_pairs == 0 in the first-pass batch: true = skipped (0 when no list is left), false = CPPF_EINVAL
+    bool skip_empty;
+};
+#define PAIR_HOST __attribute__((visibility("hidden")))
+// logits of one list: the checks of the MFMA path (N, the limits, the workspace), the per-point table, V.launch_logits.  The caller
+// has checked the architecture and the pointers and filled A (all but A.table).
+PAIR_HOST int pair_std_forward(const PairVariant& V, MlpArgs& A, int64_t N, void* workspace, size_t workspace_bytes, hipStream_t st);
+// cppf_pair_mlp[_bf16]_decode_batch and _decode_sel_batch, whole
+PAIR_HOST int pair_decode_batch(const PairVariant& V, int n_items, const CppfPairMlpItem* items, int F, const int* dims, int n_res,
+                                int out_dim, int tr_bins, int rot_bins, hipStream_t st);
+PAIR_HOST int pair_decode_sel_batch(const PairVariant& V, int n_items, const CppfPairMlpItem* items, int F, const int* dims, int n_res,
+                                    int out_dim, int tr_bins, int rot_bins, hipStream_t st);

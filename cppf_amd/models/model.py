@@ -91,6 +91,62 @@ class _DeviceWeights:
     def _param_key(self, device):
         return (str(device), self.__dict__.get("_cppf_epoch", 0)) + tuple((p.data_ptr(), p._version) for p in _params_of(self))
 
+    # ------------------------------------------------------------------ precision and the image of each
+    # An encoder supplies: _ENTRY (the prefix of its C entry points), _image_words(precision) (the image's size in 4-byte words, 0:
+    # no kernel serves this encoder in that precision), _no_kernel(precision) (the refusal's text) and _pack_image(dev, buf) (pack
+    # the image of the current precision into `buf`, on the device where it can, and return what _packed_weights() hands out).
+    @property
+    def precision(self):
+        """"fp32" (the default: bit for bit the oracle's arithmetic) or "bf16" (set_precision)"""
+        return self.__dict__.get("_cppf_precision", "fp32")
+
+    def set_precision(self, precision):
+        """Choose the arithmetic of the inference kernels: "fp32" (exact fp32 MFMAs) or "bf16" (the hidden layers as bf16 x bf16
+        products accumulated in fp32; which layers stay fp32 is the encoder's, see its class).  bf16 is inference only (the backward
+        stays fp32: a bf16 encoder asked for gradients raises CppfError) and serves the architecture the fp32 MFMA kernel serves
+        (no fall-back to fp32).  Each precision keeps its own weight image; captured pipelines capture again after a switch.
+        Returns self."""
+        if precision not in ("fp32", "bf16"):
+            raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
+        if precision == "bf16" and self._image_words(precision) == 0:
+            raise _lib.CppfError(self._no_kernel(precision))
+        self.__dict__["_cppf_precision"] = precision
+        return self
+
+    def _entry(self, name):
+        """the C entry point of the current precision: <_ENTRY>_<name> or <_ENTRY>_bf16_<name>"""
+        return f"{self._ENTRY}_bf16_{name}" if self.precision == "bf16" else f"{self._ENTRY}_{name}"
+
+    def _current_image(self):
+        """what _packed_weights() last returned for the current precision, as it is now (None before its first pack)"""
+        hit = self.__dict__.get("_cppf_images", {}).get(self.precision)
+        return None if hit is None else hit[2]
+
+    def _packed_weights(self, device):
+        """The weight image for the HIP kernels of the current precision (fp32: a float32 tensor, bf16: an int32 tensor of words),
+        rebuilt when a parameter changes.  Each precision has its own buffer and key; a rebuild rewrites the buffer in place when
+        device, size and type allow, ordered against readers on other streams."""
+        prec = self.precision
+        key = self._param_key(device)
+        images = self.__dict__.setdefault("_cppf_images", {})       # precision -> (key, buffer, what the encoder hands out)
+        hit = images.get(prec)
+        if hit is not None and hit[0] == key:
+            return hit[2]
+        n = self._image_words(prec)
+        if n == 0:
+            raise _lib.CppfError(self._no_kernel(prec))
+        dev, dtype = torch.device(device), torch.int32 if prec == "bf16" else torch.float32
+        buf = None if hit is None else hit[1]
+        if buf is not None and buf.device == dev and buf.numel() == n and buf.dtype == dtype:
+            if dev.type == "cuda":
+                self._image_rebuild_begins(dev)
+        else:
+            buf = torch.empty(n, dtype=dtype, device=dev)
+        images[prec] = (key, buf, self._pack_image(dev, buf))
+        if dev.type == "cuda":
+            self._image_rebuilt(dev)
+        return images[prec][2]
+
     # Several HIP streams may share one encoder (inference.CenterPipeline lanes, batch.BatchPoseRunner).  The image is rebuilt
     # in place on whichever stream notices the parameter change, so both directions are ordered with events: a rebuild waits for
     # every replay that was still reading the old image (`_note_image_read`), and a reader on another stream waits for the
@@ -235,44 +291,55 @@ class PointEncoder(_DeviceWeights, nn.Module):
         for _ in range(num_layers - 1):
             self.spconvs.append(SparseSO3Conv(32, out_dim + out_dim // 4, out_dim, *spfcs))
             self.aggrs.append(GlobalInfoProp(out_dim, out_dim // 4))
-        self._packed = None
-        self._packed_key = None
-        self._packed_bf16 = None
-        self._packed_bf16_key = None
 
-    # ------------------------------------------------------------------ precision (this package)
-    @property
-    def precision(self):
-        """"fp32" (the default: bit for bit the oracle's arithmetic) or "bf16" (set_precision)"""
-        return self.__dict__.get("_cppf_precision", "fp32")
+    # ------------------------------------------------------------------ precision (this package: _DeviceWeights.set_precision)
+    # "fp32": csrc/sprin.hip.  "bf16": csrc/sprin_bf16.hip -- gather, rifeat, layer 1 of the kernel-MLP and every LayerNorm in fp32
+    # as before, layers 2..5 in bf16; the contraction, the outnet and GlobalInfoProp are the fp32 code.
+    _ENTRY = "cppf_point_encoder"
 
-    def set_precision(self, precision):
-        """Choose the arithmetic of the inference kernels.  "fp32": csrc/sprin.hip, exact fp32 MFMAs.  "bf16": csrc/sprin_bf16.hip --
-        gather, rifeat, layer 1 of the kernel-MLP and every LayerNorm in fp32 as before, layers 2..5 as bf16 x bf16 products
-        accumulated in fp32; the contraction, the outnet and GlobalInfoProp are the fp32 code.  bf16 is inference
-        only (the backward stays fp32: a bf16 encoder asked for gradients raises CppfError) and serves the architecture the fp32
-        kernel serves (no fall-back to fp32).  Each precision keeps its own weight image; captured pipelines capture again after a
-        switch.  Returns self."""
-        if precision not in ("fp32", "bf16"):
-            raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
-        if precision == "bf16" and not self._std_shape():
-            raise _lib.CppfError(f"no bf16 kernel for PointEncoder(k={self.k}, spfcs={self.spfcs}, out_dim={self.out_dim}, "
-                                 f"num_nbr_feats={self.num_nbr_feats}): csrc/sprin_bf16.hip covers spfcs=[32,64,32,32], out_dim=32, "
-                                 "num_nbr_feats=2, k<=64 (train.py:34); there is no fall-back to fp32")
-        self.__dict__["_cppf_precision"] = precision
-        return self
-
-    def _std_shape(self):
-        return (self.spfcs == [32, 64, 32, 32] and self.out_dim == 32 and self.num_nbr_feats == 2 and self.k <= 64
+    def _std_layers(self):
+        return (self.spfcs == [32, 64, 32, 32] and self.out_dim == 32 and self.num_nbr_feats == 2
                 and all(sc.layer_norm is not None for sc in self.spconvs))
 
-    def _current_image(self):
-        """the cached (image, desc) of the current precision as it is now (None before its first pack)"""
-        return self._packed_bf16 if self.precision == "bf16" else self._packed
+    def _std_shape(self):
+        return self._std_layers() and self.k <= 64
 
-    def _entry(self, name):
-        """the C entry point of the current precision: cppf_point_encoder_<name> or cppf_point_encoder_bf16_<name>"""
-        return f"cppf_point_encoder_bf16_{name}" if self.precision == "bf16" else f"cppf_point_encoder_{name}"
+    def _desc(self):
+        return dict(hidden=list(self.spfcs), rank=32, n_nbr_feats=self.num_nbr_feats, n_out=self.out_dim, n_glob=self.out_dim // 4,
+                    num_layers=self.num_layers)
+
+    def _shape_args(self):
+        return ((C.c_int * len(self.spfcs))(*self.spfcs), len(self.spfcs), 32, self.num_nbr_feats, self.out_dim, self.out_dim // 4,
+                self.num_layers)
+
+    def _image_words(self, precision):
+        L = _lib.lib()
+        if precision == "bf16":
+            return int(L.cppf_point_encoder_bf16_packed_bytes(*self._shape_args())) // 4 if self._std_shape() else 0
+        # (a shape without an MFMA image keeps the natural block, and the forward says that no kernel serves it)
+        return max(int(L.cppf_point_encoder_packed_floats(*self._shape_args())), sum(p.numel() for p in _params_of(self)))
+
+    def _no_kernel(self, precision):
+        return (f"no {precision} kernel for PointEncoder(k={self.k}, spfcs={self.spfcs}, out_dim={self.out_dim}, "
+                f"num_nbr_feats={self.num_nbr_feats}): csrc/sprin_bf16.hip covers spfcs=[32,64,32,32], out_dim=32, "
+                "num_nbr_feats=2, k<=64 (train.py:34); there is no fall-back to fp32")
+
+    def _pack_image(self, dev, buf):
+        """-> (image, desc).  fp32: the natural block, then the MFMA image; bf16: the natural block verbatim, then per layer the
+        fp32 layer 1, the bf16 layers 2..5 and the fp32 vectors"""
+        pack = self._entry("pack")
+        if dev.type == "cuda" and self.num_layers == 1 and self._std_layers():
+            # standard encoder: natural block by one torch.cat, image by a device kernel -- no host round trip, so a training
+            # loop (weights change every step) stays on the stream
+            nat = torch.cat([(p.detach().t() if tr else p.detach()).reshape(-1).float()
+                             for p, tr in zip(self._ordered_params(), self._ordered_transposed())]).to(dev).contiguous()
+            call(pack + "_device", dev, nat, *self._shape_args(), buf)
+        else:
+            sd = {k: v.detach().float().cpu().numpy() for k, v in self.state_dict().items()}
+            image = torch.zeros(buf.numel(), dtype=buf.dtype)
+            call(pack, None, pack_point_encoder(sd, self.num_layers)[0], *self._shape_args(), image)
+            buf.copy_(image)
+        return buf, self._desc()
 
     def _refuse_gradients(self, *inputs):
         if torch.is_grad_enabled() and (self.training or any(isinstance(t, torch.Tensor) and t.requires_grad for t in inputs)
@@ -361,9 +428,7 @@ class PointEncoder(_DeviceWeights, nn.Module):
 
     def _has_device_backward(self, pc, pc_normal):
         """csrc/sprin_bwd.hip covers the one-layer standard encoder (train.py:34) when only the parameters need gradients"""
-        return (pc.is_cuda and self.num_layers == 1 and self.spfcs == [32, 64, 32, 32] and self.out_dim == 32
-                and self.num_nbr_feats == 2 and self.k <= 64 and not pc.requires_grad and not pc_normal.requires_grad
-                and self.spconvs[0].layer_norm is not None)
+        return pc.is_cuda and self.num_layers == 1 and self._std_shape() and not pc.requires_grad and not pc_normal.requires_grad
 
     def _ordered_params(self):
         """parameters in the packed natural order of `pack_point_encoder` (one layer); cached like `_params_of`"""
@@ -423,98 +488,6 @@ class PointEncoder(_DeviceWeights, nn.Module):
         if dist.shape[-2:] != (pc2.shape[0], pc2.shape[0]):
             raise ValueError(f"dist must be [..., N, N], got {tuple(dist.shape)}")
         return canon(dist, torch.float32, pc2.device, "dist").reshape(pc2.shape[0], pc2.shape[0])
-
-    def _packed_weights(self, device):
-        """(weight image, desc) for the HIP kernels of the current precision, rebuilt when a parameter changes (each precision its
-        own buffer and key)"""
-        if self.precision == "bf16":
-            return self._packed_weights_bf16(device)
-        key = self._param_key(device)
-        if self._packed is not None and self._packed_key == key:
-            return self._packed
-        dev = torch.device(device)
-        L = _lib.lib()
-        old = self._packed[0] if self._packed is not None and self._packed[0].device == dev else None
-        if dev.type == "cuda" and self.num_layers == 1 and self.spfcs == [32, 64, 32, 32] and self.out_dim == 32 \
-                and self.num_nbr_feats == 2 and self.spconvs[0].layer_norm is not None:
-            # standard encoder: natural block by one torch.cat, MFMA image by a device kernel -- no host round trip, so
-            # a training loop (weights change every step) stays on the stream
-            nat = torch.cat([(p.detach().t() if tr else p.detach()).reshape(-1).float()
-                             for p, tr in zip(self._ordered_params(), self._ordered_transposed())]).to(dev).contiguous()
-            desc = dict(hidden=list(self.spfcs), rank=32, n_nbr_feats=2, n_out=32, n_glob=self.out_dim // 4, num_layers=1)
-            hid = (C.c_int * 4)(*self.spfcs)
-            n = int(L.cppf_point_encoder_packed_floats(hid, 4, 32, 2, 32, desc["n_glob"], 1))
-            packed = old if old is not None and old.numel() == n else torch.empty(n, dtype=torch.float32, device=dev)
-            if packed is old:
-                self._image_rebuild_begins(dev)
-            call("cppf_point_encoder_pack_device", dev, nat, hid, 4, 32, 2, 32, desc["n_glob"], 1, packed)
-        else:
-            sd = {k: v.detach().float().cpu().numpy() for k, v in self.state_dict().items()}
-            natural, desc = pack_point_encoder(sd, self.num_layers)
-            hid = (C.c_int * len(desc["hidden"]))(*desc["hidden"])
-            n = L.cppf_point_encoder_packed_floats(hid, len(desc["hidden"]), desc["rank"], desc["n_nbr_feats"], desc["n_out"],
-                                                   desc["n_glob"], self.num_layers)
-            image = np.zeros(max(int(n), natural.size), np.float32)
-            call("cppf_point_encoder_pack", None, natural, hid, len(desc["hidden"]), desc["rank"], desc["n_nbr_feats"], desc["n_out"],
-                 desc["n_glob"], self.num_layers, image)
-            if old is not None and old.numel() == image.size:
-                packed = old
-                self._image_rebuild_begins(dev)
-                packed.copy_(torch.from_numpy(image))
-            else:
-                packed = torch.from_numpy(image).to(device)
-        self._packed = (packed, desc)
-        self._packed_key = key
-        if dev.type == "cuda":
-            self._image_rebuilt(dev)
-        return self._packed
-
-    def _packed_weights_bf16(self, device):
-        """_packed_weights for the bf16 image: an int32 tensor of cppf_point_encoder_bf16_packed_bytes() / 4 words (the natural
-        block verbatim, then per layer the fp32 layer 1, the bf16 layers 2..5 and the fp32 vectors), rebuilt in place when a
-        parameter changes, with the same ordering against readers on other streams as the fp32 image.  On a HIP device the
-        one-layer encoder packs there (cppf_point_encoder_bf16_pack_device); deeper ones and the host pack on the host."""
-        key = self._param_key(device)
-        if self._packed_bf16 is not None and self._packed_bf16_key == key:
-            return self._packed_bf16
-        if not self._std_shape():
-            raise _lib.CppfError(f"no bf16 kernel for PointEncoder(k={self.k}, spfcs={self.spfcs}, out_dim={self.out_dim}) "
-                                 "(there is no fall-back to fp32)")
-        dev = torch.device(device)
-        n_glob = self.out_dim // 4
-        desc = dict(hidden=list(self.spfcs), rank=32, n_nbr_feats=2, n_out=32, n_glob=n_glob, num_layers=self.num_layers)
-        hid = (C.c_int * 4)(*self.spfcs)
-        shape = (hid, 4, 32, 2, 32, n_glob, self.num_layers)
-        n = int(_lib.lib().cppf_point_encoder_bf16_packed_bytes(*shape)) // 4
-        if n == 0:
-            raise _lib.CppfError(f"no bf16 kernel for PointEncoder(spfcs={self.spfcs}, out_dim={self.out_dim}) (there is no fall-back "
-                                 "to fp32)")
-        old = self._packed_bf16[0] if self._packed_bf16 is not None else None
-        if old is not None and (old.device != dev or old.numel() != n):
-            old = None
-        if dev.type == "cuda" and self.num_layers == 1:
-            nat = torch.cat([(p.detach().t() if tr else p.detach()).reshape(-1).float()
-                             for p, tr in zip(self._ordered_params(), self._ordered_transposed())]).to(dev).contiguous()
-            packed = old if old is not None else torch.empty(n, dtype=torch.int32, device=dev)
-            if old is not None:
-                self._image_rebuild_begins(dev)
-            call("cppf_point_encoder_bf16_pack_device", dev, nat, *shape, packed)
-        else:
-            sd = {k: v.detach().float().cpu().numpy() for k, v in self.state_dict().items()}
-            natural, _ = pack_point_encoder(sd, self.num_layers)
-            image = np.zeros(n, np.int32)
-            call("cppf_point_encoder_bf16_pack", None, natural, *shape, image)
-            if old is not None:
-                packed = old
-                if dev.type == "cuda":
-                    self._image_rebuild_begins(dev)
-                packed.copy_(torch.from_numpy(image))
-            else:
-                packed = torch.from_numpy(image).to(dev)
-        self._packed_bf16, self._packed_bf16_key = (packed, desc), key
-        if dev.type == "cuda":
-            self._image_rebuilt(dev)
-        return self._packed_bf16
 
     def forward_dyn(self, pc, pc_normal, n_dev, out=None, nbrs=None, nbrs_ready=False):
         """Shape-polymorphic forward for captured chains (cppf_knn_dyn + cppf_point_encoder_forward_dyn): pc / pc_normal are
@@ -595,36 +568,13 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         self.res_layers = nn.ModuleList(
             ResLayer(self.ppffcs[i], self.ppffcs[i + 1]) for i in range(len(self.ppffcs) - 1))
         self.final = nn.Linear(self.ppffcs[-1], self.out_dim)
-        self._packed = None
-        self._packed_key = None
-        self._packed_bf16 = None
-        self._packed_bf16_key = None
         self._flat = None
         self._flat_key = None
 
-    # ------------------------------------------------------------------ precision (this package)
-    @property
-    def precision(self):
-        """"fp32" (the default: bit for bit the oracle's arithmetic) or "bf16" (set_precision)"""
-        return self.__dict__.get("_cppf_precision", "fp32")
-
-    def set_precision(self, precision):
-        """Choose the arithmetic of the inference kernels.  "fp32": csrc/pair_mlp.hip, exact fp32 MFMAs.  "bf16":
-        csrc/pair_mlp_bf16.hip -- layer 0 in fp32 as before, every later layer as bf16 x bf16 products accumulated in fp32, fp32
-        logits and the unchanged fp32 decode (DESIGN.md "bf16 pair encoder").  bf16 is inference only (the backward stays fp32: a
-        bf16 encoder asked for gradients raises CppfError) and serves the standard architecture only (no fall-back to fp32).
-        Each precision keeps its own weight image; captured pipelines capture again after a switch.  Returns self."""
-        if precision not in ("fp32", "bf16"):
-            raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
-        if precision == "bf16" and not (self.ppffcs == [84, 32, 32, 16] and 1 <= self.out_dim <= 144):
-            raise _lib.CppfError(f"no bf16 kernel for ppffcs={self.ppffcs}, out_dim={self.out_dim}: csrc/pair_mlp_bf16.hip covers "
-                                 "ppffcs=[84,32,32,16], out_dim<=144 (train.py:35); there is no fall-back to fp32")
-        self.__dict__["_cppf_precision"] = precision
-        return self
-
-    def _current_image(self):
-        """the cached weight image of the current precision as it is now (None before its first pack)"""
-        return self._packed_bf16 if self.precision == "bf16" else self._packed
+    # ------------------------------------------------------------------ precision (this package: _DeviceWeights.set_precision)
+    # "fp32": csrc/pair_mlp.hip.  "bf16": csrc/pair_mlp_bf16.hip -- layer 0 in fp32 as before, every later layer in bf16, fp32 logits
+    # and the unchanged fp32 decode (DESIGN.md "bf16 pair encoder"); the standard architecture only.
+    _ENTRY = "cppf_pair_mlp"
 
     def _refuse_gradients(self, feat):
         if torch.is_grad_enabled() and (self.training or feat.requires_grad):
@@ -663,11 +613,7 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         out = torch.empty((P, self.out_dim), dtype=torch.float32, device=pc.device)
         dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
         ws = self._scratch(pc, feat, dims)
-        if self.precision == "bf16":
-            call("cppf_pair_mlp_bf16_forward", pc.device, pc, pc_normal, feat, idxs, idxs.dtype == torch.int64,
-                 self._packed_weights(pc.device), pc.shape[0], feat.shape[1], dims, len(self.ppffcs) - 1, P, self.out_dim, out, scratch(ws))
-            return out
-        call("cppf_pair_mlp_forward", pc.device, pc, pc_normal, feat, idxs, idxs.dtype == torch.int64, self._packed_weights(pc.device),
+        call(self._entry("forward"), pc.device, pc, pc_normal, feat, idxs, idxs.dtype == torch.int64, self._packed_weights(pc.device),
              pc.shape[0], feat.shape[1], dims, len(self.ppffcs) - 1, P, self.out_dim, out, scratch(ws))
         return out
 
@@ -688,9 +634,8 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
         ws = self._scratch(pc, feat, dims)
         if self.precision == "bf16":             # one list = the batch of one (no per-variant single entry points)
-            item = fill(_lib.PairMlpItem(), pc.device, pc=pc, nrm=pc_normal, feat=feat, idxs=idxs, packed=self._packed_weights(pc.device),
-                        u_tr=u_tr, u_rot=u_rot, outputs=outputs, heads=heads, workspace=scratch(ws), n_points=pc.shape[0], n_pairs=P,
-                        vr0=float(vote_range[0]), vr1=float(vote_range[1]), idx_is_i64=idxs.dtype == torch.int64)
+            item = self._item(_lib.PairMlpItem(), pc, pc_normal, feat, idxs, ws, u_tr=u_tr, u_rot=u_rot, outputs=outputs, heads=heads,
+                              vr0=float(vote_range[0]), vr1=float(vote_range[1]))
             rc = call("cppf_pair_mlp_bf16_decode_batch", pc.device, 1, C.byref(item), feat.shape[1], dims, len(self.ppffcs) - 1,
                       self.out_dim, tr_num_bins, rot_num_bins, ok=(_lib.EUNSUPPORTED,))
         else:
@@ -733,9 +678,8 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
         ws = self._scratch(pc, feat, dims)
         if self.precision == "bf16":
-            item = fill(_lib.PairMlpItem(), pc.device, pc=pc, nrm=pc_normal, feat=feat, idxs=idxs, packed=self._packed_weights(pc.device),
-                        u_rot=u_rot, heads=heads, workspace=scratch(ws), n_points=pc.shape[0], n_pairs=P,
-                        idx_is_i64=idxs.dtype == torch.int64, sel=sel, n_sel_dev=n_sel, max_sel=max_sel)
+            item = self._item(_lib.PairMlpItem(), pc, pc_normal, feat, idxs, ws, u_rot=u_rot, heads=heads, sel=sel, n_sel_dev=n_sel,
+                              max_sel=max_sel)
             rc = call("cppf_pair_mlp_bf16_decode_sel_batch", pc.device, 1, C.byref(item), feat.shape[1], dims, len(self.ppffcs) - 1,
                       self.out_dim, tr_num_bins, rot_num_bins, ok=(_lib.EUNSUPPORTED,))
         else:
@@ -757,6 +701,11 @@ class PPFEncoder(_DeviceWeights, nn.Module):
         return heads
 
     # ------------------------------------------------------------------ internals
+    def _item(self, item, pc, pc_normal, feat, idxs, ws, **more):
+        """one pair list of cppf_pair_mlp*_decode_batch / _decode_sel_batch: what every pass reads, then the pass's own fields"""
+        return fill(item, pc.device, pc=pc, nrm=pc_normal, feat=feat, idxs=idxs, packed=self._packed_weights(pc.device),
+                    workspace=scratch(ws), n_points=pc.shape[0], n_pairs=idxs.shape[0], idx_is_i64=idxs.dtype == torch.int64, **more)
+
     def _scratch(self, pc, feat, dims):
         need = _lib.lib().cppf_pair_mlp_workspace_bytes(pc.shape[0], feat.shape[1], dims, len(self.ppffcs) - 1,
                                                         self.out_dim)
@@ -867,79 +816,33 @@ class PPFEncoder(_DeviceWeights, nn.Module):
             self._flat_key = key
         return self._flat
 
-    def _packed_weights(self, device):
-        """Lane-ordered weight image for the HIP kernels, rebuilt when a parameter changes.  The standard architecture
-        packs on the device (cppf_pair_mlp_pack_device: a training loop changes the weights every step and never
-        leaves the stream); other stacks pack on the host.  Under precision "bf16": the bf16 image (its own buffer and key)."""
-        if self.precision == "bf16":
-            return self._packed_weights_bf16(device)
-        key = self._param_key(device)
-        if self._packed is not None and self._packed_key == key:
-            return self._packed
-        dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
-        L = _lib.lib()
-        F_ = (self.ppffcs[0] - 4) // 2
-        n_res = len(self.ppffcs) - 1
-        n = L.cppf_pair_mlp_packed_floats(F_, dims, n_res, self.out_dim)
-        if n == 0:
-            raise _lib.CppfError(f"no device kernel for ppffcs={self.ppffcs}, out_dim={self.out_dim} "
-                                 "(layers wider than 128 units are unsupported)")
-        dev = torch.device(device)
-        old = self._packed if self._packed is not None and self._packed.device == dev and self._packed.numel() == n else None
-        if dev.type == "cuda" and self.ppffcs == [84, 32, 32, 16] and self.out_dim <= 144:
-            flat, offs_c = self._flat_params(dev)
-            packed = old if old is not None else torch.empty(n, dtype=torch.float32, device=dev)
-            if old is not None:
-                self._image_rebuild_begins(dev)
-            call("cppf_pair_mlp_pack_device", dev, flat, offs_c, F_, dims, n_res, self.out_dim, packed)
-            self._packed = packed
-        else:
-            sd = {k: v.detach().float().cpu().numpy() for k, v in self.state_dict().items()}
-            params, offs = flatten_state_dict(sd, self.ppffcs)
-            packed = np.zeros(n, np.float32)
-            call("cppf_pair_mlp_pack", None, params, offs, F_, dims, n_res, self.out_dim, packed)
-            if old is not None:
-                if dev.type == "cuda":
-                    self._image_rebuild_begins(dev)
-                old.copy_(torch.from_numpy(packed))
-                self._packed = old
-            else:
-                self._packed = torch.from_numpy(packed).to(device)
-        self._packed_key = key
-        if dev.type == "cuda":
-            self._image_rebuilt(dev)
-        return self._packed
+    def _shape_args(self):
+        return ((self.ppffcs[0] - 4) // 2, (C.c_int * len(self.ppffcs))(*self.ppffcs), len(self.ppffcs) - 1, self.out_dim)
 
-    def _packed_weights_bf16(self, device):
-        """_packed_weights for the bf16 image (cppf_pair_mlp_bf16_pack_device on a HIP device, the host pack elsewhere): an
-        int32 tensor of cppf_pair_mlp_bf16_packed_bytes() / 4 words, rebuilt in place when a parameter changes, with the same ordering
-        against readers on other streams as the fp32 image"""
-        key = self._param_key(device)
-        if self._packed_bf16 is not None and self._packed_bf16_key == key:
-            return self._packed_bf16
-        dims = (C.c_int * len(self.ppffcs))(*self.ppffcs)
-        F_, n_res = (self.ppffcs[0] - 4) // 2, len(self.ppffcs) - 1
-        n = int(_lib.lib().cppf_pair_mlp_bf16_packed_bytes(F_, dims, n_res, self.out_dim)) // 4
-        if n == 0:
-            raise _lib.CppfError(f"no bf16 kernel for ppffcs={self.ppffcs}, out_dim={self.out_dim} (there is no fall-back to fp32)")
-        dev = torch.device(device)
-        old = self._packed_bf16 if self._packed_bf16 is not None and self._packed_bf16.device == dev and self._packed_bf16.numel() == n else None
-        if dev.type == "cuda":
-            flat, offs_c = self._flat_params(dev)
-            packed = old if old is not None else torch.empty(n, dtype=torch.int32, device=dev)
-            if old is not None:
-                self._image_rebuild_begins(dev)
-            call("cppf_pair_mlp_bf16_pack_device", dev, flat, offs_c, F_, dims, n_res, self.out_dim, packed)
+    def _image_words(self, precision):
+        L = _lib.lib()
+        if precision == "bf16":
+            return int(L.cppf_pair_mlp_bf16_packed_bytes(*self._shape_args())) // 4
+        return int(L.cppf_pair_mlp_packed_floats(*self._shape_args()))
+
+    def _no_kernel(self, precision):
+        if precision == "bf16":
+            return (f"no bf16 kernel for ppffcs={self.ppffcs}, out_dim={self.out_dim}: csrc/pair_mlp_bf16.hip covers "
+                    "ppffcs=[84,32,32,16], out_dim<=144 (train.py:35); there is no fall-back to fp32")
+        return f"no device kernel for ppffcs={self.ppffcs}, out_dim={self.out_dim} (layers wider than 128 units are unsupported)"
+
+    def _pack_image(self, dev, buf):
+        """-> the lane-ordered image.  The standard architecture packs on the device (a training loop changes the weights every
+        step and never leaves the stream); other stacks (fp32 only) and the host device pack on the host."""
+        pack = self._entry("pack")
+        if dev.type == "cuda" and self.ppffcs == [84, 32, 32, 16] and self.out_dim <= 144:
+            call(pack + "_device", dev, *self._flat_params(dev), *self._shape_args(), buf)
         else:
             sd = {k: v.detach().float().cpu().numpy() for k, v in self.state_dict().items()}
-            params, offs = flatten_state_dict(sd, self.ppffcs)
-            image = np.zeros(n, np.int32)
-            call("cppf_pair_mlp_bf16_pack", None, params, offs, F_, dims, n_res, self.out_dim, image)
-            packed = torch.from_numpy(image)
-        self._packed_bf16, self._packed_bf16_key = packed, key
-        if dev.type == "cuda":
-            self._image_rebuilt(dev)
-        return packed
+            image = torch.zeros(buf.numel(), dtype=buf.dtype)
+            call(pack, None, *flatten_state_dict(sd, self.ppffcs), *self._shape_args(), image)
+            buf.copy_(image)
+        return buf
 
 
 def flatten_state_dict(sd, ppffcs):
@@ -1004,14 +907,12 @@ def forward_decode_batch(items, tr_num_bins=32, rot_num_bins=36, tables_out=None
         heads = torch.empty((P, 8), dtype=torch.float32, device=dev) if u_rot is not None else None
         need = _lib.lib().cppf_pair_mlp_workspace_bytes(pc.shape[0], feat.shape[1], dims, len(enc.ppffcs) - 1, enc.out_dim)
         ws = workspace(max(int(need), 256), dev, f"pair_mlp_batch{i}")       # (each list its own per-point table)
-        packed = enc._packed_weights(dev)
-        fill(arr[i], dev, pc=pc, nrm=nrm, feat=feat, idxs=idxs, packed=packed, u_tr=u_tr, u_rot=u_rot, outputs=outputs, heads=heads,
-             workspace=scratch(ws), n_points=pc.shape[0], n_pairs=P, vr0=float(it["vote_range"][0]), vr1=float(it["vote_range"][1]),
-             idx_is_i64=idxs.dtype == torch.int64)
-        keep.append((idxs, pc, nrm, feat, ws, packed, u_tr, u_rot))
+        enc._item(arr[i], pc, nrm, feat, idxs, ws, u_tr=u_tr, u_rot=u_rot, outputs=outputs, heads=heads,
+                  vr0=float(it["vote_range"][0]), vr1=float(it["vote_range"][1]))
+        keep.append((idxs, pc, nrm, feat, ws, u_tr, u_rot))
         outs.append((outputs, heads))
-    call("cppf_pair_mlp_bf16_decode_batch" if enc0.precision == "bf16" else "cppf_pair_mlp_decode_batch", dev, len(items), arr, items[0]["feat"].shape[1], dims, len(enc0.ppffcs) - 1, enc0.out_dim,
-         tr_num_bins, rot_num_bins)
+    call(enc0._entry("decode_batch"), dev, len(items), arr, items[0]["feat"].shape[1], dims, len(enc0.ppffcs) - 1, enc0.out_dim, tr_num_bins,
+         rot_num_bins)
     if tables_out is not None:      # the per-point tables this pass left (a batched second pass reuses them: cppf_pose_tail_batch)
         tables_out[:] = [k[4] for k in keep]
     return outs

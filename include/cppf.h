@@ -412,7 +412,8 @@ int cppf_pair_mlp_decode(const float* pc, const float* nrm, const float* feat, c
 /* The same call for up to 8 pair lists in ONE launch -- the instances of a frame (nocs/inference.py:120 loops over them), each with
  * its own cloud, pair list, outputs, per-point workspace and weight image (the reference keeps one network per category, :79-90).
  * The lists get workgroups in proportion to their lengths; the ~9 us a launch spends before its first MFMA are paid once.
- * Results are those of n_items cppf_pair_mlp_decode calls, bit for bit.  All items with heads / u_rot or none. */
+ * Results are those of n_items cppf_pair_mlp_decode calls, bit for bit.  All items with heads / u_rot or none.  A list with
+ * n_pairs == 0 is CPPF_EINVAL here (the bf16 entry below skips it: the one difference between the two item contracts). */
 typedef struct CppfPairMlpItem {
     const float* pc;        /* device f32[n_points,3] */
     const float* nrm;       /* device f32[n_points,3] */

@@ -174,13 +174,13 @@ def test_captured_pipeline_follows_weight_updates(golden, dev):
     pipe.run()
     pipe.run()
     g = pipe._graph
-    addr = enc._packed.data_ptr()
+    addr = enc._current_image().data_ptr()
     assert torch.equal(pipe.outputs, fresh())
     with torch.no_grad():                                   # what an optimizer step does
         for p in enc.parameters():
             p.add_(0.01 * torch.randn_like(p))
     pipe.run()
-    assert pipe._graph is g and enc._packed.data_ptr() == addr      # same graph, image rebuilt in place
+    assert pipe._graph is g and enc._current_image().data_ptr() == addr      # same graph, image rebuilt in place
     assert torch.equal(pipe.outputs, fresh())
     other = _encoder(dev, 2)
     enc.load_state_dict(other.state_dict())
@@ -193,6 +193,38 @@ def test_captured_pipeline_follows_weight_updates(golden, dev):
     enc.invalidate()                                        # ... until the caller says so
     pipe.run()
     assert pipe._graph is g and torch.equal(pipe.outputs, fresh()) and not torch.equal(pipe.outputs, before)
+
+
+def test_captured_bf16_pipeline_follows_weight_updates(golden, dev):
+    """the same for set_precision("bf16"): the bf16 image has its own buffer, rebuilt in place under the captured graph"""
+    enc = _encoder(dev, 1).set_precision("bf16")
+    cfg = CATEGORIES["mug"]
+    ob = syn.make_object("mug", 512, 11)
+    idx = syn.make_pairs(512, 32, 11)
+    P = idx.shape[0]
+    u_tr, u_rot = syn.make_uniforms(P, 11)
+    corners, dims = grid_shape(ob["pc"], cfg.res)
+    pipe = CenterPipeline(enc, cfg, 512, P, dims, dev)
+    pipe.load(ob["pc"], ob["normals"], ob["feat"], idx, u_tr, u_rot, corners[0].copy())
+
+    def fresh():
+        e2 = PPFEncoder([84, 32, 32, 16], 141).to(dev).eval().set_precision("bf16")
+        e2.load_state_dict(enc.state_dict())
+        with torch.no_grad():
+            o, _ = e2.forward_decode(pipe.pc, pipe.nrm, pipe.feat, pipe.idx, pipe.u_tr, cfg.vote_range, pipe.u_rot)
+        return o.clone()
+
+    pipe.run()
+    pipe.run()
+    g = pipe._graph
+    addr = enc._current_image().data_ptr()
+    assert enc._current_image().dtype == torch.int32 and torch.equal(pipe.outputs, fresh())
+    with torch.no_grad():                                   # what an optimizer step does
+        for p in enc.parameters():
+            p.add_(0.01 * torch.randn_like(p))
+    pipe.run()
+    assert pipe._graph is g and enc._current_image().data_ptr() == addr      # same graph, image rebuilt in place
+    assert torch.equal(pipe.outputs, fresh())
 
 
 def test_batch_runner_ragged_batch_bounded_cache(oracle, golden, dev):

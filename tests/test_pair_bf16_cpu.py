@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import image_cache_protocol
 import pair_bf16_cases as cases
 import pair_bf16_ref as R
 from cppf_amd import _lib
@@ -116,6 +117,13 @@ def test_set_precision_on_the_host():
         PPFEncoder([84, 64, 64, 16], 141).set_precision("bf16")        # no silent fp32 fall-back for other architectures
     with pytest.raises(_lib.CppfError, match="bf16"):
         PPFEncoder(STD, 200).set_precision("bf16")
+
+
+def test_image_cache_protocol_on_the_host():
+    """one image per precision, rebuilt in place and only when asked for (host pack: no device needed)"""
+    torch.manual_seed(3)
+    enc = PPFEncoder(STD, 141).eval()
+    image_cache_protocol.check(enc, enc.res_layers[1].fc1.weight)
 
 
 def test_emulation_equals_its_fp32_restatement_when_nothing_rounds():

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 import torch
 
+import image_cache_protocol
 import sprin_bf16_cases as cases
 import sprin_bf16_ref as R
 from cppf_amd import _lib
@@ -140,6 +141,13 @@ def test_set_precision_on_the_host():
     p16b = enc.set_precision("bf16")._packed_weights("cpu")[0]
     assert p16b is p16 and not torch.equal(p16b, before)               # re-packed in place, as the fp32 image is
     assert torch.equal(enc.set_precision("fp32")._packed_weights("cpu")[0][:_natural_floats(2)].view(torch.int32), p16b[:_natural_floats(2)])
+
+
+def test_image_cache_protocol_on_the_host():
+    """one image per precision, rebuilt in place and only when asked for (host pack: no device needed)"""
+    torch.manual_seed(3)
+    enc = PointEncoder(k=60, spfcs=STD, out_dim=32, num_layers=1).eval()
+    image_cache_protocol.check(enc, enc.spconvs[0].kernel[3].weight, tensor_of=lambda cached: cached[0])
 
 
 def test_emulation_without_rounding_is_the_reference(golden):
