@@ -1,7 +1,7 @@
 // Everything after the centre vote's arg-max for gfx950 (MI355X): translation from the arg-max, back-vote filter, survivor
 // compaction, orientation vote + sphere-bin count, axis sign / scale reductions, grid set-up (nocs/inference.py:194-195,209-339).
 // C ABI in include/cppf.h; reference semantics cited per kernel.  (Split from vote.hip in round 5; the centre vote stays there.)
-#include "vote_common.h"
+#include "backvote_common.h"
 #include "compact.h"
 
 // nocs/inference.py:209-210: cand = unravel_index(argmax); T = corners[0] + cand * res in fp64;
@@ -144,14 +144,7 @@ __device__ __forceinline__ void backvote_body(const float* __restrict__ points,
     const int entries = n_rots * (n_rots + 1) / 2;
     const bool in_lds = entries <= VOTE_TAB_LDS_MAX;
     if (in_lds) {
-        // the vote that produced gt_center left the same table in its workspace (VOTE_TAB_STAMP): 21 KB to load instead of
-        // 2 628 fp64 sincos per block
-        const float2* wtab = reinterpret_cast<const float2*>(reinterpret_cast<const char*>(vote_ws) + VOTE_WS_TAB);
-        if (vote_ws && vote_ws[31] == (VOTE_TAB_STAMP ^ (unsigned long long)n_rots) && rot_table_intact(wtab, n_rots)) {
-            for (int e = threadIdx.x; e < entries; e += blockDim.x) ltab[e] = wtab[e];
-        } else {
-            fill_rot_table(ltab, entries, threadIdx.x, blockDim.x);
-        }
+        bv_load_rot_table(ltab, entries, n_rots, vote_ws);
         __syncthreads();
     }
     const f3 cr = {corner[0], corner[1], corner[2]};
@@ -187,16 +180,8 @@ __device__ __forceinline__ void backvote_body(const float* __restrict__ points,
         if (mask) mask[idx] = nz;
         if (chunk_counts) count_survivor(idx, nz);
     };
-    // The reference's loop (:97-110) for one pair that passed stage 1, one pair per lane -- over the ARC of rotations that can
-    // pass :101 only, in index order.  With offset = cos(t) x + sin(t) y, |x| = |y| = rho and x, y, ab orthogonal,
-    //   |cc + offset - gt|^2 = |w|^2 + rho^2 - 2 (A cos t + B sin t),   w = gt - cc, A = w.x, B = w.y,
-    // so the distance test holds exactly where cos(t - phi) >= K / M, phi = atan2(B, A), M = |(A, B)|,
-    // K = (|w|^2 + rho^2 - tol^2) / 2: a run of indices around phi n / 2 pi, about 2 tol / res + 3 of them instead of n <= 72.
-    // The run is a superset (approximate acos / atan2 with their error bounds, one index of margin on either side, K lowered
-    // by the deviations of |offset|^2 from rho^2: roundings and the 1e-7 regulariser, which shortens ab by 1e-7 / L -- pairs
-    // closer than 1e-3 scan everything); each candidate still goes through the reference's exact arithmetic and the first
-    // one in index order wins, so the result is the reference's.  On inputs where every pair survives stage 1 (a trained
-    // network) the full loop was the kernel: 100 us at C2, a lane walking on average 36 rotations and a wave its slowest lane's.
+    // The reference's loop (:97-110) for one pair that passed stage 1, one pair per lane, over the arc of rotations that can pass
+    // :101 (bv_arc, backvote_common.h).
     auto rotations = [&](const int64_t idx) {
         const float2 o = reinterpret_cast<const float2*>(outputs)[idx];
         const int2 ij = load_ij(idx);
@@ -207,44 +192,19 @@ __device__ __forceinline__ void backvote_body(const float* __restrict__ points,
         const f3 x = scl3(xd, odist);
         const f3 y = cross3(x, ab);
         f3 found = {0.f, 0.f, 0.f};                                                   // :96
-        const int n = min((int)((double)(odist / res) * (2 * CPPF_PI)), n_rots);      // :97
+        const int n = bv_rot_count(odist, res, n_rots);
         const int tbase = n * (n - 1) / 2;
-        int lo = 0, cnt = n;
-        {
-            const f3 pb_ = ld3(points, ij.y);
-            const f3 dd = sub3(a, pb_);
-            const float L2 = dot3(dd, dd);
-            const f3 w = sub3(gt, cc);
-            const float A_ = dot3(w, x), B_ = dot3(w, y), w2 = dot3(w, w), rho2 = dot3(x, x);
-            const float M = __builtin_amdgcn_sqrtf(A_ * A_ + B_ * B_);
-            const float K = 0.5f * (w2 + rho2 - tol * tol) - (3e-4f * rho2 + 4e-6f * (w2 + rho2 + tol * tol));
-            if (n > 0 && L2 >= 1e-6f && M > 1e-30f) {
-                const float c = K * __builtin_amdgcn_rcpf(M);
-                if (c > 1.0005f) {
-                    cnt = 0;                                   // no rotation comes within tol of the centre
-                } else if (c > -0.9995f) {
-                    const float alpha = acos_approx(fminf(c, 1.f)) + 8e-4f;        // acos / atan2 errors, rcp, table angles
-                    const float phi = atan2_approx(B_, A_);
-                    const float k = (float)n * 0.159154943f;                       // n / 2 pi
-                    const float ic = phi * k, hw = fmaf(alpha, k, 1.0f);
-                    const int i_lo = (int)floorf(ic - hw), i_hi = (int)ceilf(ic + hw);
-                    if (i_hi - i_lo + 1 < n) {
-                        cnt = i_hi - i_lo + 1;
-                        lo = i_lo % n;
-                        lo = lo < 0 ? lo + n : lo;
-                    }
-                }
-            }
-        }
+        const f3 dd = sub3(a, ld3(points, ij.y));
+        const int2 arc = bv_arc(dot3(dd, dd), sub3(gt, cc), x, y, tol, n);
+        const int lo = arc.x, cnt = arc.y;
         const int p1 = max(0, lo + cnt - n);     // candidates that wrap past n - 1 come first in index order: 0 .. p1 - 1
         for (int kk = 0; kk < cnt; ++kk) {
             const int i = kk < p1 ? kk : lo + (kk - p1);
             const float2 cs = in_lds ? ltab[tbase + i] : rot_cs(i, n);
             const f3 offset = add3(scl3(x, cs.x), scl3(y, cs.y));
             const f3 pc = add3(cc, offset);
-            if (len3(sub3(pc, gt)) > tol) continue;                                   // :101
-            const f3 g = div3(sub3(pc, cr), res);
-            if (g.x < 0.f || g.y < 0.f || g.z < 0.f || g.x >= bx || g.y >= by || g.z >= bz) continue;  // :103-107
+            if (bv_too_far(pc, gt, tol)) continue;                                    // :101
+            if (bv_outside(pc, cr, res, bx, by, bz)) continue;                        // :103-107
             found = neg3(offset);                                                      // :108
             break;
         }
@@ -280,6 +240,9 @@ __device__ __forceinline__ void backvote_body(const float* __restrict__ points,
                     const f3 pa = pa_[u], pb = pb_[u];
                     const f3 dd = sub3(pa, pb);
                     const float L2 = dot3(dd, dd);
+                    // (The two screens below exist a second time, split into a pair's and a centre's part, in backvote_multi_kernel
+                    // of scene_multi.hip: as functions of backvote_common.h they changed this kernel's code.  A change to a
+                    // formula or a bound here belongs there too.)
                     if (L2 >= 1e-13f) {
                         // approximate arithmetic (v_sqrt / v_rcp, no exact divisions) and a slack far above its error: a pair
                         // that fails here cannot pass :101 for any rotation; the others get the reference's exact
@@ -307,7 +270,7 @@ __device__ __forceinline__ void backvote_body(const float* __restrict__ points,
                             const float proj_len = o.x, odist = o.y;
                             const f3 cc = sub3(a, scl3(ab, proj_len));
                             const f3 x = scl3(xd, odist);
-                            const int n = min((int)((double)(odist / res) * (2 * CPPF_PI)), n_rots);
+                            const int n = bv_rot_count(odist, res, n_rots);
                             const float dc = len3(sub3(cc, gt)), rho = len3(x);
                             pass = n > 0 && !(fabsf(dc - rho) > tol + 1e-5f * (dc + rho + tol) + 1e-7f);
                             if (!pass) finish(idx, f3{0.f, 0.f, 0.f});
@@ -319,10 +282,7 @@ __device__ __forceinline__ void backvote_body(const float* __restrict__ points,
                         }
                     }
                 }
-                const unsigned long long m = __ballot(pass);
-                if (pass)
-                    q[qn + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0))] = (uint32_t)idx;
-                qn += __popcll(m);
+                qn += bv_push(q + qn, pass, (uint32_t)idx);
                 while (qn >= 64) {
                     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                     const uint32_t pidx = q[qn - 64 + lane];
@@ -363,12 +323,8 @@ static int backvote_impl(const float* points, const float* outputs, float* out_o
     if (n_rots < 1 || n_rots > CPPF_MAX_ROTS || n_ppfs < 0 || n_ppfs > 0xffffffffll) return CPPF_EINVAL;
     if (n_ppfs == 0) return 0;
     if (!points || !outputs || (!out_offsets && !mask) || (!point_idxs && !idx64) || !corner || !gt_center) return CPPF_EINVAL;
-    const int entries = tri(n_rots);
-    const size_t lds = (entries <= VOTE_TAB_LDS_MAX ? (size_t)entries * sizeof(float2) : 0) + 4 * 128 * sizeof(uint32_t);
-    int64_t nb = (n_ppfs + 4 * 256 - 1) / (4 * 256);   // BV_U = 4 pairs per thread and trip
-    if (nb > 1024) nb = 1024;
-    hipLaunchKernelGGL(backvote_kernel, dim3((unsigned)nb), dim3(256), lds, (hipStream_t)stream, points,
-                       outputs, out_offsets, point_idxs, corner, res, n_ppfs, n_rots, gx, gy, gz, gt_center, tol,
+    hipLaunchKernelGGL(backvote_kernel, dim3((unsigned)backvote_blocks(n_ppfs)), dim3(256), backvote_lds_bytes(n_rots),
+                       (hipStream_t)stream, points, outputs, out_offsets, point_idxs, corner, res, n_ppfs, n_rots, gx, gy, gz, gt_center, tol,
                        mask, shape_dev, static_cast<const unsigned long long*>(vote_workspace), chunk_counts, idx64, idx32_out);
     CPPF_CHECK_LAUNCH();
     return 0;
@@ -1319,8 +1275,7 @@ extern "C" int cppf_pose_tail_batch(int n_items, const CppfPoseTailItem* items, 
         S.record_out = it.record_out; S.rec = it.rec; S.object_id_dev = it.object_id_dev; S.object_id_host = it.object_id_host;
         S.scale_mean[0] = it.scale_mean[0]; S.scale_mean[1] = it.scale_mean[1]; S.scale_mean[2] = it.scale_mean[2];
         S.regress_right = it.regress_right;
-        int64_t nb = (it.n_pairs + 4 * 256 - 1) / (4 * 256);
-        nb = nb > 256 ? 256 : nb;      // (every block loads the 21 KB rotation table: at least two trips per wave for it; 1024: 1 % slower)
+        int64_t nb = backvote_blocks(it.n_pairs, 256);      // (every block loads the 21 KB rotation table: at least two trips per wave for it; 1024: 1 % slower)
         bv_blocks = nb > bv_blocks ? nb : bv_blocks;
         nb = (it.n_pairs + CMP_BLOCK - 1) / CMP_BLOCK;
         cmp_blocks = nb > cmp_blocks ? nb : cmp_blocks;
@@ -1346,9 +1301,7 @@ extern "C" int cppf_pose_tail_batch(int n_items, const CppfPoseTailItem* items, 
     hipLaunchKernelGGL(tail_begin_batch_kernel, dim3((unsigned)n_items), dim3(256), 0, st, B);
     CPPF_CHECK_LAUNCH();
     // 2. back-vote filter (:216-231): mask + survivors per chunk of 1024 pairs; writes the int32 pair list on the way
-    const int entries = tri(n_rots);
-    const size_t lds_bv = (entries <= VOTE_TAB_LDS_MAX ? (size_t)entries * sizeof(float2) : 0) + 4 * 128 * sizeof(uint32_t);
-    hipLaunchKernelGGL(backvote_batch_kernel, dim3((unsigned)bv_blocks, (unsigned)n_items), dim3(256), lds_bv, st, B);
+    hipLaunchKernelGGL(backvote_batch_kernel, dim3((unsigned)bv_blocks, (unsigned)n_items), dim3(256), backvote_lds_bytes(n_rots), st, B);
     CPPF_CHECK_LAUNCH();
     // 3. order-preserving compaction of the survivors
     hipLaunchKernelGGL(compact_scatter_batch_kernel, dim3((unsigned)cmp_blocks, (unsigned)n_items), dim3(CMP_BLOCK), 0, st, B);

@@ -5,7 +5,7 @@
 //   cell 11  unsupervised instance segmentation            cppf_segment_instance
 // C ABI and the defined behaviour where the notebook has none: include/cppf.h.  The numpy restatement the tests hold these
 // kernels to, bit for bit: tests/zero_shot_ref.py.
-#include "vote_common.h"
+#include "backvote_common.h"
 
 #define SCN_TILE 8                    // proposals: the max table holds one (value, first index) per 8^3 cells
 #define SCN_TILE_CELLS (SCN_TILE * SCN_TILE * SCN_TILE)
@@ -16,8 +16,6 @@
 
 struct GaussWeights { double w[2 * SCN_MAX_RADIUS + 1]; };
 struct TileMax { float v; int32_t i; };
-
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ----------------------------------------------------------------------------- Gaussian smoothing (cell 9, line 1)
 // scipy.ndimage.gaussian_filter(grid, sigma, mode='reflect'): one correlate1d per axis, axes 0, 1, 2.  scipy converts each line
@@ -316,14 +314,13 @@ __global__ __launch_bounds__(256) void pair_filter_kernel(const float* __restric
 }
 
 // at most 16 384 workgroups of 256 lanes (tested: 4 194 304 + 333 pairs, every lane on its second trip or in the ragged tail)
-static int grid_blocks(int64_t n) { return (int)((n + 255) / 256 < 16384 ? ((n + 255) / 256 > 0 ? (n + 255) / 256 : 1) : 16384); }
 
 extern "C" int cppf_pair_filter_distinct(const float* pc, const float* nrm, const void* point_idxs, int idx_is_i64, int64_t n_points,
                                          int64_t n_pairs, uint8_t* keep, void* stream)
 {
     if (!pc || !nrm || !point_idxs || !keep || n_points < 0 || n_points > INT32_MAX || n_pairs < 0) return CPPF_EINVAL;
     if (n_pairs == 0) return 0;
-    hipLaunchKernelGGL(pair_filter_kernel, dim3(grid_blocks(n_pairs)), dim3(256), 0, (hipStream_t)stream, pc, nrm, point_idxs,
+    hipLaunchKernelGGL(pair_filter_kernel, dim3(blocks256(n_pairs)), dim3(256), 0, (hipStream_t)stream, pc, nrm, point_idxs,
                        idx_is_i64, n_points, n_pairs, keep);
     CPPF_CHECK_LAUNCH();
     return 0;
@@ -387,11 +384,11 @@ extern "C" int cppf_segment_instance(const int32_t* point_idxs, const uint8_t* s
     const size_t cws_bytes = workspace_bytes - cb - align256((size_t)n_pairs);
     if (hipError_t e = hipMemsetAsync(contrib, 0, (size_t)n_points * sizeof(int32_t), st)) return (int)e;
     if (n_pairs > 0)
-        hipLaunchKernelGGL(endpoint_hist_kernel, dim3(grid_blocks(n_pairs)), dim3(256), 0, st, point_idxs, surv_mask, n_pairs,
+        hipLaunchKernelGGL(endpoint_hist_kernel, dim3(blocks256(n_pairs)), dim3(256), 0, st, point_idxs, surv_mask, n_pairs,
                            n_points, contrib);
-    hipLaunchKernelGGL(point_mask_kernel, dim3(grid_blocks(n_points)), dim3(256), 0, st, contrib, n_points, min_contrib, point_mask);
+    hipLaunchKernelGGL(point_mask_kernel, dim3(blocks256(n_points)), dim3(256), 0, st, contrib, n_points, min_contrib, point_mask);
     if (n_pairs > 0)
-        hipLaunchKernelGGL(pair_keep_kernel, dim3(grid_blocks(n_pairs)), dim3(256), 0, st, point_idxs, surv_mask, n_pairs, n_points,
+        hipLaunchKernelGGL(pair_keep_kernel, dim3(blocks256(n_pairs)), dim3(256), 0, st, point_idxs, surv_mask, n_pairs, n_points,
                            point_mask, keep);
     CPPF_CHECK_LAUNCH();
     if (n_pairs == 0) {

@@ -5,39 +5,15 @@
 //                            into a [K,N] table in one pass, point masks, the kept pairs of every proposal in pair order
 // C ABI: include/cppf.h.  Each bit is held to cppf_backvote_ws / cppf_segment_instance bit for bit (tests/test_gpu_scene_multi.py).
 //
-// The arithmetic that decides a bit is the one of backvote_body (pose_tail.hip), which stays as it is: the pair's frame
-// (pair_frame), the rotation table (rot_cs / fill_rot_table) and the float3 helpers come from cppf_math.h / vote_common.h, which
-// both files include; the rotation count (:97), the distance test (:101) and the bound tests (:103-107) are the same expressions
-// in candidate() below.  Stage 1 (the circle-distance screen) and the arc of candidate rotations only decide which candidates are
-// LOOKED AT; both are supersets of what can pass (the bounds are derived at backvote_body), so a difference there could not change
-// a bit -- they are nevertheless the same formulae.
-#include "vote_common.h"
+// The arithmetic that decides a bit is backvote_body's (pose_tail.hip): both kernels call backvote_common.h, where it is derived.
+#include "backvote_common.h"
 #include "compact.h"
 
 #define BVM_MAX_CENTERS 32
 #define BVM_K_BITS 5
 #define BVM_MAX_PAIRS ((int64_t)1 << (32 - BVM_K_BITS))   // a queue entry is pair << 5 | k in one word
 
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // ----------------------------------------------------------------------------- back-vote at K centres
-// One candidate rotation of one (pair, centre): the reference's :99-108.  Returns true when the rotation passes and its offset
-// (the value :108 stores, negated) is non-zero in any component -- what nocs/inference.py:230 calls a survivor; `done` tells the
-// caller that the reference's loop ends here (:109).
-__device__ __forceinline__ bool candidate(const f3 cc, const f3 x, const f3 y, const float2 cs, const f3 gt, const float tol, const f3 cr,
-                                          const float res, const float bx, const float by, const float bz, bool& done)
-{
-    const f3 offset = add3(scl3(x, cs.x), scl3(y, cs.y));
-    const f3 pc = add3(cc, offset);
-    done = false;
-    if (len3(sub3(pc, gt)) > tol) return false;                                                    // :101
-    const f3 g = div3(sub3(pc, cr), res);
-    if (g.x < 0.f || g.y < 0.f || g.z < 0.f || g.x >= bx || g.y >= by || g.z >= bz) return false;   // :103-107
-    const f3 found = neg3(offset);                                                                  // :108
-    done = true;
-    return (found.x != 0.f) || (found.y != 0.f) || (found.z != 0.f);
-}
-
 __global__ __launch_bounds__(256) void backvote_multi_kernel(const float* __restrict__ points, const float* __restrict__ outputs,
                                                              const int32_t* __restrict__ point_idxs, const float* __restrict__ corner,
                                                              float res, int64_t n_ppfs, int n_rots, int gx, int gy, int gz,
@@ -53,15 +29,7 @@ __global__ __launch_bounds__(256) void backvote_multi_kernel(const float* __rest
     float* base_f = lds + (in_lds ? 2 * entries : 0);
     uint32_t* q = reinterpret_cast<uint32_t*>(base_f) + (threadIdx.x >> 6) * 128;
     float* lc = base_f + 4 * 128;
-    if (in_lds) {
-        // the scene vote that produced the centres left the same table in its workspace (VOTE_TAB_STAMP): see backvote_body
-        const float2* wtab = reinterpret_cast<const float2*>(reinterpret_cast<const char*>(vote_ws) + VOTE_WS_TAB);
-        if (vote_ws && vote_ws[31] == (VOTE_TAB_STAMP ^ (unsigned long long)n_rots) && rot_table_intact(wtab, n_rots)) {
-            for (int e = threadIdx.x; e < entries; e += blockDim.x) ltab[e] = wtab[e];
-        } else {
-            fill_rot_table(ltab, entries, threadIdx.x, blockDim.x);
-        }
-    }
+    if (in_lds) bv_load_rot_table(ltab, entries, n_rots, vote_ws);
     for (int e = threadIdx.x; e < 3 * n_centers; e += blockDim.x) lc[e] = centers[e];
     __syncthreads();
     const f3 cr = {corner[0], corner[1], corner[2]};
@@ -84,41 +52,23 @@ __global__ __launch_bounds__(256) void backvote_multi_kernel(const float* __rest
         const f3 cc = sub3(a, scl3(ab, proj_len));
         const f3 x = scl3(xd, odist);
         const f3 y = cross3(x, ab);
-        const int n = min((int)((double)(odist / res) * (2 * CPPF_PI)), n_rots);      // :97
+        const int n = bv_rot_count(odist, res, n_rots);
         const int tbase = n * (n - 1) / 2;
-        int lo = 0, cnt = n;
-        {
-            const f3 pb_ = ld3(points, ij.y);
-            const f3 dd = sub3(a, pb_);
-            const float L2 = dot3(dd, dd);
-            const f3 w = sub3(gt, cc);
-            const float A_ = dot3(w, x), B_ = dot3(w, y), w2 = dot3(w, w), rho2 = dot3(x, x);
-            const float M = __builtin_amdgcn_sqrtf(A_ * A_ + B_ * B_);
-            const float K = 0.5f * (w2 + rho2 - tol * tol) - (3e-4f * rho2 + 4e-6f * (w2 + rho2 + tol * tol));
-            if (n > 0 && L2 >= 1e-6f && M > 1e-30f) {
-                const float c = K * __builtin_amdgcn_rcpf(M);
-                if (c > 1.0005f) {
-                    cnt = 0;
-                } else if (c > -0.9995f) {
-                    const float alpha = acos_approx(fminf(c, 1.f)) + 8e-4f;
-                    const float phi = atan2_approx(B_, A_);
-                    const float kk = (float)n * 0.159154943f;
-                    const float ic = phi * kk, hw = fmaf(alpha, kk, 1.0f);
-                    const int i_lo = (int)floorf(ic - hw), i_hi = (int)ceilf(ic + hw);
-                    if (i_hi - i_lo + 1 < n) {
-                        cnt = i_hi - i_lo + 1;
-                        lo = i_lo % n;
-                        lo = lo < 0 ? lo + n : lo;
-                    }
-                }
-            }
-        }
+        const f3 dd = sub3(a, ld3(points, ij.y));
+        const int2 arc = bv_arc(dot3(dd, dd), sub3(gt, cc), x, y, tol, n);
+        const int lo = arc.x, cnt = arc.y;
         const int p1 = max(0, lo + cnt - n);     // candidates that wrap past n - 1 come first in index order
         for (int kk = 0; kk < cnt; ++kk) {
             const int i = kk < p1 ? kk : lo + (kk - p1);
             const float2 cs = in_lds ? ltab[tbase + i] : rot_cs(i, n);
-            bool done;
-            const bool nz = candidate(cc, x, y, cs, gt, tol, cr, res, bx, by, bz, done);
+            const f3 offset = add3(scl3(x, cs.x), scl3(y, cs.y));
+            const f3 pc = add3(cc, offset);
+            bool done = false, nz = false;         // (flags, not `continue`: the shape that keeps this kernel's registers)
+            if (!bv_too_far(pc, gt, tol) && !bv_outside(pc, cr, res, bx, by, bz)) {     // :101, :103-107
+                const f3 found = neg3(offset);                                          // :108; a survivor has found != 0
+                done = true;
+                nz = (found.x != 0.f) || (found.y != 0.f) || (found.z != 0.f);
+            }
             if (nz) atomicOr(surv_bits + idx, 1u << k);       // (zeroed by the host entry; integer OR: the same word on every run)
             if (done) break;
         }
@@ -145,7 +95,8 @@ __global__ __launch_bounds__(256) void backvote_multi_kernel(const float* __rest
             for (int u = 0; u < BV_U; ++u) {
                 const int64_t idx = base + u * 64 + lane;
                 // the pair's part of stage 1, once: mode 0 = no centre can pass, 1 = the approximate circle test, 2 = (nearly)
-                // coincident points, where the exact frame decides what is degenerate
+                // coincident points, where the exact frame decides what is degenerate.  (backvote_body's two screens, derived
+                // there, split into this part and the centre's below: a change to a formula or a bound belongs in both.)
                 int mode = 0;
                 f3 cc = {0.f, 0.f, 0.f}, ax = {0.f, 0.f, 0.f};
                 float rho = 0.f, squash = 0.f;
@@ -169,7 +120,7 @@ __global__ __launch_bounds__(256) void backvote_multi_kernel(const float* __rest
                         if (pair_frame(points, ij.x, ij.y, a, ab, xd)) {
                             const float proj_len = o.x, odist = o.y;
                             cc = sub3(a, scl3(ab, proj_len));
-                            const int n = min((int)((double)(odist / res) * (2 * CPPF_PI)), n_rots);
+                            const int n = bv_rot_count(odist, res, n_rots);
                             rho = len3(scl3(xd, odist));
                             mode = n > 0 ? 2 : 0;
                         }
@@ -191,12 +142,8 @@ __global__ __launch_bounds__(256) void backvote_multi_kernel(const float* __rest
                             const float dc = len3(sub3(cc, gt));
                             pass = !(fabsf(dc - rho) > tol + 1e-5f * (dc + rho + tol) + 1e-7f);
                         }
-                        const unsigned long long m = __ballot(pass);
-                        if (m == 0ull) continue;
-                        if (pass)
-                            q[qn + __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0))] =
-                                ((uint32_t)idx << BVM_K_BITS) | (uint32_t)k;
-                        qn += __popcll(m);
+                        if (!__any(pass)) continue;
+                        qn += bv_push(q + qn, pass, ((uint32_t)idx << BVM_K_BITS) | (uint32_t)k);
                         if (qn >= 64) {                        // (qn < 64 before the push and <= 64 pushed: one drain, < 128 entries)
                             __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
                             const uint32_t item = q[qn - 64 + lane];
@@ -227,13 +174,9 @@ extern "C" int cppf_backvote_multi(const float* points, const float* outputs, co
     if (!points || !outputs || !point_idxs || !corner || !centers || !surv_bits) return CPPF_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (hipError_t e = hipMemsetAsync(surv_bits, 0, (size_t)n_ppfs * sizeof(uint32_t), st)) return (int)e;
-    const int entries = tri(n_rots);
-    const size_t lds = (entries <= VOTE_TAB_LDS_MAX ? (size_t)entries * sizeof(float2) : 0) + 4 * 128 * sizeof(uint32_t) +
-                       3 * BVM_MAX_CENTERS * sizeof(float);
-    int64_t nb = (n_ppfs + 4 * 256 - 1) / (4 * 256);   // BV_U = 4 pairs per thread and trip
-    if (nb > 1024) nb = 1024;
-    hipLaunchKernelGGL(backvote_multi_kernel, dim3((unsigned)nb), dim3(256), lds, st, points, outputs, point_idxs, corner, res, n_ppfs,
-                       n_rots, gx, gy, gz, centers, n_centers, tol, surv_bits, static_cast<const unsigned long long*>(vote_workspace));
+    const size_t lds = backvote_lds_bytes(n_rots, 3 * BVM_MAX_CENTERS * sizeof(float));
+    hipLaunchKernelGGL(backvote_multi_kernel, dim3((unsigned)backvote_blocks(n_ppfs)), dim3(256), lds, st, points, outputs, point_idxs,
+                       corner, res, n_ppfs, n_rots, gx, gy, gz, centers, n_centers, tol, surv_bits, static_cast<const unsigned long long*>(vote_workspace));
     CPPF_CHECK_LAUNCH();
     return 0;
 }
@@ -375,7 +318,6 @@ __global__ __launch_bounds__(CMP_BLOCK) void scatter_multi_kernel(const uint32_t
 }
 
 static int64_t chunks_of(int64_t n_pairs) { return (n_pairs + CMP_BLOCK - 1) / CMP_BLOCK; }
-static int blocks256(int64_t n) { return (int)((n + 255) / 256 < 16384 ? ((n + 255) / 256 > 0 ? (n + 255) / 256 : 1) : 16384); }
 
 extern "C" size_t cppf_segment_instances_workspace_bytes(int64_t n_points, int64_t n_pairs, int n_centers)
 {

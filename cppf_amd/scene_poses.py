@@ -4,26 +4,26 @@ cells 8-11: scene vote, smoothed-grid proposals, back-vote, "unsupervised instan
 path's (nocs/inference.py:259-339 on the proposal's kept pairs):
 
   1  all-heads first pass over every pair               PPFEncoder.forward_decode (fp32 or bf16, as the encoder is set)
-  2  scene vote, proposals                              voting.vote_argmax, zero_shot.scene_proposals_device; one read-back
-  3  back-vote at every proposal, segmentation          cppf_backvote_multi, cppf_segment_instances: ONE pass over the pair list for
-                                                        all proposals (csrc/scene_multi.hip); the K+1 list offsets are read back
+  2  scene vote, proposals                              scene_stage.vote_proposals; one read-back
+  3  back-vote at every proposal, segmentation          scene_stage.segment_proposals (cppf_backvote_multi, cppf_segment_instances):
+                                                        ONE pass over the pair list for all proposals (csrc/scene_multi.hip); the
+                                                        K+1 list offsets are read back
   4  orientation votes, axis signs, scale per proposal  cppf_rot_sphere_count_dirs(_order), cppf_pose_sums on the proposal's list;
                                                         every proposal enqueued, then one read-back of all records and masks
 
 The single-list entry points of step 4 take the list's address from the host, which is why the offsets of step 3 are read before
-it (K + 1 integers; the same read decides whether the kept-pair buffer was large enough).  cppf_amd.zero_shot stays the path for
-the notebook's 9-wide regression head."""
+it (K + 1 integers; the same read decides whether the kept-pair buffer was large enough).  Steps 2 and 3 and scene_frame's
+pre-processing are scene_stage.py's, shared with cppf_amd.zero_shot, which stays the path for the notebook's 9-wide regression head."""
 import numpy as np
 import torch
 
 from . import _lib
 from ._torch_util import call, canon, require_cuda, scratch, workspace
-from .models import voting
-from .utils.util import fibonacci_sphere, num_sphere_bins
-from .zero_shot import _check_loop_args, _compact, _on_device, _pairs_tensor, scene_proposals_device
+from .scene_stage import (MAX_CENTERS, backvote_multi, frame_cloud, frame_inputs, on_device, pairs_tensor, segment_instances,
+                          segment_proposals, sphere_tables, vote_proposals)
+from .zero_shot import check_loop_args
 
-F32, I32, U8 = torch.float32, torch.int32, torch.uint8
-MAX_CENTERS = 32                          # csrc/scene_multi.hip: BVM_MAX_CENTERS (one bit per proposal in a 32-bit word)
+F32, I32 = torch.float32, torch.int32
 STD_PPFFCS = [84, 32, 32, 16]             # train.py:35
 
 
@@ -40,44 +40,7 @@ def check_args(max_proposals, thresh=50, margin=10, max_iters=None):
     """the refusals that need no device"""
     if int(max_proposals) > MAX_CENTERS:
         raise ValueError(f"max_proposals must be <= {MAX_CENTERS} (one bit per proposal), got {max_proposals}")
-    return _check_loop_args(thresh, margin, max_proposals, max_iters)
-
-
-def _sphere_tables(angle_tol, dev):
-    """the orientation bins of nocs/inference.py:100-102: (fp64 host, fp32 device, fp64 device, order of the y column for the banded
-    count -- PoseWorkspace.sphere's rule)"""
-    sph64 = np.array(fibonacci_sphere(num_sphere_bins(angle_tol)), np.float64)
-    s32 = sph64.astype(np.float32)
-    unit = bool(np.all(np.abs(np.linalg.norm(s32.astype(np.float64), axis=-1) - 1.0) < 1e-4))
-    dy = np.diff(s32[:, 1])
-    sorted_y = (1 if np.all(dy <= 0) else (-1 if np.all(dy >= 0) else 0)) if unit else 0
-    return sph64, torch.from_numpy(s32).to(dev), torch.from_numpy(sph64).to(dev), sorted_y
-
-
-def backvote_multi(pc, outputs, idx32, corner, res, dims, centers, num_rots=72, tol=None, vote_ws=None, out=None):
-    """cppf_backvote_multi: bit k of the returned u32[P] (an int32 tensor) = pair p survives the back-vote at centers[k] (device
-    f32[K,3], K <= 32); tol = float32(3 res) by default.  Everything is enqueued on the current stream."""
-    dev = pc.device
-    P, K = idx32.shape[0], centers.shape[0]
-    tol = float(np.float32(3 * res)) if tol is None else float(np.float32(tol))
-    bits = torch.empty(max(P, 1), dtype=I32, device=dev) if out is None else out
-    gx, gy, gz = (int(d) for d in dims)
-    call("cppf_backvote_multi", dev, pc, outputs, idx32, corner, float(res), P, int(num_rots), gx, gy, gz, centers, K, tol, bits, vote_ws)
-    return bits
-
-
-def segment_instances(idx32, bits, n_points, n_centers, min_contrib=12, capacity=None):
-    """cppf_segment_instances: (point_masks u8[K,N], pairs i32[capacity], offsets i32[K+1]) device tensors, all enqueued; the kept
-    pairs of proposal k are pairs[offsets[k]:offsets[k+1]] when offsets[K] <= capacity (default: the number of pairs)"""
-    dev = idx32.device
-    P, K, N = idx32.shape[0], int(n_centers), int(n_points)
-    capacity = P if capacity is None else int(capacity)
-    masks = torch.empty((K, N), dtype=U8, device=dev)
-    pairs = torch.empty(max(capacity, 1), dtype=I32, device=dev)
-    offsets = torch.empty(K + 1, dtype=I32, device=dev)
-    ws = workspace(_lib.lib().cppf_segment_instances_workspace_bytes(N, P, K), dev, "segment_multi")
-    call("cppf_segment_instances", dev, idx32, bits, P, N, K, int(min_contrib), masks, pairs, capacity, offsets, scratch(ws))
-    return masks, pairs, offsets
+    return check_loop_args(thresh, margin, max_proposals, max_iters)
 
 
 def scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, *, angle_tol=1.5, max_rot_pairs=10000, rot_order=None, num_rots=72,
@@ -105,12 +68,12 @@ def scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, *, angle_tol=1.5,
         raise ValueError(f"pc: expected a tensor on a HIP device, got {getattr(pc, 'device', type(pc).__name__)}")
     dev = pc.device
     pc, nrm = canon(pc, F32, dev, "pc", (3,)), canon(nrm, F32, dev, "nrm", (3,))
-    idx = _pairs_tensor(idx, dev)
+    idx = pairs_tensor(idx, dev)
     idx32 = idx.to(I32).contiguous()
     P, N = idx.shape[0], pc.shape[0]
     if given:
-        outputs = _on_device(outputs, dev, "outputs", (2,))
-        heads = _on_device(heads, dev, "heads", (8,))
+        outputs = on_device(outputs, dev, "outputs", (2,))
+        heads = on_device(heads, dev, "heads", (8,))
         if outputs.shape[0] != P or heads.shape[0] != P:
             raise ValueError(f"outputs / heads must have one row per pair ({P}), got {tuple(outputs.shape)} / {tuple(heads.shape)}")
     elif P:                                                                   # step 1
@@ -122,33 +85,23 @@ def scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, *, angle_tol=1.5,
         outputs, heads = torch.empty((0, 2), dtype=F32, device=dev), torch.empty((0, 8), dtype=F32, device=dev)
     if N == 0:
         raise ValueError("the scene cloud is empty")
-    corners, dims = grid_shape(pc.cpu().numpy(), cfg.res)                      # step 2
-    corner = torch.from_numpy(corners[0].copy()).to(dev)
-    out = dict(poses=[], outputs=outputs, heads=heads, grid=None, corner=corners[0], dims=dims,
+    out = dict(poses=[], outputs=outputs, heads=heads, grid=None,
                proposals=(np.zeros((0, 3), np.int32), np.zeros(0, np.float32), np.zeros(0, np.float32)),
                surv_bits=torch.zeros(P, dtype=I32, device=dev), offsets=np.zeros(1, np.int64), pairs=torch.empty(0, dtype=I32, device=dev))
     if P == 0 or int(max_proposals) == 0:
+        corners, dims = grid_shape(pc.cpu().numpy(), cfg.res)
+        out.update(corner=corners[0], dims=dims)
         return out
-    grid = torch.empty(dims, dtype=F32, device=dev)
-    voting.vote_argmax(pc, outputs, None, idx32, grid, corner, cfg.res, num_rots, True, accumulate=False)
-    loc, val, diff, count = scene_proposals_device(grid, sigma, thresh, margin, max_proposals, max_iters)
-    K = int(count.item())                                                     # the read-back of the proposals
-    loc, val, diff = loc[:K].cpu().numpy(), val[:K].cpu().numpy(), diff[:K].cpu().numpy()
-    out.update(grid=grid, proposals=(loc, val, diff))
+    grid, corners, dims, corner, loc, val, diff, worlds = vote_proposals(pc, outputs, idx32, cfg, num_rots, sigma, thresh, margin,
+                                                                         max_proposals, max_iters)                  # step 2
+    K = loc.shape[0]
+    out.update(grid=grid, corner=corners[0], dims=dims, proposals=(loc, val, diff))
     if K == 0:
         return out
-    worlds = corners[0].astype(np.float64)[None] + loc.astype(np.int64) * float(cfg.res)          # fp64, as zero_shot_scene
-    centers = torch.from_numpy(np.ascontiguousarray(worlds.astype(np.float32))).to(dev)
-
     vws = workspace(256, dev, "vote")                                         # step 3 (the vote's rotation table, when it left one)
-    bits = backvote_multi(pc, outputs, idx32, corner, cfg.res, dims, centers, num_rots, vote_ws=vws if vws.numel() >= 32768 else None)
-    masks, pairs, offsets_d = segment_instances(idx32, bits, N, K, min_contrib)
-    offsets = offsets_d.cpu().numpy().astype(np.int64)
-    if offsets[K] > pairs.shape[0]:                                           # more kept (pair, proposal) items than pairs: once more
-        masks, pairs, offsets_d = segment_instances(idx32, bits, N, K, min_contrib, capacity=int(offsets[K]))
-    counts_d = (offsets_d[1:] - offsets_d[:-1]).contiguous()
-
-    sph64, sph32_d, sph64_d, sorted_y = _sphere_tables(angle_tol, dev)        # step 4
+    masks, pairs, offsets, counts_d, bits = segment_proposals(pc, outputs, idx32, corner, cfg.res, dims, worlds, num_rots, None, min_contrib,
+                                                              vote_ws=vws if vws.numel() >= 32768 else None)
+    sph64, sph32_d, sph64_d, sorted_y = sphere_tables(angle_tol, dev)         # step 4
     S = sph64.shape[0]
     thr = float(np.float32(np.cos(angle_tol / 180 * np.pi)))
     n_dirs = 2 if cfg.regress_right else 1
@@ -182,17 +135,8 @@ def scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, *, angle_tol=1.5,
                        scale_norm=p["scale_norm"], RT=RT, cnt=float(val[k]), diff=float(diff[k]), point_mask=masks_h[k],
                        n_pairs=int(offsets[k + 1] - offsets[k]))
         out["poses"].append(poses_k)
-    out.update(surv_bits=bits[:P], offsets=offsets, pairs=pairs[:int(offsets[K])])
+    out.update(surv_bits=bits[0][:P], offsets=offsets, pairs=pairs[:int(offsets[K])])
     return out
-
-
-def frame_cloud(depth, intrinsics, cfg, jitter=None):
-    """the dense cloud of a whole frame and its normals, (hi f32[N,3], hi_nrm f32[N,3]) device tensors: frames.instance_cloud with
-    every pixel in the mask.  A function of (depth, intrinsics, cfg.res, cfg.knn, jitter) alone, so categories whose configs agree in
-    (res, knn) can share it (scene_frame's cloud=)."""
-    from .frames import instance_cloud
-    d = np.asarray(depth) if not isinstance(depth, torch.Tensor) else depth
-    return instance_cloud(depth, intrinsics, np.ones(tuple(d.shape), bool), cfg, jitter)
 
 
 def scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=5_000_000, seed=0, jitter=None, cloud=None, **kw):
@@ -203,36 +147,13 @@ def scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=5_000_00
     (hi, hi_nrm) pair frame_cloud returned for this depth, intrinsics, jitter and a config with the same (res, knn) -- it replaces the
     back-projection, the de-duplication and the normals (None: they are computed here: the same bits); kw: scene_poses' options.
     Adds hi_pc / hi_normals, indices, pc / normals, feat, idx, n_pairs (after the filter)."""
-    from .frames import draw_pairs
-    from .utils.util import sparse_quantize
     check_encoder(encoder, cfg)
     check_args(kw.get("max_proposals", 32), kw.get("thresh", 50), kw.get("margin", 10), kw.get("max_iters"))
     require_cuda()
-    hi, hi_nrm = frame_cloud(depth, intrinsics, cfg, jitter) if cloud is None else cloud
-    if hi.shape[0] == 0:
-        raise ValueError("the depth frame has no valid pixels")
-    _, ind = sparse_quantize(hi, return_index=True, quantization_size=4 * cfg.res)
-    pc, nrm = hi[ind].contiguous(), hi_nrm[ind].contiguous()
-    with torch.no_grad():
-        feat = point_encoder(hi[None], hi_nrm[None])[0][ind].contiguous()
-    idx, u = draw_pairs(seed, 0, int(n_pairs), pc.device, pc.shape[0])
-    # the filter keeps a subset in order: the uniforms of the kept pairs are found by running the draw's positions through it too
-    keep_pos = _kept_positions(pc, nrm, idx)
-    idx, u_tr, u_rot = idx[keep_pos].contiguous(), u[0][keep_pos].contiguous(), u[1][keep_pos].contiguous()
+    hi, hi_nrm, ind, pc, nrm, feat, idx, (u_tr, u_rot) = frame_inputs(depth, intrinsics, point_encoder, cfg, n_pairs, seed, jitter, cloud)
     out = scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, **kw)
     out.update(hi_pc=hi, hi_normals=hi_nrm, indices=ind, pc=pc, normals=nrm, feat=feat, idx=idx, n_pairs=int(idx.shape[0]))
     return out
-
-
-def _kept_positions(pc, nrm, idx):
-    """zero_shot.distinct_pairs as positions (i64, in order) instead of the pairs themselves"""
-    dev = pc.device
-    P = idx.shape[0]
-    keep = torch.empty(max(P, 1), dtype=U8, device=dev)
-    if P:
-        call("cppf_pair_filter_distinct", dev, pc, nrm, idx, idx.dtype == torch.int64, pc.shape[0], P, keep)
-    pos, _ = _compact(keep[:P], dev)
-    return pos.long()
 
 
 __all__ = ["scene_poses", "scene_frame", "frame_cloud", "backvote_multi", "segment_instances", "check_encoder", "check_args"]

@@ -1,0 +1,160 @@
+"""The proposal stage of a scene with no instance masks, shared by the notebook's path (zero_shot.py, 9-wide regression head) and
+the mask-free path (scene_poses.py, bin head): the callers' input forms, the frame pre-processing of nocs/zero_shot.ipynb cells
+3-6, the scene vote with its proposals (cells 8-9) and cell 11's back-vote and segmentation of ALL proposals in one pass over the
+pair list (csrc/scene_multi.hip).  What the heads do with each proposal's kept pairs stays in the two modules."""
+import numpy as np
+import torch
+
+from . import _lib
+from ._torch_util import call, canon, scratch, workspace
+from .models import voting
+from .utils.util import fibonacci_sphere, num_sphere_bins
+
+F32, I32, U8 = torch.float32, torch.int32, torch.uint8
+MAX_CENTERS = 32                          # csrc/scene_multi.hip: BVM_MAX_CENTERS (one bit per proposal in a 32-bit word)
+MAX_PAIRS = 1 << 27                       # csrc/scene_multi.hip: BVM_MAX_PAIRS (a queue entry is pair << 5 | k in one word)
+
+
+def pairs_tensor(idx, dev):
+    """the pair list as PPFEncoder takes it: a numpy array is host data and is uploaded (other integer widths widened); a tensor
+    must be int32 / int64 on `dev` -- any strides"""
+    if not isinstance(idx, torch.Tensor):
+        a = np.asarray(idx)
+        if a.dtype.kind not in "iu":
+            raise TypeError(f"pair list: expected integers, got {a.dtype}")
+        idx = torch.from_numpy(np.ascontiguousarray(a if a.dtype in (np.int32, np.int64) else a.astype(np.int64))).to(dev)
+    return canon(idx, (torch.int64, torch.int32), dev, "pair list", (2,))
+
+
+def on_device(x, dev, name, tail=None):
+    """f32 data of the caller on `dev`: a numpy array (or list) is uploaded, a tensor is converted where it is or refused"""
+    if not isinstance(x, torch.Tensor):
+        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32)).to(dev)
+    return canon(x, F32, dev, name, tail)
+
+
+def kept_positions(pc, nrm, idx):
+    """Cell 6: the positions (i64, in order) of the pairs of `idx` that are not "indistinguishable"; device tensors in"""
+    dev = pc.device
+    P = idx.shape[0]
+    keep = torch.empty(max(P, 1), dtype=U8, device=dev)
+    pos = torch.empty(max(P, 1), dtype=I32, device=dev)
+    count = torch.zeros(1, dtype=I32, device=dev)
+    if P:
+        call("cppf_pair_filter_distinct", dev, pc, nrm, idx, idx.dtype == torch.int64, pc.shape[0], P, keep)
+        cws = workspace(_lib.lib().cppf_compact_workspace_bytes(P), dev, "compact")
+        call("cppf_compact_mask", dev, keep, P, pos, count, scratch(cws))
+    return pos[:int(count.item())].long()
+
+
+def sphere_tables(angle_tol, dev):
+    """the orientation bins of nocs/inference.py:100-102: (fp64 host, fp32 device, fp64 device, order of the y column for the banded
+    count -- PoseWorkspace.sphere's rule; 1 for the Fibonacci sphere)"""
+    sph64 = np.array(fibonacci_sphere(num_sphere_bins(angle_tol)), np.float64)
+    s32 = sph64.astype(np.float32)
+    unit = bool(np.all(np.abs(np.linalg.norm(s32.astype(np.float64), axis=-1) - 1.0) < 1e-4))
+    dy = np.diff(s32[:, 1])
+    sorted_y = (1 if np.all(dy <= 0) else (-1 if np.all(dy >= 0) else 0)) if unit else 0
+    return sph64, torch.from_numpy(s32).to(dev), torch.from_numpy(sph64).to(dev), sorted_y
+
+
+def frame_cloud(depth, intrinsics, cfg, jitter=None):
+    """the dense cloud of a whole frame and its normals, (hi f32[N,3], hi_nrm f32[N,3]) device tensors: frames.instance_cloud with
+    every pixel in the mask.  A function of (depth, intrinsics, cfg.res, cfg.knn, jitter) alone, so categories whose configs agree in
+    (res, knn) can share it (frame_inputs' cloud=)."""
+    from .frames import instance_cloud
+    d = np.asarray(depth) if not isinstance(depth, torch.Tensor) else depth
+    return instance_cloud(depth, intrinsics, np.ones(tuple(d.shape), bool), cfg, jitter)
+
+
+def frame_inputs(depth, intrinsics, point_encoder, cfg, n_pairs, seed, jitter=None, cloud=None):
+    """Cells 3-6 on the device: the cloud de-duplicated at res (cloud=: frame_cloud's pair for this frame instead), the sparse cloud
+    at 4 res, SPRIN features on the dense cloud (its kNN is the dense cloud's), frames.draw_pairs(seed, 0, ...) and the
+    "indistinguishable" filter.  Returns hi, hi_nrm, ind, pc, nrm, feat, idx, (u_tr, u_rot): the filter keeps a subset in order,
+    and the draw's uniforms (which feed a bin decode) go through the same positions."""
+    from .frames import draw_pairs
+    from .utils.util import sparse_quantize
+    hi, hi_nrm = frame_cloud(depth, intrinsics, cfg, jitter) if cloud is None else cloud          # cell 3: res
+    if hi.shape[0] == 0:
+        raise ValueError("the depth frame has no valid pixels")
+    _, ind = sparse_quantize(hi, return_index=True, quantization_size=4 * cfg.res)                # cell 3: 4 res
+    pc, nrm = hi[ind].contiguous(), hi_nrm[ind].contiguous()
+    with torch.no_grad():
+        feat = point_encoder(hi[None], hi_nrm[None])[0][ind].contiguous()                        # cell 7 (kNN on the hi-res cloud)
+    idx, u = draw_pairs(seed, 0, int(n_pairs), pc.device, pc.shape[0])                            # cell 5
+    pos = kept_positions(pc, nrm, idx)                                                            # cell 6
+    return hi, hi_nrm, ind, pc, nrm, feat, idx[pos].contiguous(), (u[0][pos].contiguous(), u[1][pos].contiguous())
+
+
+def vote_proposals(pc, outputs, idx32, cfg, num_rots, sigma, thresh, margin, max_proposals, max_iters):
+    """Cells 8-9: the scene vote (adaptive, overwrite mode), the smoothed-grid proposals and their one read-back.  Returns grid (raw
+    vote, device), corners, dims (inference.grid_shape's), corner (device f32[3]), loc i32[K,3], val, diff (numpy) and worlds
+    f64[K,3] = corners[0] + loc * res in fp64 from the float32 corner."""
+    from .inference import grid_shape
+    from .zero_shot import scene_proposals_device
+    dev = pc.device
+    corners, dims = grid_shape(pc.cpu().numpy(), cfg.res)
+    corner = torch.from_numpy(corners[0].copy()).to(dev)
+    grid = torch.empty(dims, dtype=F32, device=dev)
+    voting.vote_argmax(pc, outputs, None, idx32, grid, corner, cfg.res, num_rots, True, accumulate=False)
+    loc, val, diff, count = scene_proposals_device(grid, sigma, thresh, margin, max_proposals, max_iters)
+    n = int(count.item())
+    loc, val, diff = loc[:n].cpu().numpy(), val[:n].cpu().numpy(), diff[:n].cpu().numpy()
+    worlds = corners[0].astype(np.float64)[None] + loc.astype(np.int64) * float(cfg.res)
+    return grid, corners, dims, corner, loc, val, diff, worlds
+
+
+def backvote_multi(pc, outputs, idx32, corner, res, dims, centers, num_rots=72, tol=None, vote_ws=None, out=None):
+    """cppf_backvote_multi: bit k of the returned u32[P] (an int32 tensor) = pair p survives the back-vote at centers[k] (device
+    f32[K,3], K <= 32); tol = float32(3 res) by default.  Everything is enqueued on the current stream."""
+    dev = pc.device
+    P, K = idx32.shape[0], centers.shape[0]
+    tol = float(np.float32(3 * res)) if tol is None else float(np.float32(tol))
+    bits = torch.empty(max(P, 1), dtype=I32, device=dev) if out is None else out
+    gx, gy, gz = (int(d) for d in dims)
+    call("cppf_backvote_multi", dev, pc, outputs, idx32, corner, float(res), P, int(num_rots), gx, gy, gz, centers, K, tol, bits, vote_ws)
+    return bits
+
+
+def segment_instances(idx32, bits, n_points, n_centers, min_contrib=12, capacity=None):
+    """cppf_segment_instances: (point_masks u8[K,N], pairs i32[capacity], offsets i32[K+1]) device tensors, all enqueued; the kept
+    pairs of proposal k are pairs[offsets[k]:offsets[k+1]] when offsets[K] <= capacity (default: the number of pairs)"""
+    dev = idx32.device
+    P, K, N = idx32.shape[0], int(n_centers), int(n_points)
+    capacity = P if capacity is None else int(capacity)
+    masks = torch.empty((K, N), dtype=U8, device=dev)
+    pairs = torch.empty(max(capacity, 1), dtype=I32, device=dev)
+    offsets = torch.empty(K + 1, dtype=I32, device=dev)
+    ws = workspace(_lib.lib().cppf_segment_instances_workspace_bytes(N, P, K), dev, "segment_multi")
+    call("cppf_segment_instances", dev, idx32, bits, P, N, K, int(min_contrib), masks, pairs, capacity, offsets, scratch(ws))
+    return masks, pairs, offsets
+
+
+def segment_proposals(pc, outputs, idx32, corner, res, dims, worlds, num_rots, tol, min_contrib, vote_ws=None, capacity=None):
+    """Cell 11's back-vote (tol = float32(3 res) when None) and "unsupervised instance segmentation" at every proposal centre
+    `worlds` ([K,3], handed on as fp32).  The centres go in groups of at most 32 (one bit each; fewer where P x group would pass
+    cppf_segment_instances' int32 offsets): per group one pass over the pair list and one read of its offsets, and where the kept
+    (pair, proposal) items outnumber `capacity` (default P) cppf_segment_instances alone once more with the reported size.
+    Returns (masks u8[K,N], pairs i32: device; offsets i64[K+1]: host; counts i32[K], bits (each group's survivor words): device);
+    the kept pairs of proposal k are pairs[offsets[k]:offsets[k+1]], positions in idx32 in order."""
+    dev = pc.device
+    N, P = pc.shape[0], idx32.shape[0]
+    if P >= MAX_PAIRS:
+        raise ValueError(f"the pair list has {P} pairs; one pass over all proposals takes fewer than {MAX_PAIRS} (2^27)")
+    centers = torch.from_numpy(np.ascontiguousarray(np.asarray(worlds, np.float64).reshape(-1, 3).astype(np.float32))).to(dev)
+    K = centers.shape[0]
+    group = max(1, min(MAX_CENTERS, (2 ** 31 - 1) // max(P, 1)))
+    masks, pairs, counts, bits, offsets = [], [], [], [], [0]
+    for g in range(0, K, group):
+        kg = min(group, K - g)
+        b = backvote_multi(pc, outputs, idx32, corner, res, dims, centers[g:g + kg], num_rots, tol, vote_ws)
+        m, p, off_d = segment_instances(idx32, b, N, kg, min_contrib, capacity)
+        off = off_d.cpu().numpy().astype(np.int64)
+        if off[kg] > p.shape[0]:                                              # more kept (pair, proposal) items than room: once more
+            m, p, off_d = segment_instances(idx32, b, N, kg, min_contrib, capacity=int(off[kg]))
+        masks.append(m), pairs.append(p[:int(off[kg])]), counts.append(off_d[1:] - off_d[:-1]), bits.append(b)
+        offsets.extend(offsets[g] + off[1:])
+    if len(masks) == 1:                                                       # (the usual case: nothing to join)
+        return masks[0], p, np.array(offsets, np.int64), counts[0].contiguous(), bits
+    cat = lambda ts, dt, *shape: torch.cat(ts + [torch.empty(shape, dtype=dt, device=dev)])      # (pairs: never an empty buffer)
+    return cat(masks, U8, 0, N), cat(pairs, I32, 1), np.array(offsets, np.int64), cat(counts, I32, 0), bits

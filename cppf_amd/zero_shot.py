@@ -1,15 +1,18 @@
 """Zero-shot instance segmentation and pose estimation (the reference README's "Zero-Shot Instance Segmentation and Pose
 Estimation", nocs/zero_shot.ipynb): one depth frame with NO instance masks in, every object's pose and point mask out.
 
-  cell 3   whole-frame cloud, two-level de-duplication, SPRIN features   zero_shot_frame (frames.instance_cloud, sparse_quantize)
+  cell 3   whole-frame cloud, two-level de-duplication, SPRIN features   zero_shot_frame (scene_stage.frame_inputs)
   cell 5   5 M uniform pairs over the sparse cloud                       frames.draw_pairs (cppf_sample_pairs)
   cell 6   drop "indistinguishable" pairs                                distinct_pairs (cppf_pair_filter_distinct + compaction)
   cell 7-8 9-wide regression head, scene vote                            PPFEncoder.forward_with_idx, cppf_vote_argmax
   cell 9   Gaussian smoothing + iterative peak proposals                 smooth_grid / scene_proposals (cppf_scene_proposals)
   cell 11  back-vote, segmentation, orientation, axis sign, scale        segment_instance / zero_shot_poses
 
-The notebook does cells 9 and 11 in scipy / numpy on the host after copying the grid off the device; here everything runs on the
-device and the host reads back the proposal count (to size the per-proposal work) and one small record per proposal.  The
+Cells 3-6, the vote with its proposals and cell 11's back-vote and segmentation (all proposals in one pass over the pair list, which
+therefore holds fewer than 2^27 pairs) are scene_stage.py's, shared with the bin head's scene_poses.py.  The notebook does cells 9
+and 11 in scipy / numpy on the host after copying the grid off the device; here everything runs on the device and the host reads
+back the proposals (to size the per-proposal work), the K + 1 offsets of the proposals' kept-pair lists (the pose step takes each
+list's address from the host) and at the end one small record and one point mask per proposal.  The
 semantics where the notebook has none (thin grids, a peak on a last plane, a first diff equal to the threshold) are documented at
 cppf_scene_proposals in include/cppf.h.  The notebook's "fine-grained centre vote" of cell 11 is computed and discarded there (T
 stays the proposal); it is not run here."""
@@ -18,8 +21,8 @@ import torch
 
 from . import _lib
 from ._torch_util import call, canon, require_cuda, scratch, workspace
-from .models import voting
-from .utils.util import fibonacci_sphere, num_sphere_bins
+from .scene_stage import frame_inputs, kept_positions, on_device, pairs_tensor, segment_proposals, sphere_tables, vote_proposals
+from .utils.util import num_sphere_bins  # noqa: F401  (zero_shot.num_sphere_bins: the bins of the default angle_tol)
 
 F32, I32, U8 = torch.float32, torch.int32, torch.uint8
 MAX_RADIUS, MAX_MARGIN = 32, 64          # csrc/scene.hip: SCN_MAX_RADIUS, SCN_MAX_MARGIN
@@ -65,7 +68,7 @@ def smooth_grid(grid, sigma=1.0, truncate=4.0):
     return out.cpu().numpy() if was_np else out
 
 
-def _check_loop_args(thresh, margin, max_proposals, max_iters):
+def check_loop_args(thresh, margin, max_proposals, max_iters):
     if not 1 <= int(margin) <= MAX_MARGIN:
         raise ValueError(f"margin must be in 1..{MAX_MARGIN}, got {margin}")
     if int(max_proposals) < 0:
@@ -76,6 +79,9 @@ def _check_loop_args(thresh, margin, max_proposals, max_iters):
     if not np.isfinite(float(thresh)):
         raise ValueError(f"thresh must be finite, got {thresh}")
     return max_iters
+
+
+_check_loop_args = check_loop_args          # (the name it had while only this module used it)
 
 
 def proposals_workspace(dims, device):
@@ -91,7 +97,7 @@ def scene_proposals_device(grid, sigma=1.0, thresh=50, margin=10, max_proposals=
     smoothed_out: optional device f32 grid that receives the smoothed grid (before any suppression); out: a previous result
     tuple to write into; ws: proposals_workspace(dims) (a fresh one otherwise)."""
     g, _ = _grid_tensor(grid)
-    max_iters = _check_loop_args(thresh, margin, max_proposals, max_iters)
+    max_iters = check_loop_args(thresh, margin, max_proposals, max_iters)
     w = gaussian_weights(sigma, truncate)
     dev, (gx, gy, gz) = g.device, g.shape
     K = int(max_proposals)
@@ -119,75 +125,13 @@ def scene_proposals(grid, corner, res, sigma=1, thresh=50, margin=10, max_propos
     return [(c + loc[k].astype(np.int64) * float(res), val[k], diff[k]) for k in range(n)]
 
 
-def _pairs_tensor(idx, dev):
-    """the pair list as PPFEncoder takes it: a numpy array is host data and is uploaded (other integer widths widened); a tensor
-    must be int32 / int64 on `dev` -- any strides"""
-    if not isinstance(idx, torch.Tensor):
-        a = np.asarray(idx)
-        if a.dtype.kind not in "iu":
-            raise TypeError(f"pair list: expected integers, got {a.dtype}")
-        idx = torch.from_numpy(np.ascontiguousarray(a if a.dtype in (np.int32, np.int64) else a.astype(np.int64))).to(dev)
-    return canon(idx, (torch.int64, torch.int32), dev, "pair list", (2,))
-
-
-def _on_device(x, dev, name, tail=None):
-    """f32 data of the caller on `dev`: a numpy array (or list) is uploaded, a tensor is converted where it is or refused"""
-    if not isinstance(x, torch.Tensor):
-        x = torch.from_numpy(np.ascontiguousarray(np.asarray(x), dtype=np.float32)).to(dev)
-    return canon(x, F32, dev, name, tail)
-
-
-def _compact(mask, dev):
-    """positions of the non-zero bytes of a device u8 mask, in order (cppf_compact_mask) -> (i32[n] device, n)"""
-    P = mask.numel()
-    surv = torch.empty(max(P, 1), dtype=I32, device=dev)
-    count = torch.zeros(1, dtype=I32, device=dev)
-    if P:
-        cws = workspace(_lib.lib().cppf_compact_workspace_bytes(P), dev, "compact")
-        call("cppf_compact_mask", dev, mask, P, surv, count, scratch(cws))
-    n = int(count.item())
-    return surv[:n], n
-
-
 def distinct_pairs(pc, nrm, idx):
     """Cell 6: the pairs of `idx` that are not "indistinguishable", in their order (same dtype as idx, on pc's device)."""
     require_cuda()
     dev = pc.device
     pc, nrm = canon(pc, F32, dev, "pc", (3,)), canon(nrm, F32, dev, "nrm", (3,))
-    idx = _pairs_tensor(idx, dev)
-    P = idx.shape[0]
-    keep = torch.empty(max(P, 1), dtype=U8, device=dev)
-    if P:
-        call("cppf_pair_filter_distinct", dev, pc, nrm, idx, idx.dtype == torch.int64, pc.shape[0], P, keep)
-    pos, _ = _compact(keep[:P], dev)
-    return idx[pos.long()]
-
-
-def _segment_enqueue(pc, outputs, idx32, T32, corner, res, dims, num_rots, tol, min_contrib):
-    """back-vote at T32 + segmentation, all enqueued: (point_mask u8[N], positions i32[P], count i32[1]) device tensors"""
-    dev = pc.device
-    N, P = pc.shape[0], idx32.shape[0]
-    surv = torch.empty(max(P, 1), dtype=U8, device=dev)
-    point_mask = torch.empty(N, dtype=U8, device=dev)
-    pairs = torch.empty(max(P, 1), dtype=I32, device=dev)
-    count = torch.zeros(1, dtype=I32, device=dev)
-    gx, gy, gz = (int(d) for d in dims)
-    if P:
-        call("cppf_backvote_ws", dev, pc, outputs, None, idx32, corner, float(res), P, int(num_rots), gx, gy, gz, None, T32, float(tol),
-             surv, None)
-    sws = workspace(_lib.lib().cppf_segment_instance_workspace_bytes(N, P), dev, "segment")
-    call("cppf_segment_instance", dev, idx32, surv, P, N, int(min_contrib), point_mask, pairs, count, scratch(sws))
-    return point_mask, pairs, count
-
-
-def _prep(pc, outputs, idx, corner):
-    require_cuda()
-    dev = pc.device
-    pc = canon(pc, F32, dev, "pc", (3,))
-    idx32 = _pairs_tensor(idx, dev).to(I32).contiguous()
-    outputs = _on_device(outputs, dev, "outputs")[:, :2].contiguous()
-    corner = _on_device(corner, dev, "corner")
-    return dev, pc, outputs, idx32, corner
+    idx = pairs_tensor(idx, dev)
+    return idx[kept_positions(pc, nrm, idx)]
 
 
 def segment_instance(pc, outputs, idx, center, corner, res, dims, num_rots=72, tol=None, min_contrib=12):
@@ -195,18 +139,15 @@ def segment_instance(pc, outputs, idx, center, corner, res, dims, num_rots=72, t
     `center` (tol = 3 res by default), the points that are endpoints of more than `min_contrib` of them, and the survivors with an
     endpoint among those points.  outputs: [P,2+] device (columns 0-1 = (mu, nu)); corner / dims: the scene grid's.
     Returns dict(point_mask bool[N] device, pairs i64[M] device = positions in idx, n_pairs M)."""
-    dev, pc, outputs, idx32, corner = _prep(pc, outputs, idx, corner)
-    tol = float(np.float32(3 * res)) if tol is None else float(np.float32(tol))
-    T32 = torch.as_tensor(np.asarray(center, np.float64).astype(np.float32)).to(dev)
-    pm, pairs, count = _segment_enqueue(pc, outputs, idx32, T32, corner, res, dims, num_rots, tol, min_contrib)
-    n = int(count.item())
-    return dict(point_mask=pm.bool(), pairs=pairs[:n].long(), n_pairs=n)
-
-
-def _sphere(angle_tol, dev):
-    S = num_sphere_bins(angle_tol)
-    sph64 = np.array(fibonacci_sphere(S), np.float64)
-    return sph64, torch.from_numpy(sph64.astype(np.float32)).to(dev), torch.from_numpy(sph64).to(dev)
+    require_cuda()
+    dev = pc.device
+    pc = canon(pc, F32, dev, "pc", (3,))
+    idx32 = pairs_tensor(idx, dev).to(I32).contiguous()
+    outputs = on_device(outputs, dev, "outputs")[:, :2].contiguous()
+    corner = on_device(corner, dev, "corner")
+    masks, pairs, offsets, _, _ = segment_proposals(pc, outputs, idx32, corner, res, dims, [center], num_rots, tol, min_contrib)
+    n = int(offsets[1])
+    return dict(point_mask=masks[0].bool(), pairs=pairs[:n].long(), n_pairs=n)
 
 
 def zero_shot_poses(encoder9, pc, nrm, feat, idx, cfg, angle_tol=2, max_rot_pairs=10000, rot_order=None, preds=None, num_rots=72,
@@ -227,11 +168,10 @@ def zero_shot_scene(encoder9, pc, nrm, feat, idx, cfg, angle_tol=2, max_rot_pair
                     sigma=1.0, thresh=50, margin=10, max_proposals=32, max_iters=None, min_contrib=12):
     """zero_shot_poses with the intermediate results: dict(poses, preds [P,9] device, grid (raw vote, device), corner f32[3],
     dims, proposals (loc i32[K,3], value, diff numpy))"""
-    from .inference import grid_shape
     require_cuda()
     dev = pc.device
     pc, nrm = canon(pc, F32, dev, "pc", (3,)), canon(nrm, F32, dev, "nrm", (3,))     # (detached: the host copy below is of a leaf too)
-    idx = _pairs_tensor(idx, dev)
+    idx = pairs_tensor(idx, dev)
     idx32 = idx.to(I32).contiguous()
     P = idx.shape[0]
     if preds is None:
@@ -239,49 +179,39 @@ def zero_shot_scene(encoder9, pc, nrm, feat, idx, cfg, angle_tol=2, max_rot_pair
             raise ValueError(f"the zero-shot path needs the 9-wide regression head, the encoder has out_dim {encoder9.out_dim}")
         with torch.no_grad():
             preds = encoder9.forward_with_idx(pc, nrm, feat, idx)                             # cell 7
-    preds = _on_device(preds, dev, "preds")
+    preds = on_device(preds, dev, "preds")
     if tuple(preds.shape) != (P, 9):
         raise ValueError(f"preds must be [{P}, 9], got {tuple(preds.shape)}")
     outputs = preds[:, :2].contiguous()
-    corners, dims = grid_shape(pc.cpu().numpy(), cfg.res)                                    # cell 8
-    corner = torch.from_numpy(corners[0].copy()).to(dev)
-    grid = torch.empty(dims, dtype=F32, device=dev)
-    voting.vote_argmax(pc, outputs, None, idx32, grid, corner, cfg.res, num_rots, True, accumulate=False)
-    loc, val, diff, count = scene_proposals_device(grid, sigma, thresh, margin, max_proposals, max_iters)   # cell 9
-    n = int(count.item())
-    loc, val, diff = loc[:n].cpu().numpy(), val[:n].cpu().numpy(), diff[:n].cpu().numpy()
-    worlds = [corners[0].astype(np.float64) + loc[k].astype(np.int64) * float(cfg.res) for k in range(n)]
-
-    # cell 11, every proposal enqueued before the one read-back
-    sph64, sph32_d, sph64_d = _sphere(angle_tol, dev)
+    grid, corners, dims, corner, loc, val, diff, worlds = vote_proposals(pc, outputs, idx32, cfg, num_rots, sigma, thresh, margin,
+                                                                         max_proposals, max_iters)                  # cells 8-9
+    # cell 11: all proposals segmented at once, then each one's pose step (its buffers first: after the offsets read the device waits)
+    n = worlds.shape[0]
+    sph64, sph32_d, sph64_d, sorted_y = sphere_tables(angle_tol, dev)
     S = sph64.shape[0]
     thr = float(np.float32(np.cos(angle_tol / 180 * np.pi)))
-    tol = float(np.float32(3 * cfg.res))
     if rot_order is not None:
         rot_order = torch.as_tensor(rot_order).to(device=dev, dtype=I32).contiguous()
     rws = workspace(_lib.lib().cppf_reduce_workspace_bytes(), dev, "zs_reduce")
-    recs, masks, counts_d = [], [], []
+    recs = torch.zeros((n, 10), dtype=torch.float64, device=dev)        # best_dir[3] | sign sums[3] | exp-scale sums[4]
+    counts = torch.zeros((n, S), dtype=I32, device=dev)
+    best_idx = torch.empty(n, dtype=torch.int64, device=dev)
+    masks, pairs, offsets, counts_d, _ = segment_proposals(pc, outputs, idx32, corner, cfg.res, dims, worlds, num_rots, None, min_contrib)
+    rot = preds.data_ptr() + 4 * 2
     for k in range(n):
-        T32 = torch.as_tensor(worlds[k].astype(np.float32)).to(dev)
-        pm, sel, cnt = _segment_enqueue(pc, outputs, idx32, T32, corner, cfg.res, dims, num_rots, tol, min_contrib)
-        counts = torch.zeros(S, dtype=I32, device=dev)
-        rec = torch.zeros(10, dtype=torch.float64, device=dev)          # best_dir[3] | sign sums[3] | exp-scale sums[4]
-        best_idx = torch.empty(1, dtype=torch.int64, device=dev)
-        rot = preds.data_ptr() + 4 * 2
+        sel = pairs[int(offsets[k]):int(offsets[k + 1])] if offsets[k + 1] > offsets[k] else pairs[:1]    # (empty: any valid address)
+        cnt, rec = counts_d[k:k + 1], recs[k]
         if rot_order is None:
-            call("cppf_rot_sphere_count", dev, pc, rot, 9, idx32, sel, cnt, P, int(max_rot_pairs), int(num_rots), sph32_d, S, thr, 1,
-                 counts)
+            call("cppf_rot_sphere_count", dev, pc, rot, 9, idx32, sel, cnt, P, int(max_rot_pairs), int(num_rots), sph32_d, S, thr,
+                 sorted_y, counts[k])
         else:
             call("cppf_rot_sphere_count_dirs_order", dev, pc, rot, 9, 1, 1, idx32, sel, cnt, P, rot_order, rot_order.numel(),
-                 int(max_rot_pairs), int(num_rots), sph32_d, S, thr, 1, counts, S)
-        call("cppf_counts_argmax_select", dev, counts, S, sph64_d, best_idx, rec[0:3])
+                 int(max_rot_pairs), int(num_rots), sph32_d, S, thr, sorted_y, counts[k], S)
+        call("cppf_counts_argmax_select", dev, counts[k], S, sph64_d, best_idx[k:k + 1], rec[0:3])
         call("cppf_axis_sign", dev, pc, nrm, idx32, sel, cnt, P, preds.data_ptr() + 4 * 4, 9, rec[0:3], rec[3:6], scratch(rws))
         call("cppf_scale_exp_sum", dev, preds.data_ptr() + 4 * 6, 9, sel, cnt, P, rec[6:10], scratch(rws))
-        recs.append(rec)
-        masks.append(pm)
-    poses = []
-    for k in range(n):
-        poses.append(_assemble(recs[k].cpu().numpy(), worlds[k], cfg, val[k], diff[k], masks[k].cpu().numpy().astype(bool)))
+    recs_h, masks_h = recs.cpu().numpy(), masks.cpu().numpy().astype(bool)
+    poses = [_assemble(recs_h[k], worlds[k], cfg, val[k], diff[k], masks_h[k]) for k in range(n)]
     return dict(poses=poses, preds=preds, grid=grid, corner=corners[0], dims=dims, proposals=(loc, val, diff))
 
 
@@ -309,20 +239,8 @@ def zero_shot_frame(depth, intrinsics, encoder9, point_encoder, cfg, n_pairs=5_0
     4 res), pc / normals (the sparse cloud), n_pairs (after the cell 6 filter), and zero_shot_scene's other entries).
     jitter: f32[n_pixels,3] standard-normal draws for cell 3's augmentation (None: none).  Pairs: frames.draw_pairs(seed, 0, ...)
     (the notebook's np.random.randint).  kw: zero_shot_poses' options."""
-    from .frames import draw_pairs, instance_cloud
-    from .utils.util import sparse_quantize
     require_cuda()
-    d = np.asarray(depth) if not isinstance(depth, torch.Tensor) else depth
-    ones = np.ones(tuple(d.shape), bool)
-    hi, hi_nrm = instance_cloud(depth, intrinsics, ones, cfg, jitter)                      # cell 3: res
-    if hi.shape[0] == 0:
-        raise ValueError("the depth frame has no valid pixels")
-    _, ind = sparse_quantize(hi, return_index=True, quantization_size=4 * cfg.res)         # cell 3: 4 res
-    pc, nrm = hi[ind].contiguous(), hi_nrm[ind].contiguous()
-    with torch.no_grad():
-        feat = point_encoder(hi[None], hi_nrm[None])[0][ind].contiguous()                 # cell 7 (kNN on the hi-res cloud)
-    idx, _ = draw_pairs(seed, 0, int(n_pairs), pc.device, pc.shape[0])                     # cell 5
-    idx = distinct_pairs(pc, nrm, idx)                                                     # cell 6
+    hi, hi_nrm, ind, pc, nrm, feat, idx, _ = frame_inputs(depth, intrinsics, point_encoder, cfg, n_pairs, seed, jitter)    # cells 3-6
     out = zero_shot_scene(encoder9, pc, nrm, feat, idx, cfg, **kw)
     out.update(hi_pc=hi, hi_normals=hi_nrm, indices=ind, pc=pc, normals=nrm, feat=feat, idx=idx, n_pairs=int(idx.shape[0]))
     return out

@@ -2,7 +2,7 @@
 (the method of scripts/bench_precision.py):
 
   new       cppf_backvote_multi + cppf_segment_instances                      (csrc/scene_multi.hip)
-  baseline  K x (cppf_backvote_ws + cppf_segment_instance)                    (zero_shot._segment_enqueue, what zero_shot_scene loops over)
+  baseline  K x (cppf_backvote_ws + cppf_segment_instance)                    (`single` below: what zero_shot_scene looped over before it took the new route)
 
 on a synthetic scene of eight bowls with perfect (mu, nu) for within-object pairs, K in {1, 4, 8, 32} proposals at 500 000 and
 5 000 000 pairs.  The K centres are the objects' centres, then the same centres moved by two cells per round, so every proposal sits
@@ -30,7 +30,8 @@ sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 import cppf_amd.synthetic as syn                                        # noqa: E402
 from bench_precision import stats                                        # noqa: E402
-from cppf_amd import scene_poses, training, zero_shot                    # noqa: E402
+from cppf_amd import _lib, scene_poses, training                          # noqa: E402
+from cppf_amd._torch_util import call, scratch, workspace                # noqa: E402
 from cppf_amd.config import CATEGORIES                                   # noqa: E402
 from cppf_amd.inference import grid_shape                                # noqa: E402
 
@@ -82,6 +83,20 @@ def timed_alternating(routes, reps, warmup=3):
     return {n: [a.elapsed_time(b) for a, b in v] for n, v in evs.items()}
 
 
+def single(pc, outputs, idx32, T32, corner, res, dims, num_rots, tol, min_contrib):
+    """the baseline: back-vote at T32 + segmentation of one proposal, all enqueued: (point_mask u8[N], positions i32[P], count i32[1])"""
+    dev = pc.device
+    N, P = pc.shape[0], idx32.shape[0]
+    surv = torch.empty(P, dtype=torch.uint8, device=dev)
+    point_mask = torch.empty(N, dtype=torch.uint8, device=dev)
+    pairs = torch.empty(P, dtype=torch.int32, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    call("cppf_backvote_ws", dev, pc, outputs, None, idx32, corner, float(res), P, num_rots, *(int(d) for d in dims), None, T32, tol, surv, None)
+    sws = workspace(_lib.lib().cppf_segment_instance_workspace_bytes(N, P), dev, "segment")
+    call("cppf_segment_instance", dev, idx32, surv, P, N, min_contrib, point_mask, pairs, count, scratch(sws))
+    return point_mask, pairs, count
+
+
 def stage_rows(dev, reps):
     rows = []
     d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
@@ -100,7 +115,7 @@ def stage_rows(dev, reps):
                 return scene_poses.segment_instances(idxd, bits, N, K, 12)
 
             def base():
-                return [zero_shot._segment_enqueue(pcd, outd, idxd, cs[k], corner, cfg.res, dims, 72, tol, 12) for k in range(K)]
+                return [single(pcd, outd, idxd, cs[k], corner, cfg.res, dims, 72, tol, 12) for k in range(K)]
 
             masks, pairs, offsets = new()
             off = offsets.cpu().numpy().astype(np.int64)

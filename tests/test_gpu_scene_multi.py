@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import cppf_amd.synthetic as syn
-from cppf_amd import _lib, scene_poses
+from cppf_amd import _lib, scene_poses, scene_stage
 from cppf_amd._torch_util import stream_ptr
 from cppf_amd.config import CATEGORIES
 from cppf_amd.inference import grid_shape
@@ -207,6 +207,39 @@ def test_segment_instances(case, dev, source, P):
                 for k in range(K):
                     surv = ((bits >> np.uint32(k)) & 1).astype(bool)
                     assert np.array_equal(pairs2[off2[k]:off2[k + 1]], Z.segment(case.idx[:P], surv, N, min_contrib)[1])
+
+
+def test_segment_proposals_groups(case, dev):
+    """scene_stage.segment_proposals = K x (cppf_backvote_ws + cppf_segment_instance) -- every mask, list and count -- with one,
+    exactly one, two and three groups of 32 centres.  The centres: the fixture's 32, then the first two objects' centres (positions
+    32, 33), random positions inside the grid, and the third object's centre at position 64, so that the second and the third group
+    hold real objects (asserted on the single route's results: a grouping error cannot hide behind empty output).  One case runs
+    with capacity = 1, which makes every group that keeps more than one item take the retry."""
+    N, K_ALL = case.pc.shape[0], 65
+    rng = np.random.default_rng(6)
+    lo = case.corner.astype(np.float64)
+    rand = rng.uniform(lo, lo + (np.array(case.dims) - 1) * RES, (K_ALL - 35, 3))
+    centers = np.concatenate([case.centers, case.obj_centers[:2], rand, case.obj_centers[2:]]).astype(np.float32)
+    assert centers.shape == (K_ALL, 3)
+    d_centers = torch.from_numpy(np.ascontiguousarray(centers)).to(dev)
+    for P in (257, 4099):
+        d_idx, d_out = case.d_idx[:P].contiguous(), case.d_out[:P].contiguous()
+        surv = [backvote_ws(dev, case.d_pc, d_out, d_idx, case.d_corner, case.dims, d_centers[k], 72, case.tol) for k in range(K_ALL)]
+        for min_contrib in (0, 12):
+            want = [_segment_single(dev, d_idx, m, N, min_contrib) for m in surv]           # once per (P, min_contrib), for every K
+            if P == P_MAX and min_contrib == 0:
+                assert all(want[k][0].any() and want[k][1].size > 0 for k in (32, 33, 64))
+            for K in (1, 32, 33, 65):
+                for cap in ((None, 1) if (P, K, min_contrib) == (P_MAX, 65, 0) else (None,)):
+                    masks, pairs, offsets, counts, bits = scene_stage.segment_proposals(
+                        case.d_pc, d_out, d_idx, case.d_corner, RES, case.dims, centers[:K], 72, None, min_contrib, capacity=cap)
+                    masks, pairs, counts = masks.cpu().numpy().astype(bool), pairs.cpu().numpy(), counts.cpu().numpy()
+                    assert masks.shape == (K, N) and counts.shape == (K,) and offsets.shape == (K + 1,) and offsets[0] == 0
+                    assert len(bits) == (K + 31) // 32
+                    for k in range(K):
+                        assert np.array_equal(masks[k], want[k][0]), (P, K, k, min_contrib, cap)
+                        assert np.array_equal(pairs[offsets[k]:offsets[k + 1]], want[k][1]), (P, K, k, min_contrib, cap)
+                        assert counts[k] == want[k][1].size == offsets[k + 1] - offsets[k]
 
 
 def test_segment_instances_small_capacity(case, dev):

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import cppf_amd.synthetic as syn
-from cppf_amd import zero_shot
+from cppf_amd import scene_stage, zero_shot
 from cppf_amd.config import CATEGORIES
 from cppf_amd.utils.util import fibonacci_sphere
 
@@ -169,10 +169,14 @@ def test_graph_replay_equals_eager(dev):
     ws = zero_shot.proposals_workspace(dims, dev)
     res_t = tuple(torch.empty(s, dtype=t, device=dev) for s, t in [((32, 3), torch.int32), (32, torch.float32), (32, torch.float32),
                                                                    (1, torch.int32)])
-    T32 = torch.from_numpy(eager["poses"][0]["T"].astype(np.float32)).to(dev)
+    T32 = torch.from_numpy(eager["poses"][0]["T"].astype(np.float32)[None]).to(dev)
     cd = torch.from_numpy(corner.copy()).to(dev)
+
+    def segment():                                     # the enqueue zero_shot_scene shares with scene_poses, at one centre
+        bits = scene_stage.backvote_multi(pcd, od, i32, cd, cfg.res, dims, T32, 72, float(np.float32(3 * cfg.res)))
+        return scene_stage.segment_instances(i32, bits, pcd.shape[0], 1, 12)
     zero_shot.scene_proposals_device(grid, out=res_t, ws=ws)                     # warm-up (scratch allocated outside the capture)
-    zero_shot._segment_enqueue(pcd, od, i32, T32, cd, cfg.res, dims, 72, float(np.float32(3 * cfg.res)), 12)
+    segment()
     torch.cuda.synchronize()
     s = torch.cuda.Stream(dev)
     s.wait_stream(torch.cuda.current_stream(dev))
@@ -180,7 +184,7 @@ def test_graph_replay_equals_eager(dev):
     with torch.cuda.stream(s):
         with torch.cuda.graph(g, stream=s):
             zero_shot.scene_proposals_device(grid, out=res_t, ws=ws)
-            seg = zero_shot._segment_enqueue(pcd, od, i32, T32, cd, cfg.res, dims, 72, float(np.float32(3 * cfg.res)), 12)
+            seg = segment()
     for t in res_t:
         t.fill_(-7)
     g.replay()
@@ -189,9 +193,9 @@ def test_graph_replay_equals_eager(dev):
     loc, val, diff = eager["proposals"]
     assert n == loc.shape[0] and np.array_equal(res_t[0][:n].cpu().numpy(), loc)
     assert np.array_equal(_bits(res_t[1][:n].cpu().numpy()), _bits(val)) and np.array_equal(_bits(res_t[2][:n].cpu().numpy()), _bits(diff))
-    pm, pairs, cnt = seg
-    assert np.array_equal(pm.cpu().numpy().astype(bool), eager["poses"][0]["point_mask"])
-    assert int(cnt.item()) == eager["poses"][0]["n_pairs"]
+    masks, pairs, offsets = seg
+    assert np.array_equal(masks[0].cpu().numpy().astype(bool), eager["poses"][0]["point_mask"])
+    assert int(offsets[1].item()) == eager["poses"][0]["n_pairs"]
 
 
 def test_zero_shot_frame_demo_depth(oracle, dev):
