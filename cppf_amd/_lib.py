@@ -126,6 +126,10 @@ _SIGS = {
     # greedy 3D box NMS, all (image, class) groups in one call (csrc/box_nms.hip); the group table is a host array
     "cppf_box_nms_workspace_bytes": (sz, [i64, i32]),
     "cppf_box_nms_batch": (C.c_int, [vp, vp, vp, i64, vp, i32, C.c_double, vp, vp, vp, vp, sz, vp]),
+    # proposal verification, up to 32 proposals in one pass (csrc/verify.hip)
+    "cppf_proposal_support_workspace_bytes": (sz, [i64]),
+    "cppf_proposal_support": (C.c_int, [vp, vp, vp, i64, i64, i32, vp, vp, sz, vp]),
+    "cppf_box_support": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, vp, vp]),
     "cppf_knn": (C.c_int, [vp, vp, i32, i32, vp, vp]),
     "cppf_frame_cloud_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "cppf_frame_cloud_dyn": (C.c_int, [vp, i32, vp, i32, i32, i32, i32, vp, C.c_double, C.c_double, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),

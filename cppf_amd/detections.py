@@ -22,7 +22,12 @@ def _finite(p):
         and p["scale_norm"] > 0
 
 
-def pool_detections(outs, names, cfgs=None, nms_thresh=0.3, cross_category=False, score="diff", device=None):
+def _needs_verify(score, min_agreement, min_fill, min_within):
+    return score == "agreement" or any(m is not None for m in (min_agreement, min_fill, min_within))
+
+
+def pool_detections(outs, names, cfgs=None, nms_thresh=0.3, cross_category=False, score="diff", device=None, min_agreement=None,
+                    min_fill=None, min_within=None):
     """outs: scene_poses / scene_frame dicts, one per category, in the order of `names` (the categories' names); cfgs: their configs
     (kept beside the detections for callers; nothing here reads them).
     Every finite proposal with scale_norm > 0 becomes a detection dict:
@@ -38,22 +43,36 @@ def pool_detections(outs, names, cfgs=None, nms_thresh=0.3, cross_category=False
     Returns dict(detections=[...] in descending score order (equal scores: the higher pooled index first, NMS' tie rule),
     kept_per_category {name: n}, suppressed {name: n} (both passes), proposals_per_category {name: n}, result=dict(pred_class_ids
     i32[n] = category + 1 (0 is the background of a synset list ["BG"] + names), pred_RTs, pred_scales, pred_scores) as
-    evaluation.compute_degree_cm_mAP reads them, cfgs)."""
+    evaluation.compute_degree_cm_mAP reads them, cfgs).
+    Proposal verification (poses computed with verify=True, else ValueError): score="agreement" ranks by
+    pose["verify"]["agreement"], a ratio in [0, 1] that means the same for every network.  min_agreement / min_fill / min_within (None:
+    no filter) drop, BEFORE the NMS, every detection whose verify agreement / fill / within is below the bound.  When any of these is
+    used the dict gains filtered {name: n}, the detections the filters dropped per category; they count in proposals_per_category and
+    not in suppressed.  With all four at their defaults nothing here changes."""
     names = list(names)
     if len(outs) != len(names):
         raise ValueError(f"{len(outs)} outputs for {len(names)} category names")
-    if score not in ("diff", "cnt"):
-        raise ValueError(f"score must be 'diff' or 'cnt', got {score!r}")
-    dets = []
+    if score not in ("diff", "cnt", "agreement"):
+        raise ValueError(f"score must be 'diff', 'cnt' or 'agreement', got {score!r}")
+    verified = _needs_verify(score, min_agreement, min_fill, min_within)
+    bounds = [(key, float(m)) for key, m in (("agreement", min_agreement), ("fill", min_fill), ("within", min_within)) if m is not None]
+    dets, dropped = [], [0] * len(names)
     for c, out in enumerate(outs):
         for k, p in enumerate(out["poses"]):
-            if p is None or not _finite(p) or not np.isfinite(p[score]):
+            if verified and p is not None and "verify" not in p:
+                raise ValueError(f"score='agreement' and the min_agreement / min_fill / min_within filters read pose['verify']: proposal "
+                                 f"{k} of {names[c]!r} has none -- compute the poses with verify=True")
+            value = None if p is None else (p["verify"]["agreement"] if score == "agreement" else p[score])
+            if p is None or not _finite(p) or not np.isfinite(value):
+                continue
+            if any(p["verify"][key] < m for key, m in bounds):
+                dropped[c] += 1
                 continue
             RT = np.eye(4)
             RT[:3, :3] = np.asarray(p["R"], np.float64) * float(p["scale_norm"])
             RT[:3, 3] = np.asarray(p["T"], np.float64)
             dets.append(dict(class_name=names[c], category=c, RT=RT, scales=np.asarray(p["scale"], np.float64) / float(p["scale_norm"]),
-                             score=float(p[score]), pose=p, proposal=k))
+                             score=float(value), pose=p, proposal=k))
     n = len(dets)
     cat = np.array([d["category"] for d in dets], np.int64).reshape(n)
     scores = np.array([d["score"] for d in dets], np.float64).reshape(n)
@@ -71,24 +90,32 @@ def pool_detections(outs, names, cfgs=None, nms_thresh=0.3, cross_category=False
     kept = [dets[i] for i in keep]
     per_cat = lambda idx: OrderedDict((nm, int((cat[idx] == c).sum())) for c, nm in enumerate(names))
     total, left = per_cat(np.arange(n)), per_cat(keep)
+    suppressed = OrderedDict((nm, total[nm] - left[nm]) for nm in names)
+    extra = {}
+    if verified:
+        extra["filtered"] = OrderedDict(zip(names, dropped))
+        total = OrderedDict((nm, total[nm] + dropped[c]) for c, nm in enumerate(names))
     result = dict(pred_class_ids=(cat[keep] + 1).astype(np.int32), pred_RTs=RTs[keep].reshape(-1, 4, 4),
                   pred_scales=(np.stack([d["scales"] for d in kept]) if kept else np.zeros((0, 3))), pred_scores=scores[keep])
-    return dict(detections=kept, kept_per_category=left, suppressed=OrderedDict((nm, total[nm] - left[nm]) for nm in names),
-                proposals_per_category=total, result=result, cfgs=cfgs)
+    return dict(detections=kept, kept_per_category=left, suppressed=suppressed, proposals_per_category=total, result=result, cfgs=cfgs,
+                **extra)
 
 
 def frame_detections(depth, intrinsics, networks, n_pairs=5_000_000, seed=0, jitter=None, nms_thresh=0.3, cross_category=False,
-                     score="diff", **scene_kw):
+                     score="diff", min_agreement=None, min_fill=None, min_within=None, **scene_kw):
     """One depth frame with no instance masks -> the detections of all categories (pool_detections' dict, plus outs: the categories'
     scene_frame dicts).
     networks: an ordered mapping name -> (point_encoder, encoder, cfg), modules on one HIP device, in either precision (what the
     encoders are set to is what runs).  scene_frame runs once per category with the same `seed` (and jitter); the dense cloud and its
     normals are computed once per distinct (cfg.res, cfg.knn) and shared (scene_frame's cloud=: the same bits as without sharing).
-    The NMS runs on the networks' device.  scene_kw: scene_poses' options (thresh, max_proposals, ...)."""
+    The NMS runs on the networks' device.  score="agreement" / min_agreement / min_fill / min_within: pool_detections'; scene_frame
+    then runs with verify=True (only then).  scene_kw: scene_poses' options (thresh, max_proposals, ...)."""
     from .scene_poses import frame_cloud, scene_frame
     if not networks:
         raise ValueError("frame_detections needs at least one category network")
     names, outs, cfgs, clouds, dev = [], [], [], {}, None
+    if _needs_verify(score, min_agreement, min_fill, min_within):
+        scene_kw = dict(scene_kw, verify=True)
     for name, (point_encoder, encoder, cfg) in networks.items():
         key = (float(cfg.res), int(cfg.knn))
         if key not in clouds:
@@ -97,7 +124,8 @@ def frame_detections(depth, intrinsics, networks, n_pairs=5_000_000, seed=0, jit
                           **scene_kw)
         dev = out["pc"].device
         names.append(name); outs.append(out); cfgs.append(cfg)
-    res = pool_detections(outs, names, cfgs, nms_thresh, cross_category, score, device=dev)
+    res = pool_detections(outs, names, cfgs, nms_thresh, cross_category, score, device=dev, min_agreement=min_agreement,
+                          min_fill=min_fill, min_within=min_within)
     res["outs"] = outs
     return res
 

@@ -20,7 +20,7 @@ import torch
 from . import _lib
 from ._torch_util import call, canon, require_cuda, scratch, workspace
 from .scene_stage import (MAX_CENTERS, backvote_multi, frame_cloud, frame_inputs, on_device, pairs_tensor, segment_instances,
-                          segment_proposals, sphere_tables, vote_proposals)
+                          segment_proposals, sphere_tables, verify_proposals, vote_proposals)
 from .zero_shot import check_loop_args
 
 F32, I32 = torch.float32, torch.int32
@@ -44,7 +44,7 @@ def check_args(max_proposals, thresh=50, margin=10, max_iters=None):
 
 
 def scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, *, angle_tol=1.5, max_rot_pairs=10000, rot_order=None, num_rots=72,
-                sigma=1.0, thresh=50, margin=10, max_proposals=32, max_iters=None, min_contrib=12, outputs=None, heads=None):
+                sigma=1.0, thresh=50, margin=10, max_proposals=32, max_iters=None, min_contrib=12, outputs=None, heads=None, verify=False):
     """The poses of every object of a scene cloud, with no instance masks.
     encoder: PPFEncoder with the standard architecture and the bin head (out_dim = 2 tr_bins + 2 rot_bins + 5), on pc's device, in
     the precision it is set to; pc, nrm f32[N,3], feat f32[N,F], idx [P,2], u_tr / u_rot f32[P,2] (uniforms standing in for
@@ -55,7 +55,9 @@ def scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, *, angle_tol=1.5,
     Returns dict(poses, outputs, heads, grid (raw vote, device), corner f32[3], dims, proposals (loc i32[K,3], value, diff numpy),
     surv_bits (device i32[P], bit k = survivor at proposal k), offsets (numpy i64[K+1]), pairs (device i32: the kept lists));
     poses: one dict per proposal with T f64[3] (the proposal), R, up, right (None unless cfg.regress_right), scale f64[3],
-    scale_norm, RT f64[4,4], cnt (smoothed peak), diff, point_mask bool[N], n_pairs -- what inference.nocs_result reads."""
+    scale_norm, RT f64[4,4], cnt (smoothed peak), diff, point_mask bool[N], n_pairs -- what inference.nocs_result reads.
+    verify=True: every pose dict gains verify, scene_stage.verify_proposals' dict for that proposal (two more launches per group of 32
+    proposals and one more read-back after the poses; everything else is computed and launched as without it)."""
     from .inference import _assemble, grid_shape
     max_iters = check_args(max_proposals, thresh, margin, max_iters)
     given = outputs is not None and heads is not None
@@ -135,6 +137,9 @@ def scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, *, angle_tol=1.5,
                        scale_norm=p["scale_norm"], RT=RT, cnt=float(val[k]), diff=float(diff[k]), point_mask=masks_h[k],
                        n_pairs=int(offsets[k + 1] - offsets[k]))
         out["poses"].append(poses_k)
+    if verify:
+        for p, v in zip(out["poses"], verify_proposals(pc, idx32, bits, masks, out["poses"], cfg)):
+            p["verify"] = v
     out.update(surv_bits=bits[0][:P], offsets=offsets, pairs=pairs[:int(offsets[K])])
     return out
 

@@ -130,6 +130,12 @@ def segment_instances(idx32, bits, n_points, n_centers, min_contrib=12, capacity
     return masks, pairs, offsets
 
 
+def proposal_group(n_pairs):
+    """how many proposals one pass over a list of n_pairs pairs serves: 32 (one bit each), fewer where n_pairs x group would pass
+    cppf_segment_instances' int32 offsets"""
+    return max(1, min(MAX_CENTERS, (2 ** 31 - 1) // max(int(n_pairs), 1)))
+
+
 def segment_proposals(pc, outputs, idx32, corner, res, dims, worlds, num_rots, tol, min_contrib, vote_ws=None, capacity=None):
     """Cell 11's back-vote (tol = float32(3 res) when None) and "unsupervised instance segmentation" at every proposal centre
     `worlds` ([K,3], handed on as fp32).  The centres go in groups of at most 32 (one bit each; fewer where P x group would pass
@@ -143,7 +149,7 @@ def segment_proposals(pc, outputs, idx32, corner, res, dims, worlds, num_rots, t
         raise ValueError(f"the pair list has {P} pairs; one pass over all proposals takes fewer than {MAX_PAIRS} (2^27)")
     centers = torch.from_numpy(np.ascontiguousarray(np.asarray(worlds, np.float64).reshape(-1, 3).astype(np.float32))).to(dev)
     K = centers.shape[0]
-    group = max(1, min(MAX_CENTERS, (2 ** 31 - 1) // max(P, 1)))
+    group = proposal_group(P)
     masks, pairs, counts, bits, offsets = [], [], [], [], [0]
     for g in range(0, K, group):
         kg = min(group, K - g)
@@ -158,3 +164,87 @@ def segment_proposals(pc, outputs, idx32, corner, res, dims, worlds, num_rots, t
         return masks[0], p, np.array(offsets, np.int64), counts[0].contiguous(), bits
     cat = lambda ts, dt, *shape: torch.cat(ts + [torch.empty(shape, dtype=dt, device=dev)])      # (pairs: never an empty buffer)
     return cat(masks, U8, 0, N), cat(pairs, I32, 1), np.array(offsets, np.int64), cat(counts, I32, 0), bits
+
+
+# ----------------------------------------------------------------------------- proposal verification (csrc/verify.hip)
+VERIFY_COUNTS = ("within", "agree", "cross", "cross_agree", "mask_pts", "mask_in_box", "box_pts")
+VERIFY_RATIOS = (("agreement", "agree", "within"), ("leak", "cross_agree", "cross"), ("fill", "mask_in_box", "mask_pts"),
+                 ("purity", "mask_in_box", "box_pts"))
+
+
+def proposal_support(idx32, bits, masks, out=None):
+    """cppf_proposal_support: i32[K,4] (within, agree, cross, cross_agree) on the device for the K <= 32 rows of masks (u8[K,N], as
+    segment_instances writes them) and their survivor words `bits`; enqueued on the current stream, nothing is read back"""
+    dev = idx32.device
+    P, (K, N) = idx32.shape[0], masks.shape
+    counts = torch.empty((K, 4), dtype=I32, device=dev) if out is None else out
+    ws = workspace(_lib.lib().cppf_proposal_support_workspace_bytes(N), dev, "proposal_support")
+    call("cppf_proposal_support", dev, idx32, bits, masks, P, N, K, counts, scratch(ws))
+    return counts
+
+
+def box_support(pc, masks, centers, axes, half, out=None):
+    """cppf_box_support: i32[K,3] (mask_pts, mask_in_box, box_pts) on the device for K <= 32 oriented boxes -- centers f32[K,3], axes
+    f32[K,9] (row-major R: its columns are the axes), half f32[K,3] -- over the cloud pc f32[N,3] and the rows of masks u8[K,N]"""
+    dev = pc.device
+    K, N = masks.shape
+    counts = torch.empty((K, 3), dtype=I32, device=dev) if out is None else out
+    call("cppf_box_support", dev, pc, masks, centers, axes, half, N, K, counts)
+    return counts
+
+
+def verify_boxes(poses, cfg, pad=None):
+    """the boxes verify_proposals tests, f32[K,15] per proposal {centre T | axes R row-major | half extents scale / 2 + pad} (scale_3d
+    on the zero-shot path; pad = cfg.res by default), computed in fp64 and rounded once.  A pose that is not finite gets half extents
+    of -1: a box that holds no point."""
+    pad = float(cfg.res) if pad is None else float(pad)
+    boxes = np.zeros((len(poses), 15), np.float32)
+    for k, p in enumerate(poses):
+        row = np.concatenate([np.asarray(p["T"], np.float64).reshape(3), np.asarray(p["R"], np.float64).reshape(9),
+                              np.asarray(p["scale_3d"] if "scale_3d" in p else p["scale"], np.float64).reshape(3) / 2 + pad])
+        if np.all(np.isfinite(row)):
+            boxes[k] = row
+        else:
+            boxes[k, 12:] = -1
+    return boxes
+
+
+def verify_ratios(counts):
+    """one proposal's seven counts (VERIFY_COUNTS' order) -> the dict verify_proposals returns: the counts as ints and agreement =
+    agree / within, leak = cross_agree / cross, fill = mask_in_box / mask_pts, purity = mask_in_box / box_pts in fp64, each 0.0 where
+    its denominator is 0"""
+    d = {name: int(v) for name, v in zip(VERIFY_COUNTS, counts)}
+    for name, num, den in VERIFY_RATIOS:
+        d[name] = d[num] / d[den] if d[den] else 0.0
+    return d
+
+
+def verify_proposals(pc, idx32, bits, masks, poses, cfg, pad=None):
+    """Per-proposal evidence after the proposal stage: how far the pairs inside proposal k's point mask agree with
+    centre k, and how far the mask and the pose's box cover each other.
+    pc f32[N,3], idx32 i32[P,2], masks u8[K,N]: device tensors; bits: the survivor words of every group of <= 32 proposals, the list
+    segment_proposals returns (a single tensor: one group); poses: the K pose dicts (T, R and scale, or scale_3d on the zero-shot
+    path).  The box of proposal k has centre T, axes R's columns and half extents scale / 2 + pad (pad = cfg.res by default); a pose
+    that is not finite gets mask_in_box = box_pts = 0.  Both kernels run per group, then ONE read-back of the two count tables.
+    Returns one dict per proposal: the seven counts of VERIFY_COUNTS (int) and agreement, leak, fill, purity (fp64, verify_ratios)."""
+    dev = pc.device
+    K, P = len(poses), idx32.shape[0]
+    if K == 0:
+        return []
+    if tuple(masks.shape) != (K, pc.shape[0]):
+        raise ValueError(f"masks must be [{K}, {pc.shape[0]}] (one row per pose), got {tuple(masks.shape)}")
+    bits = [bits] if isinstance(bits, torch.Tensor) else list(bits)
+    group = proposal_group(P)
+    if len(bits) != (K + group - 1) // group:
+        raise ValueError(f"{len(bits)} survivor-word tensors for {K} proposals in groups of {group}")
+    boxes = torch.from_numpy(verify_boxes(poses, cfg, pad)).to(dev)
+    centers, axes, half = boxes[:, 0:3].contiguous(), boxes[:, 3:12].contiguous(), boxes[:, 12:15].contiguous()
+    table = torch.empty(7 * K, dtype=I32, device=dev)
+    sup, box = table[:4 * K].view(K, 4), table[4 * K:].view(K, 3)
+    for i, g in enumerate(range(0, K, group)):
+        e = min(g + group, K)
+        proposal_support(idx32, bits[i], masks[g:e], out=sup[g:e])
+        box_support(pc, masks[g:e], centers[g:e], axes[g:e], half[g:e], out=box[g:e])
+    t = table.cpu().numpy()                                                   # the one read-back
+    sup_h, box_h = t[:4 * K].reshape(K, 4), t[4 * K:].reshape(K, 3)
+    return [verify_ratios(np.concatenate([sup_h[k], box_h[k]])) for k in range(K)]

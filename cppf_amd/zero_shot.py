@@ -21,7 +21,8 @@ import torch
 
 from . import _lib
 from ._torch_util import call, canon, require_cuda, scratch, workspace
-from .scene_stage import frame_inputs, kept_positions, on_device, pairs_tensor, segment_proposals, sphere_tables, vote_proposals
+from .scene_stage import (frame_inputs, kept_positions, on_device, pairs_tensor, segment_proposals, sphere_tables, verify_proposals,
+                          vote_proposals)
 from .utils.util import num_sphere_bins  # noqa: F401  (zero_shot.num_sphere_bins: the bins of the default angle_tol)
 
 F32, I32, U8 = torch.float32, torch.int32, torch.uint8
@@ -151,7 +152,7 @@ def segment_instance(pc, outputs, idx, center, corner, res, dims, num_rots=72, t
 
 
 def zero_shot_poses(encoder9, pc, nrm, feat, idx, cfg, angle_tol=2, max_rot_pairs=10000, rot_order=None, preds=None, num_rots=72,
-                    sigma=1.0, thresh=50, margin=10, max_proposals=32, max_iters=None, min_contrib=12):
+                    sigma=1.0, thresh=50, margin=10, max_proposals=32, max_iters=None, min_contrib=12, verify=False):
     """Cells 7-11 on a scene: the 9-wide regression head (out_dim = 2+2+2+3: mu nu | up right | aux up, aux right | log-scales)
     on every pair, the scene vote, the proposals, then per proposal the back-vote, the segmentation, the orientation vote on
     column 2 of the kept pairs (the first `max_rot_pairs`, or the positions `rot_order` in their list), the axis sign from column
@@ -159,13 +160,13 @@ def zero_shot_poses(encoder9, pc, nrm, feat, idx, cfg, angle_tol=2, max_rot_pair
     pc, nrm f32[N,3], feat f32[N,F], idx [P,2] device tensors; preds: precomputed [P,9] head outputs (then encoder9 is unused).
     Returns one dict per proposal: T (the proposal, f64[3]), R f64[3,3], up, scale_3d f64[3], scale (its norm), RT f64[4,4],
     cnt (smoothed peak), diff, point_mask bool[N] (numpy), n_pairs (kept pairs).  zero_shot_scene also returns the grid and
-    the proposals."""
+    the proposals.  verify=True: every dict gains verify, scene_stage.verify_proposals' dict (the box: T, R, scale_3d / 2 + res)."""
     return zero_shot_scene(encoder9, pc, nrm, feat, idx, cfg, angle_tol, max_rot_pairs, rot_order, preds, num_rots, sigma, thresh,
-                           margin, max_proposals, max_iters, min_contrib)["poses"]
+                           margin, max_proposals, max_iters, min_contrib, verify)["poses"]
 
 
 def zero_shot_scene(encoder9, pc, nrm, feat, idx, cfg, angle_tol=2, max_rot_pairs=10000, rot_order=None, preds=None, num_rots=72,
-                    sigma=1.0, thresh=50, margin=10, max_proposals=32, max_iters=None, min_contrib=12):
+                    sigma=1.0, thresh=50, margin=10, max_proposals=32, max_iters=None, min_contrib=12, verify=False):
     """zero_shot_poses with the intermediate results: dict(poses, preds [P,9] device, grid (raw vote, device), corner f32[3],
     dims, proposals (loc i32[K,3], value, diff numpy))"""
     require_cuda()
@@ -196,7 +197,7 @@ def zero_shot_scene(encoder9, pc, nrm, feat, idx, cfg, angle_tol=2, max_rot_pair
     recs = torch.zeros((n, 10), dtype=torch.float64, device=dev)        # best_dir[3] | sign sums[3] | exp-scale sums[4]
     counts = torch.zeros((n, S), dtype=I32, device=dev)
     best_idx = torch.empty(n, dtype=torch.int64, device=dev)
-    masks, pairs, offsets, counts_d, _ = segment_proposals(pc, outputs, idx32, corner, cfg.res, dims, worlds, num_rots, None, min_contrib)
+    masks, pairs, offsets, counts_d, bits = segment_proposals(pc, outputs, idx32, corner, cfg.res, dims, worlds, num_rots, None, min_contrib)
     rot = preds.data_ptr() + 4 * 2
     for k in range(n):
         sel = pairs[int(offsets[k]):int(offsets[k + 1])] if offsets[k + 1] > offsets[k] else pairs[:1]    # (empty: any valid address)
@@ -212,6 +213,9 @@ def zero_shot_scene(encoder9, pc, nrm, feat, idx, cfg, angle_tol=2, max_rot_pair
         call("cppf_scale_exp_sum", dev, preds.data_ptr() + 4 * 6, 9, sel, cnt, P, rec[6:10], scratch(rws))
     recs_h, masks_h = recs.cpu().numpy(), masks.cpu().numpy().astype(bool)
     poses = [_assemble(recs_h[k], worlds[k], cfg, val[k], diff[k], masks_h[k]) for k in range(n)]
+    if verify:
+        for p, v in zip(poses, verify_proposals(pc, idx32, bits, masks, poses, cfg)):
+            p["verify"] = v
     return dict(poses=poses, preds=preds, grid=grid, corner=corners[0], dims=dims, proposals=(loc, val, diff))
 
 

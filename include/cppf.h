@@ -1156,6 +1156,42 @@ int cppf_box_nms_batch(const double* RT, const double* scales, const double* sco
                        int n_groups, double thresh, int32_t* pick, int32_t* n_pick, double* iou_out, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Proposal verification (csrc/verify.hip; additive, ABI version unchanged): per-proposal evidence for up to 32 proposals of a
+ * mask-free scene, from what cppf_backvote_multi and cppf_segment_instances have written.  The reference filters nothing, so the
+ * definitions are this project's; tests/verify_ref.py restates them in numpy.  Host side: scene_stage.verify_proposals.
+ * Both calls clear `counts`, count with integer atomics (the same words on every run), read nothing back, allocate nothing and can
+ * be captured in a graph.
+ *
+ * cppf_proposal_support: one pass over the pair list.  point_idxs device i32[n_pairs,2]; surv_bits device u32[n_pairs] as
+ *   cppf_backvote_multi writes them; point_masks device u8[n_props,n_points] as cppf_segment_instances writes them (non-zero =
+ *   member).  counts device i32[n_props,4], for proposal k:
+ *     within       pairs whose two endpoints are both members of mask k
+ *     agree        those of `within` with bit k of surv_bits set
+ *     cross        pairs with exactly one endpoint in mask k
+ *     cross_agree  those of `cross` with bit k set
+ *   An endpoint outside [0, n_points) is a non-member (the pair still counts through its other endpoint); a pair (i, i) with i in
+ *   the mask is `within`, once; bits >= n_props of surv_bits are ignored.  n_pairs == 0 writes zeros and launches nothing more.
+ *   The workspace holds one membership word per point (cppf_proposal_support_workspace_bytes).
+ *   CPPF_EINVAL: n_props outside 1..32, n_points outside 1..2^31-1, n_pairs < 0 or >= 2^27, a null pointer (point_idxs and
+ *   surv_bits may be null when n_pairs == 0), a workspace below cppf_proposal_support_workspace_bytes(n_points).
+ *
+ * cppf_box_support: one pass over the cloud.  points device f32[n_points,3]; centers f32[n_props,3]; axes f32[n_props,9]: the
+ *   row-major 3x3 whose COLUMNS are the box axes (R of a pose); half f32[n_props,3]: half extents, padding included.  counts device
+ *   i32[n_props,3], for proposal k:
+ *     mask_pts     members of mask k
+ *     mask_in_box  members that lie inside box k
+ *     box_pts      all points inside box k
+ *   Inside, in fp32, for a = 0, 1, 2: |d.x A[0][a] + d.y A[1][a] + d.z A[2][a]| <= half[a] with d = p - c, the products summed left
+ *   to right without contraction.  A point with a non-finite coordinate is inside no box; a box with a NaN entry or a negative half
+ *   extent holds no point.  CPPF_EINVAL: n_props outside 1..32, n_points outside 1..2^31-1, a null pointer.
+ * ------------------------------------------------------------------------------------------- */
+size_t cppf_proposal_support_workspace_bytes(int64_t n_points);
+int cppf_proposal_support(const int32_t* point_idxs, const uint32_t* surv_bits, const uint8_t* point_masks, int64_t n_pairs,
+                          int64_t n_points, int n_props, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+int cppf_box_support(const float* points, const uint8_t* point_masks, const float* centers, const float* axes, const float* half,
+                     int64_t n_points, int n_props, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,6 +25,16 @@ suppression.  The record (profiles/scene_detections_eval.json) holds the APs wit
 the same frames and seeds, and the proposals kept / suppressed per category.  Again a first figure, no threshold.
 
     python scripts/eval_mesh_frames.py --procedural --train-steps 3000 --train-pairs 200000 --frames 20 --objects 4 --mask-free --nms 0.3 --cross-category
+
+--mask-free --score agreement [--min-agreement A] [--min-fill F] [--tune-frames N] [--cross-category]: proposal verification (DESIGN.md
+3.7g).  The frames go through scene_frame(verify=True) once; the same proposals are then pooled three ways (NMS per category at --nms,
+default 0.3): ranked by `diff` (today's baseline), ranked by `agreement`, and ranked by `agreement` behind the min_agreement / min_fill
+filters.  Without --min-agreement the bound is CHOSEN on --tune-frames frames of a separate sampler (seed + 1000, pair seeds apart
+from the reported frames'): the candidate with the best mean IoU25 AP there.  The record (profiles/scene_verify_eval.json) also holds,
+for the un-suppressed proposals of the reported frames, how each of agreement / leak / fill / purity / diff correlates with the proposal
+being a true positive (IoU >= 0.25 with a ground truth of its class).  Figures, no threshold.
+
+    python scripts/eval_mesh_frames.py --procedural --train-steps 3000 --train-pairs 200000 --frames 20 --objects 4 --mask-free --score agreement --tune-frames 20
 """
 import argparse
 import json
@@ -166,6 +176,128 @@ def _detections(args, sampler, encs, pencs, dev):
     return results, ms, counts, n_prop, n_gt
 
 
+def _verified_frames(args, sampler, encs, pencs, n_frames, seed0):
+    """n_frames frames of `sampler` through scene_frame(verify=True) per category (pair seed seed0 + i) -> ([(frame, [dict(poses)])],
+    ms per frame).  Only the pose lists are kept: pool_detections reads nothing else."""
+    from cppf_amd.scene_poses import frame_cloud, scene_frame
+    frames, ms = [], []
+    for i in range(n_frames):
+        fr = sampler.sample()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        outs, clouds = [], {}
+        for c in sampler.categories:
+            cfg = CATEGORIES[c]
+            key = (float(cfg.res), int(cfg.knn))
+            if key not in clouds:
+                clouds[key] = frame_cloud(fr.depth_mm, fr.intrinsics, cfg)
+            out = scene_frame(fr.depth_mm, fr.intrinsics, encs[c], pencs[c], cfg, n_pairs=args.scene_pairs, seed=seed0 + i, cloud=clouds[key],
+                              thresh=args.thresh, max_proposals=args.max_proposals, verify=True)
+            outs.append(dict(poses=out["poses"]))
+        ms.append((time.perf_counter() - t0) * 1e3)
+        frames.append((fr, outs))
+    return frames, ms
+
+
+def _pooled_ap(frames, sampler, cats, dev, **pool_kw):
+    """the frames' proposals pooled with pool_kw -> (iou_aps, pose_aps, detections evaluated, kept per category, filtered per category)"""
+    from cppf_amd.detections import pool_detections
+    names = sampler.synset_names
+    recs, n_det = [], 0
+    kept, filtered = {c: 0 for c in cats}, {c: 0 for c in cats}
+    for fr, outs in frames:
+        res = pool_detections(outs, cats, None, device=dev, **pool_kw)
+        dets = res["detections"][:20]                                   # (the evaluation's match tables hold 20 predictions per image)
+        recs.append(_mask_free_record(fr, [(names.index(d["class_name"]), d["pose"], d["score"]) for d in dets]))
+        n_det += len(dets)
+        for c in cats:
+            kept[c] += res["kept_per_category"][c]
+            filtered[c] += res.get("filtered", {}).get(c, 0)
+    deg, sh = [5, 10, 15], [5, 10, 15]
+    iou = [float(t) for t in np.round(np.linspace(0, 1, 101), 2)]
+    iou_aps, pose_aps, _, _ = E.compute_degree_cm_mAP(recs, names, None, deg, sh, iou, 0.1, True, device=dev)
+    return iou_aps, pose_aps, n_det, kept, filtered
+
+
+def _true_positive_table(frames, sampler, cats):
+    """every finite proposal of the frames (no NMS, no filter) with its verify ratios, its diff and whether it is a true positive: IoU
+    >= 0.25 (compute_3d_iou, the up-symmetry sweep included) with a ground truth of its class.  -> dict(n, true_positives, per
+    quantity: Pearson r with the true-positive flag, mean over the true and over the false positives)"""
+    from cppf_amd.detections import pool_detections
+    names = sampler.synset_names
+    rows = []
+    for fr, outs in frames:
+        gt = fr.record([None] * len(fr.visible(1)), min_pixels=1)
+        for d in pool_detections(outs, cats, None, nms_thresh=None)["detections"]:
+            cid = names.index(d["class_name"])
+            best = 0.0
+            for j in np.nonzero(gt["gt_class_ids"] == cid)[0]:
+                best = max(best, E.compute_3d_iou(d["RT"], gt["gt_RTs"][j], d["scales"], gt["gt_scales"][j], bool(gt["gt_up_syms"][j]),
+                                                  d["class_name"], d["class_name"]))
+            v = d["pose"]["verify"]
+            rows.append([float(best >= 0.25), v["agreement"], v["leak"], v["fill"], v["purity"], float(d["pose"]["diff"])])
+    t = np.array(rows, np.float64).reshape(-1, 6)
+    out = dict(n=int(t.shape[0]), true_positives=int(t[:, 0].sum()) if t.size else 0, quantities={})
+    for k, q in enumerate(("agreement", "leak", "fill", "purity", "diff"), 1):
+        tp, fp = t[t[:, 0] == 1, k], t[t[:, 0] == 0, k]
+        r = float(np.corrcoef(t[:, 0], t[:, k])[0, 1]) if tp.size and fp.size and t[:, k].std() > 0 else None
+        out["quantities"][q] = dict(pearson_r_with_true_positive=r, mean_true_positive=float(tp.mean()) if tp.size else None,
+                                    mean_false_positive=float(fp.mean()) if fp.size else None)
+    return out
+
+
+def _verify_eval(args, cat_paths, sampler, encs, pencs, trained, weights, dev):
+    """--mask-free --score agreement / --min-agreement / --min-fill: see the module docstring"""
+    cats = list(sampler.categories)
+    names = sampler.synset_names
+    deg, sh = [5, 10, 15], [5, 10, 15]
+    mean25 = lambda iou_aps: float(iou_aps[[names.index(c) for c in cats]].mean(0)[25])
+    tuning = None
+    min_agreement = args.min_agreement
+    if min_agreement is None and args.tune_frames > 0:
+        tune_sampler = MF.MeshFrameSampler(cat_paths, args.objects, device=dev, seed=args.seed + 1000)
+        tune, _ = _verified_frames(args, tune_sampler, encs, pencs, args.tune_frames, seed0=1_000_000)
+        table = []
+        for a in [round(0.05 * k, 2) for k in range(0, 20)]:
+            iou_aps, _, n_det, _, _ = _pooled_ap(tune, tune_sampler, cats, dev, nms_thresh=args.nms, score="agreement", min_agreement=a,
+                                                 min_fill=args.min_fill)
+            table.append(dict(min_agreement=a, mean_iou25_ap=mean25(iou_aps), detections=n_det))
+        best = max(table, key=lambda r: (r["mean_iou25_ap"], -r["min_agreement"]))
+        min_agreement = best["min_agreement"]
+        tuning = dict(frames=args.tune_frames, sampler_seed=args.seed + 1000, pair_seeds="1000000 + frame", candidates=table, chosen=min_agreement,
+                      rule="the candidate with the best mean IoU25 AP on the tuning frames, the lowest bound on a tie")
+        print(f"min_agreement chosen on {args.tune_frames} separate frames: {min_agreement}")
+    frames, ms = _verified_frames(args, sampler, encs, pencs, args.frames, seed0=0)
+    n_gt = sum(len(fr.categories) for fr, _ in frames)
+    variants = [("score_diff", dict(score="diff")), ("score_agreement", dict(score="agreement")),
+                ("score_agreement_filtered", dict(score="agreement", min_agreement=min_agreement, min_fill=args.min_fill))]
+    variants = [(n, dict(kw, nms_thresh=args.nms)) for n, kw in variants]
+    if args.cross_category:
+        variants += [(n + "_cross_category", dict(kw, cross_category=True)) for n, kw in list(variants)]
+    variants.insert(0, ("score_diff_no_nms", dict(score="diff", nms_thresh=None)))      # (profiles/scene_poses_eval.json's figure, re-run)
+    rec = dict(device=torch.cuda.get_device_name(0), mode="mask-free: scene_frame(verify=True) per category on the whole depth image; the same "
+               "proposals pooled by detections.pool_detections with NMS per category, ranked by diff, by agreement, and by agreement behind "
+               "the filters", frames=args.frames, objects_per_frame=args.objects, scene_pairs=args.scene_pairs, thresh=args.thresh,
+               max_proposals=args.max_proposals, nms_thresh=args.nms, seed=args.seed, categories={c: len(p) for c, p in cat_paths.items()},
+               procedural=bool(args.procedural), trained=trained, weights=weights, ground_truths=n_gt,
+               ms_per_frame_median_with_verify=float(np.median(ms[min(1, len(ms) - 1):])), min_agreement=min_agreement, min_fill=args.min_fill,
+               tuning=tuning, variants={}, note="figures: no threshold is attached to these APs")
+    for name, kw in variants:
+        iou_aps, pose_aps, n_det, kept, filtered = _pooled_ap(frames, sampler, cats, dev, **kw)
+        one = dict(pool=kw, evaluated_predictions=n_det, detections_kept=int(sum(kept.values())),
+                   detections_kept_per_ground_truth=round(sum(kept.values()) / max(n_gt, 1), 3), kept_per_category=kept,
+                   filtered_per_category=filtered, iou_ap={}, pose_ap={})
+        print(f"--- {name}: kept {sum(kept.values())} for {n_gt} ground truths, filtered {sum(filtered.values())}")
+        _tables(iou_aps, pose_aps, names, cats, deg, sh, one)
+        rec["variants"][name] = one
+    rec["true_positive_correlation"] = _true_positive_table(frames, sampler, cats)
+    print("true positives among the un-suppressed proposals:", json.dumps(rec["true_positive_correlation"]))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        json.dump(rec, fh, indent=1)
+        fh.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--meshes", action="append", help="CATEGORY=directory of OBJ files or names file (repeatable)")
@@ -188,11 +320,24 @@ def main():
                     "with 3D box NMS per category at IoU threshold T (the reference's 0.3); AP with and without it from the same frames")
     ap.add_argument("--cross-category", action="store_true", help="--mask-free --nms: also a second NMS pass over the survivors of "
                     "all categories (scores of different networks are not calibrated against each other)")
+    ap.add_argument("--score", choices=("diff", "agreement"), default="diff", help="--mask-free: 'agreement' evaluates proposal "
+                    "verification (scene_frame(verify=True)): the same proposals ranked by diff, by agreement and by agreement behind the filters")
+    ap.add_argument("--min-agreement", type=float, default=None, help="--mask-free --score agreement: the filter's bound (default: chosen "
+                    "on --tune-frames separate frames)")
+    ap.add_argument("--min-fill", type=float, default=None, help="--mask-free --score agreement: drop proposals whose mask fills less of "
+                    "their box")
+    ap.add_argument("--tune-frames", type=int, default=0, help="--score agreement without --min-agreement: frames of a separate sampler "
+                    "(seed + 1000) on which the bound is chosen")
     ap.add_argument("--out", default=None, help="default profiles/mesh_frames_eval.json (profiles/scene_poses_eval.json with --mask-free, "
-                    "profiles/scene_detections_eval.json with --nms)")
+                    "profiles/scene_detections_eval.json with --nms, profiles/scene_verify_eval.json with --score agreement)")
     args = ap.parse_args()
-    if args.cross_category and args.nms is None:
+    verify_mode = args.score == "agreement" or args.min_agreement is not None or args.min_fill is not None
+    if (args.cross_category or verify_mode) and args.nms is None:
         args.nms = 0.3
+    if verify_mode and not args.mask_free:
+        sys.exit("--score agreement / --min-agreement / --min-fill belong to --mask-free")
+    if verify_mode and args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "scene_verify_eval.json")
     if args.nms is not None and not args.mask_free:
         sys.exit("--nms / --cross-category belong to --mask-free")
     if args.out is None:
@@ -224,6 +369,10 @@ def main():
         else:
             sys.exit(f"category {c}: --weights {c}=FILE or --train-steps N")
     sampler = MF.MeshFrameSampler(cat_paths, args.objects, device=dev, seed=args.seed)
+    if verify_mode:
+        _verify_eval(args, cat_paths, sampler, encs, pencs, trained, weights, dev)
+        tmp.cleanup()
+        return
     if args.mask_free and args.nms is not None:
         results, ms, counts, n_prop, n_gt = _detections(args, sampler, encs, pencs, dev)
         deg, sh = [5, 10, 15], [5, 10, 15]
