@@ -11,7 +11,7 @@ the grid is the cloud's bounding box over `res` (:194-195).  The runner therefor
 grid class, lane); an instance's real {N, gx, gy, gz} travels in a 16-byte device record next to its cloud.  The cache
 is bounded (least recently used pipelines are released with their buffers and scratch).  Grids beyond the tiled vote
 (> 64 LDS tiles) run on exact-shape pipelines, which share the same bounded cache."""
-from collections import OrderedDict
+from collections import OrderedDict, deque
 
 import numpy as np
 import torch
@@ -28,6 +28,21 @@ def _shape_error(obj, pipe):
 
 
 class BatchPoseRunner:
+    """Runs batches of object instances on cached, captured pipelines (module docstring; the constructor documents the knobs).
+
+    REFUSED INSTANCES.  A staged batch -- objects returned by put(), or host arrays whose pairs are drawn on the device
+    (staged_host) -- returns its records on the device without a read-back, so the runner cannot know at return time that the
+    shape-polymorphic vote refused an instance: the grid the DEVICE laid over its cloud needs more vote tiles than the class of the
+    pipeline the HOST's dims chose (dims handed to put() that understate the cloud; host and device arithmetic one cell apart at a
+    class boundary).  The mark of a refused instance is `record[:, 12] < 0`: its row carries NaN in columns 0..11 (T, up, right,
+    scale), -1 in column 12 (arg-max), NaN in column 13 (peak), and its object id in column 15 as always; the other rows of the batch
+    are unaffected.  The runner reports it too, late: every staged batch leaves a pinned snapshot of its records in a FIFO, and
+      check()  waits for all of them and raises CppfError with `.batch` (the sequence number of the run() that produced the refusal,
+               counted from 0 per runner) and `.object_ids` (indices within that batch), one batch per call, oldest first;
+      run()    looks at what has landed without blocking and raises the same error, naming the OLD batch, before it enqueues
+               anything of the new one -- calling run() again with the new batch then works.
+    A refusal is reported once, no batch's check is dropped because the next batch came first, and the runner stays usable."""
+
     def __init__(self, encoders, device, num_rots=72, adaptive=True, angle_tol=1.5, max_rot_pairs=10000,
                  use_graph=True, point_encoders=None, n_bucket=1024, max_pipelines=192, dynamic=True, n_lanes=3,
                  max_scratch_bytes=64 << 30, vote_workgroups=None, chain_len=None, max_chains=24, staged_host=True,
@@ -86,6 +101,9 @@ class BatchPoseRunner:
         self.staged_host, self.overlap_batches, self.idx_i32 = bool(staged_host), bool(overlap_batches), bool(idx_i32)
         self._stage_pos = 0
         self._streams = None
+        # the staged batches' late checks: a FIFO with one entry per batch -- its own pinned record snapshot and event, from a small
+        # ring grown on demand -- and the refusals found but not yet raised (_collect, check())
+        self._checks, self._snap_free, self._reports, self._batch_no = deque(), [], [], 0
 
     # ------------------------------------------------------------------ pipeline cache
     def _pipe(self, cfg, n_points, n_pairs, dims, lane=0, slot=0, idx_i32=False):
@@ -309,10 +327,10 @@ class BatchPoseRunner:
     def _run_resident(self, objects, mine, rank, world, seed, host_dims=None):
         """run() for objects put() on the device -- and for host objects whose pairs are drawn on the device, which are uploaded on
         the way (_upload_batch): per chain one 48-byte-per-member descriptor copy, one graph replay, one device copy
-        of the finished records; nothing is read back (the survivor counts that choose a chain's form for the NEXT batch are copied
-        to pinned memory asynchronously and looked at when the next batch starts)."""
+        of the finished records; nothing is read back (the records -- survivor counts that choose a chain's form for a LATER batch, the
+        arg-max that marks a refused instance -- are copied to a pinned snapshot of the batch's own asynchronously and looked at by a
+        later run() or by check(): _collect)."""
         dev, n, n_total = self.device, len(mine), len(objects)
-        self._adapt_resident()
         # two record buffers alternate: with overlap_batches a lane may write batch k + 1's rows while the caller's stream still reads
         # batch k's (its clone / gather); a buffer is rewritten only after the read of two batches ago has been enqueued AND waited for
         lb = self.__dict__.get("_locals")
@@ -379,12 +397,10 @@ class BatchPoseRunner:
             blk["free"].record(main)        # (joined: every chain that read the device block has finished before this point of `main`)
         if self.__dict__.get("own_done") is not None:      # a caller's timing event: this rank's chains, before the gather (bench.py)
             self.own_done.record(main)
-        snap = self.__dict__.get("_snap")
-        if snap is None or snap[0].shape[0] < n:
-            snap = self._snap = (torch.zeros((max(n, 1), sharding.RECORD), dtype=torch.float64).pin_memory(), torch.cuda.Event())
-        copy_words(snap[0][:n], local[:n], dev)             # (into pinned memory by a kernel: no copy engine in a batch's steady state)
-        snap[1].record(main)
-        self._pending = ran
+        snap, ev = self._snapshot(n)                        # this batch's own: a later batch never takes its check away (_collect)
+        copy_words(snap[:n], local[:n], dev)                # (into pinned memory by a kernel: no copy engine in a batch's steady state)
+        ev.record(main)
+        self._checks.append(dict(batch=self._batch_no - 1, ran=ran, mine=list(mine), snap=snap, ev=ev))
         if world == 1 and not (sharding.forced() and sharding.dist.is_initialized()):
             out = local[:n_total].clone()                  # (a later batch overwrites `local`: hand the caller its own copy)
         else:
@@ -407,20 +423,51 @@ class BatchPoseRunner:
             out[j] = dims
         return out
 
-    def _adapt_resident(self):
-        """the split / full-first form of the chains of the last resident batch, from its survivor counts (PoseChain.adapt), once
-        their asynchronous copy has landed"""
-        ran = self.__dict__.get("_pending")
-        if not ran or not self._snap[1].query():
-            return
-        host = self._snap[0].numpy()
-        if np.any(host[[s for _, slots in ran for s in slots], 12] < 0):
-            self._pending = None
-            from ._lib import CppfError
-            raise CppfError("an instance of the last batch did not fit the shape-polymorphic pipeline it ran on (arg-max index -1)")
-        for chain, slots in ran:
-            chain.adapt([host[s, 14] for s in slots])
-        self._pending = None
+    def _snapshot(self, n):
+        """a pinned record snapshot of at least n rows with its event, from the ring (grown on demand: one per batch in flight)"""
+        for k, (buf, ev) in enumerate(self._snap_free):
+            if buf.shape[0] >= n:
+                return self._snap_free.pop(k)
+        return torch.zeros((max(n, 1), sharding.RECORD), dtype=torch.float64).pin_memory(), torch.cuda.Event()
+
+    def _collect(self, wait):
+        """Look at the staged batches whose record snapshots have landed, oldest first (wait: at all of them, blocking): the split /
+        full-first form of their chains from the survivor counts (PoseChain.adapt), and a report -- queued in `_reports`, raised by
+        _raise_report -- for every batch with a refused instance.  A batch's check leaves the FIFO only here."""
+        while self._checks:
+            c = self._checks[0]
+            if wait:
+                c["ev"].synchronize()
+            elif not c["ev"].query():
+                break
+            self._checks.popleft()
+            host = c["snap"].numpy()
+            refused = [int(c["mine"][s]) for _, slots in c["ran"] for s in slots if host[s, 12] < 0]
+            for chain, slots in c["ran"]:
+                if all(host[s, 12] >= 0 for s in slots):           # (a refused member's survivor count is no pose's)
+                    chain.adapt([host[s, 14] for s in slots])
+            if refused:
+                from ._lib import CppfError
+                err = CppfError(f"batch {c['batch']}: object(s) {refused} did not fit the shape-polymorphic pipeline they ran on (arg-max "
+                                "index -1: the grid the device laid over the cloud needs more vote tiles than the pipeline's class holds); "
+                                "their records carry NaN in columns 0..11 and -1 in column 12")
+                err.batch, err.object_ids = c["batch"], refused
+                self._reports.append(err)
+            c["ran"] = None
+            self._snap_free.append((c["snap"], c["ev"]))
+
+    def _raise_report(self):
+        if self._reports:
+            raise self._reports.pop(0)
+
+    def check(self):
+        """Wait for the record snapshot of every staged batch run so far and settle them: the chains' forms adapted from the survivor
+        counts, and CppfError -- with `.batch`, the sequence number of the run() that produced it (counted from 0 per runner), and
+        `.object_ids`, the refused objects' indices within that batch -- if an instance was refused (class docstring).  One batch per
+        error, oldest first: what is raised is cleared, a further call reports the next.  With nothing outstanding it returns at once;
+        the runner stays usable after the error."""
+        self._collect(wait=True)
+        self._raise_report()
 
     def run_object(self, obj):
         """obj: dict(pc, normals, feat, point_idxs, u_tr, u_rot, cfg) of host arrays -> pose dict."""
@@ -439,7 +486,14 @@ class BatchPoseRunner:
         The rank's instances are enqueued back to back -- inputs, graph replay, a 21-double device copy of the result --
         and all results are read back once at the end (one synchronisation per batch instead of one per instance).  An
         object without `point_idxs` gets its pairs (n_pairs = obj["n_pairs"]) and bin uniforms drawn on the device from
-        `seed` and its index: then only the cloud itself crosses PCIe."""
+        `seed` and its index: then only the cloud itself crosses PCIe.
+
+        Staged batches (class docstring) are checked late: whatever has landed of EARLIER batches is looked at here, without
+        blocking, and a refused instance among them raises CppfError naming the old batch (`.batch`, `.object_ids`) before anything
+        of this one is enqueued -- call run() again with this batch; check() settles everything at once."""
+        self._collect(wait=False)
+        self._raise_report()
+        self._batch_no += 1                     # (this batch's sequence number is _batch_no - 1)
         mine = sharding.shard_objects(len(objects), rank, world)
         resident = [torch.is_tensor(objects[j]["pc"]) and objects[j]["pc"].is_cuda for j in mine]
         if any(resident):

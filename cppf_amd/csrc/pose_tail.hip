@@ -1018,6 +1018,10 @@ __device__ __forceinline__ void assemble_record(const PoseSumsArgs& A, const dou
     }
     out[12] = A.rec[19]; out[13] = A.rec[20]; out[14] = n_surv;
     out[15] = (double)(A.object_id_dev ? *A.object_id_dev : A.object_id_host);
+    // an instance the shape-polymorphic vote refused (arg-max -1, peak NaN: its grid did not fit the pipeline's tile class) has no
+    // pose: the tail ran on from index -1, and what it made of that must not pass for one
+    if (A.rec[19] < 0.0)
+        for (int c = 0; c < 12; ++c) out[c] = __longlong_as_double(0x7ff8000000000000ll);
 }
 __device__ __forceinline__ void pose_sums_body(const PoseSumsArgs& A)
 {

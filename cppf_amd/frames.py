@@ -319,7 +319,9 @@ class FrameRunner:
         hs["raw"][:n].copy_(raw, non_blocking=True)                     # the frame's one read-back (two small arrays), asynchronous
         hs["shapes"][:n].copy_(shapes, non_blocking=True)
         hs["done"].record(main)
-        pend = PendingFrame(self, hs, depth, instances, seed, on_chain, ran, (raw, shapes))
+        # (the frame keeps the depth's TYPE, not the caller's array: a video loop refills one buffer while this frame is pending, and
+        # the eager fallback of result() reads the frame's own pinned copy, hs["depth"], which is the set's until result() returns)
+        pend = PendingFrame(self, hs, depth.dtype, instances, seed, on_chain, ran, (raw, shapes))
         hs["owner"] = pend
         return pend
 
@@ -354,7 +356,8 @@ class FrameRunner:
                 pose.update(n_points=n, dims=tuple(int(v) for v in shp[i, 1:4]))
                 out[i] = pose
         if eager:
-            sub = frame_poses(pend._depth, [instances[i] for i in eager], self.encoders, self.point_encoders, self.intrinsics, self.n_pairs,
+            depth = hs["depth"].numpy().view(pend._depth_dtype)          # this frame's depth as submit() saw it
+            sub = frame_poses(depth, [instances[i] for i in eager], self.encoders, self.point_encoders, self.intrinsics, self.n_pairs,
                               pend._seed, self.device, self.angle_tol, self.num_rots, self.cfgs, index_of=eager)
             for i, p in zip(eager, sub):
                 out[i] = p
@@ -364,8 +367,8 @@ class FrameRunner:
 class PendingFrame:
     """a frame FrameRunner.submit() enqueued; result() -> its poses (waits for the frame's read-back; idempotent)"""
 
-    def __init__(self, runner, hs, depth, instances, seed, on_chain, ran, keep):
-        self._runner, self._hs, self._depth, self._instances, self._seed = runner, hs, depth, instances, seed
+    def __init__(self, runner, hs, depth_dtype, instances, seed, on_chain, ran, keep):
+        self._runner, self._hs, self._depth_dtype, self._instances, self._seed = runner, hs, depth_dtype, instances, seed
         self._on_chain, self._ran, self._keep, self._out = on_chain, ran, keep, None
 
     def result(self):

@@ -21,6 +21,7 @@ surviving pairs only, like the reference's, through cppf_pair_mlp_decode_sel), a
 i.i.d. uniform, so a prefix is distributed exactly like a shuffled subset).
 """
 import ctypes as C
+import gc
 import os
 
 import numpy as np
@@ -223,9 +224,20 @@ class _GraphCache:
                         chain_fn()
                     cur.wait_stream(s)
                     graph = torch.cuda.CUDAGraph()
-                    # thread_local: other threads (the RCCL watchdog of a multi-rank run) may touch the runtime meanwhile
-                    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                        tensors = chain_fn()
+                    # No cycle collection inside the capture: chain_fn allocates enough Python objects to trigger one, and a dead
+                    # pipeline or chain that sits in a reference cycle (a runner kept alive by an exception's traceback, say) would
+                    # have its __del__ run right here -- release() drops ITS captured graphs, and destroying a graph while this
+                    # thread captures aborts the process.  (torch.cuda.graph no longer collects on entry.)  Such garbage goes at
+                    # the first collection after the capture instead.
+                    gc_was_on = gc.isenabled()
+                    gc.disable()
+                    try:
+                        # thread_local: other threads (the RCCL watchdog of a multi-rank run) may touch the runtime meanwhile
+                        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                            tensors = chain_fn()
+                    finally:
+                        if gc_was_on:
+                            gc.enable()
                     entry = self.entries[form] = (graph, key, tensors)
             for p in members:
                 p._await_images()

@@ -22,6 +22,41 @@ def forced():
     return os.environ.get("CPPF_FORCE_DIST", "0") not in ("", "0")
 
 
+_LOCAL_SIZE_VARS = ("LOCAL_WORLD_SIZE", "OMPI_COMM_WORLD_LOCAL_SIZE", "SLURM_NTASKS_PER_NODE")
+
+
+def placement(env, n_dev):
+    """Where a rank runs and how the ranks meet: a pure function of the environment mapping and the number of GPUs this node
+    shows -> (local device index, shared, default backend).  The ranks on this node are the first that is set of LOCAL_WORLD_SIZE
+    (torchrun), OMPI_COMM_WORLD_LOCAL_SIZE (Open MPI's mpirun) and SLURM_NTASKS_PER_NODE (srun); without any of them the job is taken
+    to be ONE node (WORLD_SIZE).  Every one of these is a value all ranks of a node agree on, so that all of them pick the same
+    backend (a per-rank guess made rank 0 choose nccl and rank 1 gloo).  shared: the node has fewer GPUs than local ranks -- the
+    device index is LOCAL_RANK mod the GPUs present and the default backend is gloo (RCCL needs a GPU per rank).  When only the
+    WORLD_SIZE guess makes `shared` true -- a multi-node launch that named no ranks per node looks exactly like that -- one warning
+    says which variable is missing and what the job falls back to."""
+    world = int(env.get("WORLD_SIZE", "1") or 1)
+    local = int(env.get("LOCAL_RANK", "0") or 0)
+    n_dev = int(n_dev)
+    local_world = 0
+    for name in _LOCAL_SIZE_VARS:
+        local_world = int(str(env.get(name, "0") or 0).split("(")[0] or 0)      # (SLURM writes "8(x2)" for repeated node counts)
+        if local_world > 0:
+            break
+    guessed = local_world <= 0
+    if guessed:
+        local_world = world
+    shared = 0 < n_dev < local_world
+    if shared:
+        local = local % n_dev
+        if guessed:
+            import warnings
+            warnings.warn(f"{world} ranks and {n_dev} GPUs on this node, and LOCAL_WORLD_SIZE is not set (nor "
+                          f"{' / '.join(_LOCAL_SIZE_VARS[1:])}): taking all ranks to be on this node, so they share its GPUs and the "
+                          "job falls back to gloo with host staging.  Set LOCAL_WORLD_SIZE to the ranks per node for RCCL.",
+                          RuntimeWarning, stacklevel=3)
+    return local, shared, ("nccl" if n_dev > 0 and not shared else "gloo")
+
+
 def init_distributed(backend=None, force=None):
     """Reads RANK / WORLD_SIZE / LOCAL_RANK / LOCAL_WORLD_SIZE / MASTER_* from the environment (torchrun contract).  The group is
     created when WORLD_SIZE > 1, or when `force` (default: CPPF_FORCE_DIST) asks for it with a single rank.  Returns (rank, world,
@@ -29,19 +64,13 @@ def init_distributed(backend=None, force=None):
     share devices and rendezvous over gloo (RCCL needs a GPU per rank), so that a one-GPU box runs the whole multi-rank path."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    # ranks on this node: LOCAL_WORLD_SIZE (torchrun sets it); without it the job is taken to be ONE node (WORLD_SIZE) -- a value every
-    # rank agrees on, so that all of them pick the same backend (a per-rank guess made rank 0 choose nccl and rank 1 gloo)
-    local_world = int(os.environ.get("LOCAL_WORLD_SIZE", "0") or 0) or world
     n_dev = torch.cuda.device_count() if torch.cuda.is_available() else 0
-    shared = 0 < n_dev < local_world
-    if shared:
-        local = local % n_dev
+    local, shared, default_backend = placement(os.environ, n_dev)
     if force is None:
         force = forced()
     if (world > 1 or force) and not dist.is_initialized():
         if backend is None:   # RCCL on GPUs; CPPF_DIST_BACKEND=gloo lets two ranks share one GPU when debugging on a small box
-            backend = os.environ.get("CPPF_DIST_BACKEND") or ("nccl" if n_dev > 0 and not shared else "gloo")
+            backend = os.environ.get("CPPF_DIST_BACKEND") or default_backend
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29500")
         if backend == "nccl":

@@ -192,7 +192,9 @@ typedef struct CppfPoseTailItem {
      *   record_out  device f64[16]: T[3] | up[3] | right[3] | scale[3] | arg-max index | peak | survivors | object id
      *   object id = *object_id_dev (device i64, e.g. &CppfStageDesc.object_id) when that is not NULL, else object_id_host
      * A degenerate right axis (|right| < 1e-7, :325-328: the reference draws a random vector) takes the fixed vector
-     * numpy.random.default_rng(0).standard_normal(3), as cppf_amd.inference._assemble does. */
+     * numpy.random.default_rng(0).standard_normal(3), as cppf_amd.inference._assemble does.
+     * An instance the shape-polymorphic vote refused (arg-max index -1, peak NaN) has no pose: T, up, right and scale of its record
+     * are NaN; the arg-max -1, the survivor count and the object id are written as always. */
     double* record_out;
     const long long* object_id_dev;
     long long object_id_host;

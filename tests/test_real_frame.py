@@ -284,6 +284,50 @@ def test_pipelined_frames_equal_the_synchronous_ones(dev):
     assert pend[0].result() is got[0]           # idempotent
 
 
+@pytest.mark.gpu
+def test_a_pipelined_frame_keeps_its_own_depth_when_the_caller_refills_one_buffer(dev):
+    """A video loop with ONE depth buffer, refilled in place: frame A submitted, the buffer overwritten with frame B, frame B
+    submitted, then both results collected.  The runner is fresh, so frame A's many-tile instances (the laptop, and a bowl mask that
+    covers both bowls) are refused by their chains and take the eager fallback of result() -- which must compute them from frame
+    A's depth (the frame's own pinned copy), not from whatever the caller's buffer holds by then.  Both frames equal run() of a second
+    runner on separate copies of A and B, with the comparisons of test_pipelined_frames_equal_the_synchronous_ones."""
+    from cppf_amd import training
+    from cppf_amd.config import CATEGORIES
+    from cppf_amd.frames import FrameRunner
+    from cppf_amd.utils.util import read_depth_png
+    A = read_depth_png(DEPTH)
+    B = np.ascontiguousarray(np.where(A > 0, A + np.uint16(7), A).astype(A.dtype))
+    inst = instances(A)
+    inst[1] = ("bowl", inst[1][1] | inst[2][1])
+    nets = {}
+    for cat, src in (("mug", "mug"), ("laptop", "laptop"), ("bowl", "bottle"), ("can", "bottle")):
+        penc, enc = training.load_weights(os.path.join(GOLDEN, f"trained_{src}.npz"), CATEGORIES[src], dev)
+        nets[cat] = (enc, penc)
+    encs = {c: v[0] for c, v in nets.items()}
+    pencs = {c: v[1] for c, v in nets.items()}
+    sync = FrameRunner(encs, pencs, dev)
+    want = [sync.run(A.copy(), inst, seed=21), sync.run(B.copy(), inst, seed=22)]
+    assert any(a is not None and b is not None and not np.array_equal(a["T"], b["T"]) for a, b in zip(*want))     # the frames differ
+    piped = FrameRunner(encs, pencs, dev)
+    buf = np.empty_like(A)
+    assert buf.dtype == np.uint16 and buf.flags.c_contiguous
+    buf[...] = A
+    pa = piped.submit(buf, inst, seed=21)
+    buf[...] = B
+    pb = piped.submit(buf, inst, seed=22)
+    got_a = pa.result()
+    assert piped.last["eager"] > 0, piped.last        # frame A did take the fallback: the test cannot pass without it having run
+    got = [got_a, pb.result()]
+    for k, (w_f, g_f) in enumerate(zip(want, got)):
+        assert len(w_f) == len(g_f)
+        for i, (w, g) in enumerate(zip(w_f, g_f)):
+            assert (w is None) == (g is None), (k, i)
+            if w is not None:
+                assert g["argmax"] == w["argmax"] and g["n_surv"] == w["n_surv"] and g["n_points"] == w["n_points"], (k, i)
+                for key in ("T", "up", "right", "scale"):
+                    assert np.array_equal(g[key], w[key]), (k, i, key)
+
+
 def _eager_frame_cloud(d_dev, mask, res, k, k_min, n_cap):
     """What the frame stage must leave for one member, from the eager path alone (frames.instance_cloud's steps -- the sort-based
     cppf_backproject / cppf_voxel_dedupe, cppf_knn, cppf_estimate_normals -- and the host's grid_shape): the first n_cap valid
