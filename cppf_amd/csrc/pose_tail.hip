@@ -1293,6 +1293,8 @@ extern "C" int cppf_pose_tail_batch(int n_items, const CppfPoseTailItem* items, 
             if (second_kind != 0 && second_kind != kind) return CPPF_EINVAL;   // one launch, one precision
             second_kind = kind;
             if (!it.feat || !it.packed || !it.u_rot || !it.mlp_workspace) return CPPF_EINVAL;
+            // (here, not in launch 4's own check: by then launches 1-3 have zeroed the record and written the mask)
+            if (it.mlp_workspace_bytes < cppf_pair_mlp_workspace_bytes(it.n_points, F, dims, n_res, out_dim)) return CPPF_EWORKSPACE;
             CppfPairMlpItem& M = sel_items[n_second++];
             M = CppfPairMlpItem{};
             M.pc = it.pc; M.nrm = it.nrm; M.feat = it.feat; M.idxs = it.idx64 ? (const void*)it.idx64 : (const void*)it.idx32;

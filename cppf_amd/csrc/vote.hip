@@ -1974,11 +1974,33 @@ extern "C" int cppf_vote_batch_workgroups(int n_items, int flags)
     return w;
 }
 
+// whether the item's own call would refuse its workspace (vote_impl's checks, in their order): the batch asks before its first launch
+static bool v3_item_workspace_short(const CppfVoteItem& it, int n_rots)
+{
+    const bool dyn = it.shape_dev != nullptr;
+    const int gx = dyn ? 1 : it.gx, gy = dyn ? 1 : it.gy, gz = dyn ? 1 : it.gz;
+    if (!it.points || !it.grid || !it.corner) return false;
+    if (it.n_ppfs > 0 && (!it.outputs || !it.point_idxs)) return false;
+    if (gx < 1 || gy < 1 || gz < 1 || it.n_ppfs < 0 || it.n_points < 1 || (int64_t)gx * gy * gz > 0x7fffffffll) return false;
+    size_t need = 256;
+    if (dyn) {
+        if (it.n_ppfs < 1 || it.n_ppfs > 0xffffffffll || it.grid_capacity < 1 || it.grid_capacity > 0x7fffffffll) return false;
+        need = v3_workspace_bytes_dyn(it.many_tiles, it.n_ppfs);
+    } else if (v3_eligible(it.n_ppfs, n_rots, gx, gy, gz)) {
+        need = v3_workspace_bytes(it.n_ppfs, gx, gy, gz);
+    }
+    return !it.workspace || it.workspace_bytes < need;
+}
+
 extern "C" int cppf_vote_argmax_batch(int n_items, const CppfVoteItem* items, int n_rots, int adaptive, int flags, void* stream)
 {
     if (n_items < 1 || n_items > V3_BATCH_MAX || !items) return CPPF_EINVAL;
     if ((flags & ~(1 | (0x1ff << 8))) != 0) return CPPF_EINVAL;
     if (n_rots < 1 || n_rots > CPPF_MAX_ROTS) return CPPF_EINVAL;
+    // a short workspace refuses the whole batch before anything is launched: the loop below launches as it goes (an item's own
+    // launches, a many-tile item's binning), so a later item's refusal would otherwise find earlier items half run
+    for (int i = 0; i < n_items; ++i)
+        if (v3_item_workspace_short(items[i], n_rots)) return CPPF_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int accumulate = flags & 1;
     auto shares_the_launch = [&](const CppfVoteItem& it) -> bool {

@@ -168,7 +168,9 @@ int cppf_counts_argmax_select(const int32_t* counts, int n, const double* sphere
  *            cppf_pair_mlp_bf16_decode_sel_batch); a batch that mixes 1 and 2 is CPPF_EINVAL
  *   mlp_workspace  the per-point table the first pass (cppf_pair_mlp_decode / _batch) left for this object
  * Common to the batch: the pair-encoder architecture (standard fused one only), n_rots, the sphere bins (unit vectors with a monotone y
- * column: fibonacci_sphere; sphere_sorted_by_y = +1 descending / -1 ascending), thr = cos(angle_tol), max_rot_pairs (:277-280). */
+ * column: fibonacci_sphere; sphere_sorted_by_y = +1 descending / -1 ascending), thr = cos(angle_tol), max_rot_pairs (:277-280).
+ * A sums_workspace below cppf_pose_sums_workspace_bytes() or, for an item with second_pass, an mlp_workspace below
+ * cppf_pair_mlp_workspace_bytes(n_points, ...) is CPPF_EWORKSPACE, returned before anything is enqueued: no buffer of any item is touched. */
 typedef struct CppfPoseTailItem {
     const float* pc; const float* nrm; const float* feat;          /* device f32[n_points,3], f32[n_points,3], f32[n_points,F] */
     const long long* idx64; int32_t* idx32;                         /* pair list i64[n_pairs,2]; its i32 copy (OUTPUT of launch 2).  idx64 NULL:
@@ -286,7 +288,8 @@ int cppf_vote_argmax_dyn(const float* points, const float* outputs, const float*
  * gets the launches cppf_vote_argmax / cppf_vote_argmax_dyn would issue for it.  Per item the grid, arg-max and peak are those of
  * its own cppf_vote_argmax* call, bit for bit, whatever either call's width: the grid is the exact integer sum of the quantised
  * deposits and the fixed-point scale is that of a 64-wide launch at every width (both forms).  flags: as `accumulate` of
- * cppf_vote_argmax.  Replaces n launches of `ppf_kernel` (models/voting.py:8-66, nocs/inference.py:192-205) + np.argmax (:207-208). */
+ * cppf_vote_argmax.  An item whose workspace is missing or shorter than its query refuses the whole batch (CPPF_EWORKSPACE)
+ * before anything is launched: no item's grid, result or workspace state has been touched.  Replaces n launches of `ppf_kernel` (models/voting.py:8-66, nocs/inference.py:192-205) + np.argmax (:207-208). */
 typedef struct CppfVoteItem {
     const float* points;      /* device f32[n_points,3] */
     const float* outputs;     /* device f32[n_ppfs,2] (mu, nu) */
