@@ -22,12 +22,21 @@ def _finite(p):
         and p["scale_norm"] > 0
 
 
+def _box(p):
+    """RT (rotation * scale_norm, translation), scales (scale / scale_norm) and extents (scale) of a pose dict"""
+    RT = np.eye(4)
+    RT[:3, :3] = np.asarray(p["R"], np.float64) * float(p["scale_norm"])
+    RT[:3, 3] = np.asarray(p["T"], np.float64)
+    scale = np.asarray(p["scale"], np.float64)
+    return dict(RT=RT, scales=scale / float(p["scale_norm"]), extents=scale)
+
+
 def _needs_verify(score, min_agreement, min_fill, min_within):
     return score == "agreement" or any(m is not None for m in (min_agreement, min_fill, min_within))
 
 
 def pool_detections(outs, names, cfgs=None, nms_thresh=0.3, cross_category=False, score="diff", device=None, min_agreement=None,
-                    min_fill=None, min_within=None):
+                    min_fill=None, min_within=None, use_refined=False):
     """outs: scene_poses / scene_frame dicts, one per category, in the order of `names` (the categories' names); cfgs: their configs
     (kept beside the detections for callers; nothing here reads them).
     Every finite proposal with scale_norm > 0 becomes a detection dict:
@@ -48,7 +57,11 @@ def pool_detections(outs, names, cfgs=None, nms_thresh=0.3, cross_category=False
     pose["verify"]["agreement"], a ratio in [0, 1] that means the same for every network.  min_agreement / min_fill / min_within (None:
     no filter) drop, BEFORE the NMS, every detection whose verify agreement / fill / within is below the bound.  When any of these is
     used the dict gains filtered {name: n}, the detections the filters dropped per category; they count in proposals_per_category and
-    not in suppressed.  With all four at their defaults nothing here changes."""
+    not in suppressed.  With all four at their defaults nothing here changes.
+    use_refined=True (scene_poses.refine_poses has run on the poses): where pose["refined"] is a finite pose, the detection's RT, scales
+    and the box the NMS sees come from it, and the detection gains coarse = dict(RT, scales, scale), the first pass's values.  The score,
+    the verify counts and the filters stay the FIRST pass's: nothing is re-scored or re-verified from the refined pose.  A proposal
+    without a refined pose (skipped, refused, not finite) stays a detection with its first-pass box."""
     names = list(names)
     if len(outs) != len(names):
         raise ValueError(f"{len(outs)} outputs for {len(names)} category names")
@@ -68,16 +81,16 @@ def pool_detections(outs, names, cfgs=None, nms_thresh=0.3, cross_category=False
             if any(p["verify"][key] < m for key, m in bounds):
                 dropped[c] += 1
                 continue
-            RT = np.eye(4)
-            RT[:3, :3] = np.asarray(p["R"], np.float64) * float(p["scale_norm"])
-            RT[:3, 3] = np.asarray(p["T"], np.float64)
-            dets.append(dict(class_name=names[c], category=c, RT=RT, scales=np.asarray(p["scale"], np.float64) / float(p["scale_norm"]),
-                             score=float(value), pose=p, proposal=k))
+            det = dict(class_name=names[c], category=c, score=float(value), pose=p, proposal=k, **_box(p))
+            r = p.get("refined") if use_refined else None
+            if r is not None and _finite(r):
+                det.update(coarse=dict(RT=det["RT"], scales=det["scales"], scale=det["extents"]), **_box(r))
+            dets.append(det)
     n = len(dets)
     cat = np.array([d["category"] for d in dets], np.int64).reshape(n)
     scores = np.array([d["score"] for d in dets], np.float64).reshape(n)
     RTs = np.stack([d["RT"] for d in dets]) if n else np.zeros((0, 4, 4))
-    extents = np.stack([np.asarray(d["pose"]["scale"], np.float64) for d in dets]) if n else np.zeros((0, 3))
+    extents = np.stack([d.pop("extents") for d in dets]) if n else np.zeros((0, 3))
     keep = np.arange(n)
     if nms_thresh is not None and n:
         keep = np.concatenate(E.nms_3d(RTs, extents, scores, nms_thresh, groups=cat, device=device) + [np.zeros(0, np.int64)])
@@ -102,30 +115,39 @@ def pool_detections(outs, names, cfgs=None, nms_thresh=0.3, cross_category=False
 
 
 def frame_detections(depth, intrinsics, networks, n_pairs=5_000_000, seed=0, jitter=None, nms_thresh=0.3, cross_category=False,
-                     score="diff", min_agreement=None, min_fill=None, min_within=None, **scene_kw):
+                     score="diff", min_agreement=None, min_fill=None, min_within=None, refine=None, refine_kw=None, **scene_kw):
     """One depth frame with no instance masks -> the detections of all categories (pool_detections' dict, plus outs: the categories'
     scene_frame dicts).
     networks: an ordered mapping name -> (point_encoder, encoder, cfg), modules on one HIP device, in either precision (what the
     encoders are set to is what runs).  scene_frame runs once per category with the same `seed` (and jitter); the dense cloud and its
     normals are computed once per distinct (cfg.res, cfg.knn) and shared (scene_frame's cloud=: the same bits as without sharing).
     The NMS runs on the networks' device.  score="agreement" / min_agreement / min_fill / min_within: pool_detections'; scene_frame
-    then runs with verify=True (only then).  scene_kw: scene_poses' options (thresh, max_proposals, ...)."""
+    then runs with verify=True (only then).  scene_kw: scene_poses' options (thresh, max_proposals, ...).
+    refine (opt-in, default None: the same launches and the same bits as ever): a BatchPoseRunner that holds every category's two
+    encoders, or a dict name -> runner.  Every category's proposals are then refined as instances (scene_frame(refine=...): the
+    voxel-owner map is computed once per shared cloud) and pooled with use_refined=True: box, RT and scales from `refined` where it
+    exists, the first pass's under `coarse`; score, verification and filters stay the first pass's.  refine_kw: refine_poses' options."""
     from .scene_poses import frame_cloud, scene_frame
     if not networks:
         raise ValueError("frame_detections needs at least one category network")
-    names, outs, cfgs, clouds, dev = [], [], [], {}, None
+    names, outs, cfgs, clouds, owners, dev = [], [], [], {}, {}, None
     if _needs_verify(score, min_agreement, min_fill, min_within):
         scene_kw = dict(scene_kw, verify=True)
     for name, (point_encoder, encoder, cfg) in networks.items():
         key = (float(cfg.res), int(cfg.knn))
         if key not in clouds:
             clouds[key] = frame_cloud(depth, intrinsics, cfg, jitter)
+        extra = {}
+        if refine is not None:
+            extra = dict(refine=refine[name] if isinstance(refine, dict) else refine, refine_kw=dict(refine_kw or {}, owner=owners.get(key)))
         out = scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=n_pairs, seed=seed, jitter=jitter, cloud=clouds[key],
-                          **scene_kw)
+                          **extra, **scene_kw)
+        if refine is not None:
+            owners[key] = out["owner"]
         dev = out["pc"].device
         names.append(name); outs.append(out); cfgs.append(cfg)
     res = pool_detections(outs, names, cfgs, nms_thresh, cross_category, score, device=dev, min_agreement=min_agreement,
-                          min_fill=min_fill, min_within=min_within)
+                          min_fill=min_fill, min_within=min_within, **({} if refine is None else dict(use_refined=True)))
     res["outs"] = outs
     return res
 

@@ -631,7 +631,8 @@ def _assemble(rec, cfg, rng=None):
 
 def nocs_result(poses, res=None):
     """The per-image result record of nocs/inference.py:114-117,213,338-342 from a list of pose dicts (estimate_pose /
-    PosePipeline.run / _assemble): `pred_RTs` f32[n,4,4] (identity-initialised, translation in the last column, rotation
+    PosePipeline.run / _assemble; a mask-free pose of scene_poses or its `refined` dict, scene_poses.refine_poses: T, R, scale and
+    scale_norm are what is read): `pred_RTs` f32[n,4,4] (identity-initialised, translation in the last column, rotation
     scaled by |scale|) and `pred_scales` f32[n,3] (scale / |scale|), written into `res` (the detection dict the script
     pickles, :344-345) or a new dict -- the format nocs/eval.py reads."""
     n = len(poses)

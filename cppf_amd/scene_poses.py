@@ -19,8 +19,8 @@ import torch
 
 from . import _lib
 from ._torch_util import call, canon, require_cuda, scratch, workspace
-from .scene_stage import (MAX_CENTERS, backvote_multi, frame_cloud, frame_inputs, on_device, pairs_tensor, segment_instances,
-                          segment_proposals, sphere_tables, verify_proposals, vote_proposals)
+from .scene_stage import (MAX_CENTERS, backvote_multi, frame_cloud, frame_inputs, gather_instances, on_device, pairs_tensor,
+                          segment_instances, segment_proposals, sphere_tables, verify_proposals, vote_proposals, voxel_owner)
 from .zero_shot import check_loop_args
 
 F32, I32 = torch.float32, torch.int32
@@ -44,7 +44,8 @@ def check_args(max_proposals, thresh=50, margin=10, max_iters=None):
 
 
 def scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, *, angle_tol=1.5, max_rot_pairs=10000, rot_order=None, num_rots=72,
-                sigma=1.0, thresh=50, margin=10, max_proposals=32, max_iters=None, min_contrib=12, outputs=None, heads=None, verify=False):
+                sigma=1.0, thresh=50, margin=10, max_proposals=32, max_iters=None, min_contrib=12, outputs=None, heads=None, verify=False,
+                keep_masks=False):
     """The poses of every object of a scene cloud, with no instance masks.
     encoder: PPFEncoder with the standard architecture and the bin head (out_dim = 2 tr_bins + 2 rot_bins + 5), on pc's device, in
     the precision it is set to; pc, nrm f32[N,3], feat f32[N,F], idx [P,2], u_tr / u_rot f32[P,2] (uniforms standing in for
@@ -57,7 +58,9 @@ def scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, *, angle_tol=1.5,
     poses: one dict per proposal with T f64[3] (the proposal), R, up, right (None unless cfg.regress_right), scale f64[3],
     scale_norm, RT f64[4,4], cnt (smoothed peak), diff, point_mask bool[N], n_pairs -- what inference.nocs_result reads.
     verify=True: every pose dict gains verify, scene_stage.verify_proposals' dict for that proposal (two more launches per group of 32
-    proposals and one more read-back after the poses; everything else is computed and launched as without it)."""
+    proposals and one more read-back after the poses; everything else is computed and launched as without it).
+    keep_masks=True: the dict gains point_masks, the device u8[K,N] rows segment_proposals wrote (what refine_poses gathers from);
+    nothing else changes."""
     from .inference import _assemble, grid_shape
     max_iters = check_args(max_proposals, thresh, margin, max_iters)
     given = outputs is not None and heads is not None
@@ -141,24 +144,116 @@ def scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, *, angle_tol=1.5,
         for p, v in zip(out["poses"], verify_proposals(pc, idx32, bits, masks, out["poses"], cfg)):
             p["verify"] = v
     out.update(surv_bits=bits[0][:P], offsets=offsets, pairs=pairs[:int(offsets[K])])
+    if keep_masks:
+        out["point_masks"] = masks
     return out
 
 
-def scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=5_000_000, seed=0, jitter=None, cloud=None, **kw):
+REFINED_KEYS = ("T", "R", "up", "right", "scale", "scale_norm", "RT", "n_points", "peak", "argmax")
+
+
+def refined_pose(rec, cfg, n_points):
+    """one finished record of BatchPoseRunner (sharding.pack_record's layout: T, up, right, scale, arg-max, peak) -> a dict with the
+    first pass's keys T, R, up, right (None unless cfg.regress_right), scale, scale_norm, RT, plus n_points, peak and argmax"""
+    rec = np.asarray(rec, np.float64)
+    T, up, right, scale = rec[0:3].copy(), rec[3:6].copy(), rec[6:9].copy(), rec[9:12].copy()
+    R = np.stack([np.cross(up, right), up, right], -1) if cfg.z_right else np.stack([right, up, np.cross(right, up)], -1)
+    scale_norm = float(np.linalg.norm(scale))
+    RT = np.eye(4)
+    RT[:3, :3] = R * scale_norm
+    RT[:3, -1] = T
+    return dict(T=T, R=R, up=up, right=right if cfg.regress_right else None, scale=scale, scale_norm=scale_norm, RT=RT,
+                n_points=int(n_points), peak=float(rec[13]), argmax=int(rec[12]))
+
+
+def refine_poses(out, runner, cfg, n_pairs=100_000, seed=0, min_points=None, owner=None):
+    """Every proposal of a mask-free frame once more as an INSTANCE: its point mask (over the sparse cloud at 4 res) selects its
+    points of the dense cloud (res) on the device -- scene_stage.gather_instances, one pass for all proposals -- and the packed clouds
+    go through the instance path (SPRIN on the instance's own cloud, n_pairs pairs inside it, the whole pose) as ONE resident batch of
+    `runner`, a BatchPoseRunner that holds the pair encoder and the point encoder of cfg.category.
+    out: scene_frame's dict (hi_pc, hi_normals, indices, poses; point_masks, the device masks, when it was computed with
+    keep_masks=True -- else the poses' host masks are uploaded again).  owner: scene_stage.voxel_owner(hi_pc, indices, 4 cfg.res) when
+    the caller has it already (it depends on the cloud alone: categories that share a cloud share it).
+    Sets, for every pose p of out["poses"], p["refined"] = dict(T, R, up, right, scale, scale_norm, RT, n_points, peak, argmax)
+    (refined_pose), or p["refined"] = None with p["refine_skipped"] = "points" (fewer than min_points gathered points; default: the
+    smallest cloud the point encoder takes, its k) or "refused" (the runner's mark record[:, 12] < 0: the instance did not fit the
+    pipeline it ran on).  A refusal is settled here -- the runner's late check of THIS batch is taken and not raised; an earlier
+    batch's still raises.  Object j of the batch is the j-th proposal that has enough points: its pairs are drawn from (seed, j).
+    The first-pass fields of every pose stay as they were.  Returns the list of refined dicts / None, one per proposal."""
+    from ._lib import CppfError
+    poses = out["poses"]
+    K = len(poses)
+    if K == 0:
+        return []
+    cat = cfg.category
+    if cat not in runner.encoders or cat not in runner.point_encoders:
+        raise ValueError(f"refine_poses: the runner needs the pair encoder and the point encoder of {cat!r}")
+    hi, hi_nrm = out["hi_pc"], out["hi_normals"]
+    dev = hi.device
+    min_points = int(runner.point_encoders[cat].k) if min_points is None else int(min_points)
+    if owner is None:
+        owner = voxel_owner(hi, out["indices"], 4 * cfg.res)
+    masks = out.get("point_masks")
+    if masks is None:
+        masks = torch.from_numpy(np.ascontiguousarray(np.stack([p["point_mask"] for p in poses]).astype(np.uint8))).to(dev)
+    clouds = []                                                               # (pts, nrm) row ranges of the packed buffers, per proposal
+    for g in range(0, K, MAX_CENTERS):
+        pts, nrm, _, off, _ = gather_instances(hi, hi_nrm, owner, masks[g:g + MAX_CENTERS])
+        clouds += [(pts[int(a):int(b)], nrm[int(a):int(b)]) for a, b in zip(off[:-1], off[1:])]
+    take = [k for k in range(K) if clouds[k][0].shape[0] >= max(min_points, 1)]
+    refined = [None] * K
+    for p in poses:
+        p["refined"] = None
+        p["refine_skipped"] = "points"
+    if take:
+        objs = runner.put([dict(pc=clouds[k][0], normals=clouds[k][1], cfg=cfg, n_pairs=int(n_pairs)) for k in take])
+        recs = runner.run(objs, seed=seed)
+        batch = runner._batch_no - 1
+        recs = recs.cpu().numpy() if torch.is_tensor(recs) else np.asarray(recs)
+        try:
+            runner.check()
+        except CppfError as e:
+            if getattr(e, "batch", None) != batch:
+                raise
+        for j, k in enumerate(take):
+            if recs[j, 12] < 0:
+                poses[k]["refine_skipped"] = "refused"
+                continue
+            refined[k] = poses[k]["refined"] = refined_pose(recs[j], cfg, clouds[k][0].shape[0])
+            del poses[k]["refine_skipped"]
+    return refined
+
+
+def scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=5_000_000, seed=0, jitter=None, cloud=None, refine=None,
+                refine_kw=None, **kw):
     """One depth frame with NO instance masks -> scene_poses' dict: zero_shot_frame's pre-processing (nocs/zero_shot.ipynb cells 3-6:
     the cloud de-duplicated at res, the sparse cloud at 4 res, SPRIN features on the dense cloud, frames.draw_pairs(seed, 0, ...) --
     whose uniforms feed the bin decode -- and the "indistinguishable" pair filter), then scene_poses with the bin-head encoder.
     depth [H,W] in millimetres (numpy uint16 or device); jitter: f32[n_pixels,3] standard-normal draws (None: none); cloud: the
     (hi, hi_nrm) pair frame_cloud returned for this depth, intrinsics, jitter and a config with the same (res, knn) -- it replaces the
     back-projection, the de-duplication and the normals (None: they are computed here: the same bits); kw: scene_poses' options.
-    Adds hi_pc / hi_normals, indices, pc / normals, feat, idx, n_pairs (after the filter)."""
+    Adds hi_pc / hi_normals, indices, pc / normals, feat, idx, n_pairs (after the filter).
+    refine (opt-in; None: nothing below runs and the dict has the keys and the bits it always had): a BatchPoseRunner with both
+    encoders of cfg.category.  Every pose then gains `refined` (refine_poses: the proposal's dense points through the instance path)
+    and the dict gains point_masks (device) and owner (scene_stage.voxel_owner's map of the dense cloud); refine_kw: refine_poses'
+    options (n_pairs, seed -- default: this frame's seed --, min_points, owner)."""
     check_encoder(encoder, cfg)
     check_args(kw.get("max_proposals", 32), kw.get("thresh", 50), kw.get("margin", 10), kw.get("max_iters"))
     require_cuda()
     hi, hi_nrm, ind, pc, nrm, feat, idx, (u_tr, u_rot) = frame_inputs(depth, intrinsics, point_encoder, cfg, n_pairs, seed, jitter, cloud)
+    if refine is not None:
+        kw = dict(kw, keep_masks=True)
     out = scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, **kw)
     out.update(hi_pc=hi, hi_normals=hi_nrm, indices=ind, pc=pc, normals=nrm, feat=feat, idx=idx, n_pairs=int(idx.shape[0]))
+    if refine is not None:
+        rkw = dict(refine_kw or {})
+        rkw.setdefault("seed", seed)
+        if rkw.get("owner") is None:
+            rkw["owner"] = voxel_owner(hi, ind, 4 * cfg.res)
+        out["owner"] = rkw["owner"]
+        refine_poses(out, refine, cfg, **rkw)
     return out
 
 
-__all__ = ["scene_poses", "scene_frame", "frame_cloud", "backvote_multi", "segment_instances", "check_encoder", "check_args"]
+__all__ = ["scene_poses", "scene_frame", "refine_poses", "refined_pose", "frame_cloud", "backvote_multi", "segment_instances", "check_encoder",
+           "check_args"]

@@ -166,6 +166,96 @@ def segment_proposals(pc, outputs, idx32, corner, res, dims, worlds, num_rots, t
     return cat(masks, U8, 0, N), cat(pairs, I32, 1), np.array(offsets, np.int64), cat(counts, I32, 0), bits
 
 
+# ----------------------------------------------------------------------------- proposal masks -> instance clouds (csrc/instances.hip)
+GATHER_CHUNK, GATHER_MAX_CHUNKS = 1024, 8192      # include/cppf.h: CPPF_GATHER_CHUNK, CPPF_GATHER_MAX_CHUNKS
+
+
+def voxel_owner(hi, pc_index, q):
+    """i32[M] on hi's device: for every point of the dense cloud hi f32[M,3] the position in the sparse cloud hi[pc_index] of the
+    point that represents its voxel of edge q, -1 where no sparse point has that voxel (pc_index: frame_inputs' `ind`, q = 4 cfg.res;
+    on sparse_quantize's output every dense point has an owner.  A caller's own subset may leave voxels out, or name one twice: the
+    first position then owns it).  The voxel is floor((double)p / q) per axis by TRUE division, sparse_quantize's arithmetic
+    (utils/util.py:117-121): a tensor divisor divides, a Python number would be multiplied by as its reciprocal and move points on a
+    voxel face into the neighbouring voxel.  Points that are not finite or beyond 2^20 voxels from the origin (the range of
+    cppf_voxel_dedupe's key) get -1.  Torch ops on the device (keys, one sort, one searchsorted): it runs once per cloud, and every
+    category whose config shares (res, knn) can reuse the result."""
+    dev = hi.device
+    hi = canon(hi, F32, dev, "hi", (3,))
+    pc_index = canon(pc_index, (torch.int64, torch.int32), dev, "pc_index").reshape(-1).long()
+    M, n = hi.shape[0], pc_index.shape[0]
+    if M == 0 or n == 0:
+        return torch.full((M,), -1, dtype=I32, device=dev)
+    if int(pc_index.min()) < 0 or int(pc_index.max()) >= M:
+        raise ValueError(f"pc_index must index the dense cloud (0..{M - 1})")
+    p64 = hi.double()
+    v = torch.floor(p64 / torch.full_like(p64, float(q)))
+    ok = (torch.isfinite(v) & (v >= -(1 << 20)) & (v < (1 << 20))).all(dim=1)
+    c = torch.where(ok[:, None], v, torch.zeros_like(v)).long() + (1 << 20)
+    key = torch.where(ok, (c[:, 0] << 42) | (c[:, 1] << 21) | c[:, 2], torch.full((M,), -1, dtype=torch.int64, device=dev))
+    sk, order = torch.sort(key[pc_index], stable=True)
+    pos = torch.searchsorted(sk, key)                                         # (left: the first of equal keys)
+    pos_c = pos.clamp(max=n - 1)
+    hit = ok & (pos < n) & (sk[pos_c] == key)
+    return torch.where(hit, order[pos_c], torch.full_like(pos_c, -1)).to(I32)
+
+
+def check_gather_args(n_props, n_sparse, n_dense, capacity):
+    """the refusals of cppf_gather_instances that need no device, as ValueError"""
+    K, N, M, cap = int(n_props), int(n_sparse), int(n_dense), int(capacity)
+    if not 1 <= K <= MAX_CENTERS:
+        raise ValueError(f"gather_instances takes 1..{MAX_CENTERS} masks (one bit per proposal), got {K}")
+    if N < 0 or M < 0 or cap < 0:
+        raise ValueError(f"negative size: n_sparse {N}, n_dense {M}, capacity {cap}")
+    if M > 2 ** 31 - 1 or K * M > 2 ** 31 - 1 or N > 2 ** 31 - 1:
+        raise ValueError(f"{K} masks over {M} dense points pass the int32 offsets")
+    if (M + GATHER_CHUNK - 1) // GATHER_CHUNK > GATHER_MAX_CHUNKS:
+        raise ValueError(f"{M} dense points: one pass takes at most {GATHER_CHUNK * GATHER_MAX_CHUNKS}")
+
+
+def gather_instances_device(hi, hi_nrm, owner, masks, capacity=None, out=None):
+    """cppf_gather_instances, enqueued on the current stream with nothing read back: dict(member i32[M] (the u32 words), offsets
+    i32[K+1], pts f32[capacity,3], nrm f32[capacity,3], src i32[capacity]) of device tensors; capacity: M by default; out: such a dict
+    to write into (the caller's buffers)."""
+    dev = hi.device
+    (K, N), M = masks.shape, hi.shape[0]
+    capacity = M if capacity is None else int(capacity)
+    check_gather_args(K, N, M, capacity)
+    if out is None:
+        out = dict(member=torch.empty(max(M, 1), dtype=I32, device=dev), offsets=torch.empty(K + 1, dtype=I32, device=dev),
+                   pts=torch.empty((max(capacity, 1), 3), dtype=F32, device=dev), nrm=torch.empty((max(capacity, 1), 3), dtype=F32, device=dev),
+                   src=torch.empty(max(capacity, 1), dtype=I32, device=dev))
+    counts = torch.empty(max(K * ((M + GATHER_CHUNK - 1) // GATHER_CHUNK), 1), dtype=I32, device=dev)
+    call("cppf_gather_instances", dev, hi, hi_nrm, owner, masks, K, N, M, capacity, out["member"], out["offsets"], out["pts"], out["nrm"],
+         out["src"], counts)
+    return out
+
+
+def gather_instances(hi, hi_nrm, owner, masks, capacity=None):
+    """Proposal masks -> instance clouds, all proposals of a group in one pass over the dense cloud (cppf_gather_instances).
+    hi, hi_nrm f32[M,3]: the dense cloud and its normals; owner i32[M]: voxel_owner's map; masks u8[K,N], K <= 32: the point_masks
+    of segment_proposals (over the sparse cloud): device tensors.
+    Returns (pts f32[T,3], nrm f32[T,3], src i32[T]: device; offsets i64[K+1]: host; member i32[M] (bit k = dense point i belongs to
+    proposal k): device): proposal k's points are rows offsets[k]:offsets[k+1], in increasing dense index -- hi[member_k].  The K + 1
+    offsets are read back once; where the members outnumber `capacity` rows (default M) the call runs once more with the reported
+    size.  An owner >= N raises ValueError (found on the device, nothing was gathered)."""
+    dev = hi.device
+    hi, hi_nrm = canon(hi, F32, dev, "hi", (3,)), canon(hi_nrm, F32, dev, "hi_nrm", (3,))
+    owner, masks = canon(owner, I32, dev, "owner"), canon(masks, U8, dev, "masks")
+    if masks.dim() != 2 or owner.shape != (hi.shape[0],) or hi_nrm.shape != hi.shape:
+        raise ValueError(f"gather_instances: hi {tuple(hi.shape)}, hi_nrm {tuple(hi_nrm.shape)}, owner {tuple(owner.shape)}, masks "
+                         f"{tuple(masks.shape)}: expected [M,3], [M,3], [M], [K,N]")
+    K = masks.shape[0]
+    capacity = hi.shape[0] if capacity is None else int(capacity)
+    g = gather_instances_device(hi, hi_nrm, owner, masks, capacity)
+    off = g["offsets"].cpu().numpy().astype(np.int64)
+    if off[K] < 0:
+        raise ValueError(f"gather_instances: an owner is >= {masks.shape[1]}, the number of sparse points the masks speak of")
+    if off[K] > capacity:
+        g = gather_instances_device(hi, hi_nrm, owner, masks, capacity=int(off[K]))
+    T = int(off[K])
+    return g["pts"][:T], g["nrm"][:T], g["src"][:T], off, g["member"][:hi.shape[0]]
+
+
 # ----------------------------------------------------------------------------- proposal verification (csrc/verify.hip)
 VERIFY_COUNTS = ("within", "agree", "cross", "cross_agree", "mask_pts", "mask_in_box", "box_pts")
 VERIFY_RATIOS = (("agreement", "agree", "within"), ("leak", "cross_agree", "cross"), ("fill", "mask_in_box", "mask_pts"),

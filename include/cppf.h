@@ -934,6 +934,41 @@ int cppf_segment_instances(const int32_t* point_idxs, const uint32_t* surv_bits,
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Instance clouds of the proposals (csrc/instances.hip; additive, ABI version unchanged): what connects the mask-free path's point
+ * masks to the instance path.  A mask of cppf_segment_instances speaks of the SPARSE cloud (one point per voxel of 4 res); the
+ * instance path wants the DENSE cloud's points (res).  `owner` maps the one onto the other: owner[i] = the position in the sparse
+ * cloud of the point that represents dense point i's voxel, negative = none (cppf_amd.scene_stage.voxel_owner computes it once per
+ * cloud with the fp64 true division of cppf_voxel_dedupe).
+ *
+ * cppf_gather_instances: ONE pass over the dense cloud for n_props (1..32) proposals.
+ *   in:  hi, hi_nrm device f32[n_dense,3]; owner device i32[n_dense]; masks device u8[n_props,n_sparse] (non-zero = member: the
+ *        point_masks of cppf_segment_instances).
+ *   out: member device u32[n_dense]: bit k of member[i] is set iff 0 <= owner[i] and masks[k][owner[i]] != 0; bits >= n_props are 0.
+ *        offsets device i32[n_props+1]: the exclusive prefix of the proposals' member counts -- always complete.
+ *        pts, nrm device f32[capacity,3], src device i32[capacity]: rows offsets[k] .. offsets[k+1] hold hi[i], hi_nrm[i] and i for
+ *        the members i of proposal k in increasing i (what hi[member_k] gives on the host; a point in several masks is copied
+ *        into each).  Nothing is written at or beyond row `capacity`: when offsets[n_props] > capacity the call still returns 0 and
+ *        the caller repeats it with buffers of offsets[n_props] rows.  n_dense rows hold any one proposal.
+ *        chunk_counts device i32[CPPF_GATHER_COUNTS(n_props, n_dense)]: the members per proposal and chunk of CPPF_GATHER_CHUNK
+ *        dense points, proposal-major -- the call's only intermediate, a typed argument and not a workspace: n_props *
+ *        ceil(n_dense / CPPF_GATHER_CHUNK) integers, overwritten by every call.
+ *   Two launches on `stream` (memberships and counts from wave ballots; the copy, every workgroup summing the counts in front of
+ *   its own), no atomics, no read-back: the same words on every run.
+ *   An owner[i] >= n_sparse is never followed.  It is found on the stream and reported as offsets[n_props] = -1 (offsets[k] = 0
+ *   below it); pts, nrm and src are then left untouched and member is unspecified -- the way cppf_voxel_dedupe reports a cloud
+ *   it refuses.  The return value is still 0: the caller reads offsets.
+ *   CPPF_EINVAL: n_props outside 1..32, a negative size, n_dense or n_props n_dense or n_sparse > 2^31-1 (offsets, src and owner are
+ *   int32), a null pointer (pts / nrm / src may be NULL with capacity 0; every input and member / chunk_counts with n_dense 0).
+ *   CPPF_EUNSUPPORTED: more than CPPF_GATHER_MAX_CHUNKS chunks (8 388 608 dense points, cppf_frame_cloud_dyn's frame bound).
+ * ------------------------------------------------------------------------------------------- */
+#define CPPF_GATHER_CHUNK 1024
+#define CPPF_GATHER_MAX_CHUNKS 8192
+#define CPPF_GATHER_COUNTS(n_props, n_dense) ((int64_t)(n_props) * (((int64_t)(n_dense) + CPPF_GATHER_CHUNK - 1) / CPPF_GATHER_CHUNK))
+int cppf_gather_instances(const float* hi, const float* hi_nrm, const int32_t* owner, const uint8_t* masks, int n_props,
+                          int64_t n_sparse, int64_t n_dense, int64_t capacity, uint32_t* member, int32_t* offsets, float* pts,
+                          float* nrm, int32_t* src, int32_t* chunk_counts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Training views (utils/dataset.py:103-207, csrc/raster.hip): the pyrender `RenderFlags.DEPTH_ONLY` render of one mesh through
  * the dataset's PinholeCamera (:108-138), and the covered pixels as the dataset's point cloud.  Parity with pyrender is UNPINNED
  * (pyrender and its 24-bit depth buffer are not part of the project); the definition below is, to the operation, and

@@ -35,6 +35,13 @@ for the un-suppressed proposals of the reported frames, how each of agreement / 
 being a true positive (IoU >= 0.25 with a ground truth of its class).  Figures, no threshold.
 
     python scripts/eval_mesh_frames.py --procedural --train-steps 3000 --train-pairs 200000 --frames 20 --objects 4 --mask-free --score agreement --tune-frames 20
+
+--mask-free --refine: every proposal once more as an instance (scene_frame(refine=BatchPoseRunner): the proposal's point mask gathers
+its dense points on the device, scene_poses.refine_poses).  The same frames and the same networks in ONE run give two AP tables, the
+first pass's poses and the refined ones (a proposal without a refined pose keeps its first-pass pose; the scores are the first
+pass's in both), written to profiles/refine_eval.json (--out) under `mesh_frames`.  Figures, no threshold.
+
+    python scripts/eval_mesh_frames.py --procedural --train-steps 3000 --train-pairs 200000 --frames 20 --objects 4 --mask-free --refine
 """
 import argparse
 import json
@@ -117,10 +124,16 @@ def _mask_free_record(fr, preds):
 
 
 def _mask_free(args, sampler, encs, pencs, dev):
-    """the frames through scene_frame per category -> (result records, ms per frame, proposals, ground truths)"""
+    """the frames through scene_frame per category -> (result records, ms per frame, proposals, ground truths); with --refine also the
+    records with the refined poses in place of the first pass's and how many proposals have one (else None, 0)"""
     from cppf_amd.scene_poses import scene_frame
     names = sampler.synset_names
-    results, ms, n_prop, n_gt = [], [], 0, 0
+    ok = lambda p: all(np.all(np.isfinite(p[k])) for k in ("T", "R", "scale")) and p["scale_norm"] > 0
+    runner = None
+    if args.refine:
+        from cppf_amd.batch import BatchPoseRunner
+        runner = BatchPoseRunner(encs, dev, point_encoders=pencs)
+    results, refined, ms, n_prop, n_gt, n_ref = [], [], [], 0, 0, 0
     for i in range(args.frames):
         fr = sampler.sample()
         torch.cuda.synchronize()
@@ -128,16 +141,20 @@ def _mask_free(args, sampler, encs, pencs, dev):
         preds = []
         for c in sampler.categories:
             out = scene_frame(fr.depth_mm, fr.intrinsics, encs[c], pencs[c], CATEGORIES[c], n_pairs=args.scene_pairs, seed=i,
-                              thresh=args.thresh, max_proposals=args.max_proposals)
+                              thresh=args.thresh, max_proposals=args.max_proposals, **({} if runner is None else dict(refine=runner)))
             for p in out["poses"]:
-                if all(np.all(np.isfinite(p[k])) for k in ("T", "R", "scale")) and p["scale_norm"] > 0:
+                if ok(p):
                     preds.append((names.index(c), p, p["diff"]))
         ms.append((time.perf_counter() - t0) * 1e3)
         preds = sorted(preds, key=lambda t: -t[2])[:20]                  # (the evaluation's match tables hold 20 predictions per image)
         results.append(_mask_free_record(fr, preds))
+        if runner is not None:
+            use = lambda p: p["refined"] if p.get("refined") is not None and ok(p["refined"]) else p
+            refined.append(_mask_free_record(fr, [(c, use(p), s_) for c, p, s_ in preds]))
+            n_ref += sum(use(p) is not p for _, p, _ in preds)
         n_prop += len(preds)
         n_gt += len(fr.categories)
-    return results, ms, n_prop, n_gt
+    return results, ms, n_prop, n_gt, (refined if runner is not None else None), n_ref
 
 
 def _detections(args, sampler, encs, pencs, dev):
@@ -316,6 +333,8 @@ def main():
     ap.add_argument("--thresh", type=float, default=50.0, help="--mask-free: the proposal loop's threshold")
     ap.add_argument("--max-proposals", type=int, default=6, help="--mask-free: proposals per category and frame (the 20 best-scored "
                     "predictions of a frame are evaluated)")
+    ap.add_argument("--refine", action="store_true", help="--mask-free: also refine every proposal as an instance (scene_poses.refine_poses) "
+                    "and report the AP table with and without it from the same frames")
     ap.add_argument("--nms", type=float, default=None, metavar="T", help="--mask-free: the frames go through detections.frame_detections "
                     "with 3D box NMS per category at IoU threshold T (the reference's 0.3); AP with and without it from the same frames")
     ap.add_argument("--cross-category", action="store_true", help="--mask-free --nms: also a second NMS pass over the survivors of "
@@ -340,6 +359,10 @@ def main():
         args.out = os.path.join(ROOT, "profiles", "scene_verify_eval.json")
     if args.nms is not None and not args.mask_free:
         sys.exit("--nms / --cross-category belong to --mask-free")
+    if args.refine and (not args.mask_free or args.nms is not None or verify_mode):
+        sys.exit("--refine belongs to the plain --mask-free run (no --nms, no --score agreement)")
+    if args.refine and args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "refine_eval.json")
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "scene_detections_eval.json" if args.nms is not None else
                                 ("scene_poses_eval.json" if args.mask_free else "mesh_frames_eval.json"))
@@ -399,10 +422,37 @@ def main():
         tmp.cleanup()
         return
     if args.mask_free:
-        results, ms, n_prop, n_gt = _mask_free(args, sampler, encs, pencs, dev)
+        results, ms, n_prop, n_gt, refined, n_ref = _mask_free(args, sampler, encs, pencs, dev)
         deg, sh = [5, 10, 15], [5, 10, 15]
         iou = [float(t) for t in np.round(np.linspace(0, 1, 101), 2)]
         iou_aps, pose_aps, _, _ = E.compute_degree_cm_mAP(results, sampler.synset_names, None, deg, sh, iou, 0.1, True, device=dev)
+        if refined is not None:
+            rec = dict(device=torch.cuda.get_device_name(0), mode="mask-free with refinement: scene_frame(refine=BatchPoseRunner) per category "
+                       "on the whole depth image; the same proposals evaluated with the first pass's poses and with the refined ones",
+                       frames=args.frames, objects_per_frame=args.objects, scene_pairs=args.scene_pairs, refine_pairs=100000, thresh=args.thresh,
+                       max_proposals=args.max_proposals, seed=args.seed, categories={c: len(p) for c, p in cat_paths.items()},
+                       procedural=bool(args.procedural), trained=trained, weights=weights, ground_truths=n_gt, proposals=n_prop,
+                       proposals_with_a_refined_pose=n_ref, ms_per_frame_median_with_refine=float(np.median(ms[min(3, len(ms) - 1):])),
+                       variants={}, note="figures: no threshold is attached to these APs")
+            print(f"{args.frames} frames, {n_gt} ground truths, {n_prop} proposals, {n_ref} with a refined pose; "
+                  f"{rec['ms_per_frame_median_with_refine']:.1f} ms per frame (all categories, refinement included)")
+            r_iou, r_pose, _, _ = E.compute_degree_cm_mAP(refined, sampler.synset_names, None, deg, sh, iou, 0.1, True, device=dev)
+            for v, (a, b) in (("first_pass", (iou_aps, pose_aps)), ("refined", (r_iou, r_pose))):
+                print(f"--- {v}")
+                one = dict(iou_ap={}, pose_ap={})
+                _tables(a, b, sampler.synset_names, list(cat_paths), deg, sh, one)
+                rec["variants"][v] = one
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            old = {}
+            if os.path.exists(args.out):
+                with open(args.out) as fh:
+                    old = json.load(fh)
+            old["mesh_frames"] = rec
+            with open(args.out, "w") as fh:
+                json.dump(old, fh, indent=1)
+                fh.write("\n")
+            tmp.cleanup()
+            return
         rec = dict(device=torch.cuda.get_device_name(0), mode="mask-free: scene_frame per category on the whole depth image", frames=args.frames,
                    objects_per_frame=args.objects, scene_pairs=args.scene_pairs, thresh=args.thresh, max_proposals=args.max_proposals, seed=args.seed,
                    categories={c: len(p) for c, p in cat_paths.items()}, procedural=bool(args.procedural), trained=trained, weights=weights,
