@@ -1232,6 +1232,55 @@ int cppf_proposal_support(const int32_t* point_idxs, const uint32_t* surv_bits, 
 int cppf_box_support(const float* points, const uint8_t* point_masks, const float* centers, const float* axes, const float* half,
                      int64_t n_points, int n_props, int32_t* counts, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Scene training (csrc/scene_train.hip; additive, ABI version unchanged): what a training step on a whole labelled frame needs
+ * besides the encoders -- a pair draw that yields same-instance pairs, and the targets of utils/dataset.py:27-60,229-246 for many
+ * instances in one pass.  The reference trains on one object at a time, so the definitions are this project's;
+ * tests/scene_training_ref.py restates them in numpy.  Host side: cppf_amd/scene_training.py.  Neither call takes a workspace,
+ * allocates, synchronises with the host or uses atomics: both can be captured in a graph.
+ *
+ * The labelled cloud: inst device i32[n_points], the instance each point belongs to, -1 (or any value outside [0, n_inst)) =
+ * background.
+ *
+ * The stratified draw.  members device i32[M]: the points of the TARGET category's instances, grouped by instance, ascending within
+ *   a group; seg_off device i32[n_inst + 1] into members (an instance of another category has an empty segment); M = seg_off[n_inst]
+ *   is read on the device; members_capacity = the entries the members buffer holds (>= M; 0 with a null pointer when there is none).
+ *   idx device i32[n_pairs,2], 8-byte aligned.
+ *   Pair p: {w} = Philox-4x32-10({p, 0, 4, 0}, key = seed) -- stream 4; streams 0..3 are taken (the uniform pair draw, the mesh
+ *   statistics).  For p < n_pos_pairs and M > 0:  a = members[(w.x M) >> 32], k = inst[a], b = members[seg_off[k] + ((w.y L) >> 32)]
+ *   with L = seg_off[k+1] - seg_off[k].  Otherwise a = (w.x N) >> 32, b = (w.y N) >> 32, the uniform draw's rule.  a == b is kept.
+ *   A pair's draw depends on (seed, p) alone.  Lists that break the promises above (M above members_capacity, a member outside the cloud, a
+ *   label without a segment, offsets outside [0, M]) give that pair the uniform rule and never an out-of-bounds read.
+ *   CPPF_EINVAL: n_pairs outside 0..2^31-1, n_pos_pairs outside 0..n_pairs, and with n_pairs > 0: n_inst < 1, n_points outside
+ *   1..2^31-1, a null pointer (members aside while its capacity is 0), a misaligned idx.
+ *
+ * The targets.  points / normals device f32[n_points,3]; idx device i32[n_pairs,2]; table device f32[n_inst,12] = {centre, up axis,
+ *   right axis, scale target} per instance (the scale target, log(half extents) - log(scale_mean), is not read by the kernel: the
+ *   loss gathers it by pair_inst); flags device i32[n_inst]: bit 0 = the instance is of the target category, bit 1 = up_sym, bit 2 =
+ *   right_sym.  n_inst <= CPPF_SCENE_TRAIN_MAX_INSTANCES.  vote_range0 / vote_range1: the category's vote_range.
+ *   Outputs, a structure of arrays over the pairs: kind u8[P], pair_inst i32[P], low u8[P,4] (4-byte aligned), w_low f32[P,4]
+ *   (16-byte aligned), aux u8[P,2] (2-byte aligned); the head order is mu, nu, up, right.
+ *   - POSITIVE (kind 1, pair_inst k): both points carry the same label k in [0, n_inst) and bit 0 of flags[k] is set.  In fp32, no
+ *     contraction, dot products summed left to right: a = P_i - c, b = P_j - c, d = a - b, u = d / (|d| + 1e-7f), proj = a.u,
+ *     dist2o = |a - proj u|, th_up = acosf(clamp(u.up, -1, 1)), under up_sym min(th_up, acosf(clamp(-(u.up), -1, 1))), th_right
+ *     likewise with right_sym; n = N_i, negated when n.u < 0; aux = {n.up > 0, n.right > 0}.
+ *     Values {clamp(proj + v0, 0, 2 v0), clamp(dist2o, 0, v1), th_up, th_right} over the maxima {2 v0, v1, pi, pi}; with interval =
+ *     (float)(max / (bins - 1)) (fp64, rounded once):  x = value / interval, low = min(floor(x), bins - 2), w_low = 1 - (x - low):
+ *     weight w_low on bin low and 1 - w_low on bin low + 1.
+ *   - NEGATIVE (kind 0, pair_inst -1): every other pair, and a positive pair one of whose values is not finite.  low = {0, tr_bins -
+ *     2, 0, 0}, w_low = {1, 0, 1, 1}, aux = {0, 0}: all nu weight on the farthest bin.
+ *   - An index outside [0, n_points): kind 255, nothing is read for that pair, the other outputs as a negative pair's.
+ *   CPPF_EINVAL: n_inst outside 1..32, bins outside 2..256, a vote range that is not positive, n_pairs outside 0..2^31-1, and with
+ *   n_pairs > 0: n_points outside 1..2^31-1, a null pointer, a misaligned idx / low / w_low / aux.
+ * ------------------------------------------------------------------------------------------- */
+#define CPPF_SCENE_TRAIN_MAX_INSTANCES 32
+int cppf_sample_scene_pairs(const int32_t* members, int64_t members_capacity, const int32_t* seg_off, int n_inst, const int32_t* inst,
+                            int64_t n_points, int64_t n_pairs, int64_t n_pos_pairs, unsigned long long seed, int32_t* idx, void* stream);
+int cppf_scene_pair_targets(const float* points, const float* normals, const int32_t* inst, int64_t n_points, const int32_t* idx,
+                            int64_t n_pairs, const float* table, const int32_t* flags, int n_inst, double vote_range0,
+                            double vote_range1, int tr_bins, int rot_bins, uint8_t* kind, int32_t* pair_inst, uint8_t* low,
+                            float* w_low, uint8_t* aux, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
