@@ -225,7 +225,7 @@ def refine_poses(out, runner, cfg, n_pairs=100_000, seed=0, min_points=None, own
 
 
 def scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=5_000_000, seed=0, jitter=None, cloud=None, refine=None,
-                refine_kw=None, **kw):
+                refine_kw=None, segments=None, intra_frac=1.0, segment_cloud=None, **kw):
     """One depth frame with NO instance masks -> scene_poses' dict: zero_shot_frame's pre-processing (nocs/zero_shot.ipynb cells 3-6:
     the cloud de-duplicated at res, the sparse cloud at 4 res, SPRIN features on the dense cloud, frames.draw_pairs(seed, 0, ...) --
     whose uniforms feed the bin decode -- and the "indistinguishable" pair filter), then scene_poses with the bin-head encoder.
@@ -236,15 +236,28 @@ def scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=5_000_00
     refine (opt-in; None: nothing below runs and the dict has the keys and the bits it always had): a BatchPoseRunner with both
     encoders of cfg.category.  Every pose then gains `refined` (refine_poses: the proposal's dense points through the instance path)
     and the dict gains point_masks (device) and owner (scene_stage.voxel_owner's map of the dense cloud); refine_kw: refine_poses'
-    options (n_pairs, seed -- default: this frame's seed --, min_points, owner)."""
+    options (n_pairs, seed -- default: this frame's seed --, min_points, owner).
+    segments (opt-in; None: the uniform draw above, the same launches and the same bits as ever): segments.frame_segments' dict for
+    this frame.  The pairs are then drawn INSIDE segments (segments.segment_inputs replaces frame_inputs: the same clouds, features
+    and bin uniforms; the first round(intra_frac n_pairs) pairs join two points of one segment, the rest are uniform) and the dict
+    gains segment_ids, the segment of every point of pc (-1: none).  segment_cloud: segments.labelled_frame_cloud's tuple for this
+    frame when the caller has it (categories that share (res, knn) share it); `cloud` is not read then."""
     check_encoder(encoder, cfg)
     check_args(kw.get("max_proposals", 32), kw.get("thresh", 50), kw.get("margin", 10), kw.get("max_iters"))
     require_cuda()
-    hi, hi_nrm, ind, pc, nrm, feat, idx, (u_tr, u_rot) = frame_inputs(depth, intrinsics, point_encoder, cfg, n_pairs, seed, jitter, cloud)
+    seg_ids = None
+    if segments is None:
+        hi, hi_nrm, ind, pc, nrm, feat, idx, (u_tr, u_rot) = frame_inputs(depth, intrinsics, point_encoder, cfg, n_pairs, seed, jitter, cloud)
+    else:
+        from .segments import segment_inputs
+        hi, hi_nrm, ind, pc, nrm, feat, idx, (u_tr, u_rot), seg_ids = segment_inputs(depth, intrinsics, point_encoder, cfg, n_pairs, seed, segments,
+                                                                                     intra_frac, jitter=jitter, cloud=segment_cloud)
     if refine is not None:
         kw = dict(kw, keep_masks=True)
     out = scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, **kw)
     out.update(hi_pc=hi, hi_normals=hi_nrm, indices=ind, pc=pc, normals=nrm, feat=feat, idx=idx, n_pairs=int(idx.shape[0]))
+    if seg_ids is not None:
+        out["segment_ids"] = seg_ids
     if refine is not None:
         rkw = dict(refine_kw or {})
         rkw.setdefault("seed", seed)

@@ -1281,6 +1281,52 @@ int cppf_scene_pair_targets(const float* points, const float* normals, const int
                             double vote_range1, int tr_bins, int rot_bins, uint8_t* kind, int32_t* pair_inst, uint8_t* low,
                             float* w_low, uint8_t* aux, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Depth segments (csrc/segments.hip; additive, ABI version unchanged): what a depth frame says about its objects without any network
+ * -- connected components of the depth image under a depth-discontinuity rule, and a RANSAC plane fit to cut the support surface
+ * away first.  The reference has neither, so the definitions are this project's; tests/segments_ref.py restates them in numpy /
+ * scipy.  Host side: cppf_amd/segments.py.  Neither call takes a workspace: all scratch is a defined output.  Neither allocates or
+ * synchronises with the host; both use integer atomics only, so the same inputs give the same bits, and both can be captured in a
+ * graph.
+ *
+ * cppf_depth_segments.  depth device [H,W]: the int16 bits of the uint16 millimetres, compared as UNSIGNED; valid device u8[H,W] or
+ *   NULL.  Outputs, device: labels i32[H,W], comp_size i32[H,W], first i32[capacity], sizes i32[capacity], counts i32[4].
+ *   All in 32-bit integers:
+ *   - a pixel is LIVE when depth > 0 and (valid is NULL or valid[p] != 0);
+ *   - two 4-neighbours a, b are LINKED when both are live and |za - zb| <= tol_mm + (slope_permille * min(za, zb)) / 1000 (floor);
+ *   - a component is a connected component of that graph, its ROOT its smallest flat pixel index;
+ *   - comp_size[p] = the size of p's component for a live pixel, 0 for a dead one;
+ *   - a component is KEPT when size >= min_pixels and (max_pixels == 0 or size <= max_pixels); the S kept components are numbered
+ *     0..S-1 by ascending root; labels[p] = that number for the pixels of kept components, -1 everywhere else;
+ *   - first[s] = the root and sizes[s] = the size of kept component s; first[s] = -1 and sizes[s] = 0 for S <= s < capacity;
+ *   - counts = {S, components of any size, live pixels, 0}.
+ *   Overflow, S > capacity: counts and comp_size are as defined; the caller retries with a larger capacity.  (labels, first and
+ *   sizes are then not to be relied on; this implementation writes -1 / -1 / 0 everywhere.)
+ *   Every output is a function of the inputs alone: a root is a minimum and a number is a rank.
+ *   CPPF_EINVAL: H or W < 1, H * W > 2^24, tol_mm outside 0..65535, slope_permille outside 0..1000, min_pixels < 1, max_pixels < 0,
+ *   capacity outside 1..CPPF_SEGMENTS_MAX, a null pointer (valid aside).
+ *
+ * cppf_plane_ransac.  points device f32[n_points,3]; outputs, device: planes f32[n_hyp,4] (16-byte aligned), counts i32[n_hyp],
+ *   best i32[2].  Hypothesis h: {w} = Philox-4x32-10({h, 0, 5, 0}, key = seed) -- stream 5; streams 0..4 are taken.  i_k = (w.k
+ *   n_points) >> 32 for k = x, y, z name the points a, b, c.  In fp32, no contraction: e1 = b - a, e2 = c - a, n = e1 x e2 (each
+ *   component two products and one subtraction), l = sqrtf((n.x n.x + n.y n.y) + n.z n.z).  DEGENERATE when !(l > 1e-12f), when any
+ *   of the nine coordinates is not finite, or when the plane below is not finite (a cross product that overflowed).  Otherwise n = n /
+ *   l, d = -((n.x a.x + n.y a.y) + n.z a.z), and all four are negated when d < 0: the origin is on the non-negative side.  A
+ *   degenerate hypothesis has the plane {0, 0, 0, 0} and the count 0.
+ *   counts[h] = the points with fabsf(((n.x p.x + n.y p.y) + n.z p.z) + d) <= thresh; a point with a non-finite coordinate is no
+ *   inlier of any plane.  best = {the lowest h with the largest count among the hypotheses that are not degenerate, that count}, or
+ *   {-1, 0} when every hypothesis is degenerate.
+ *   CPPF_EINVAL: n_points outside 1..2^31-1, n_hyp outside 1..CPPF_PLANE_MAX_HYPOTHESES, a thresh that is not finite and >= 0, a
+ *   null pointer, a misaligned planes.
+ * ------------------------------------------------------------------------------------------- */
+#define CPPF_SEGMENTS_MAX 1024
+#define CPPF_PLANE_MAX_HYPOTHESES 1024
+int cppf_depth_segments(const int16_t* depth, const uint8_t* valid, int H, int W, int tol_mm, int slope_permille, int min_pixels,
+                        int max_pixels, int capacity, int32_t* labels, int32_t* comp_size, int32_t* first, int32_t* sizes,
+                        int32_t* counts, void* stream);
+int cppf_plane_ransac(const float* points, int64_t n_points, int n_hyp, float thresh, unsigned long long seed, float* planes,
+                      int32_t* counts, int32_t* best, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

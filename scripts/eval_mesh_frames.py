@@ -42,6 +42,14 @@ first pass's poses and the refined ones (a proposal without a refined pose keeps
 pass's in both), written to profiles/refine_eval.json (--out) under `mesh_frames`.  Figures, no threshold.
 
     python scripts/eval_mesh_frames.py --procedural --train-steps 3000 --train-pairs 200000 --frames 20 --objects 4 --mask-free --refine
+
+--mask-free --segments [--seg-planes N] [--seg-min-pixels M] [--seg-tol-mm T] [--seg-slope S] [--intra-frac F]: depth segments (DESIGN.md
+3.7j).  Every frame is segmented on the device first (cppf_amd.segments.frame_segments; --seg-planes 0, the default, suits rendered
+frames, which have no background) and each category's pairs are drawn inside the segments (scene_frame(segments=...)); the time per
+frame includes the segmentation.  Works with the plain --mask-free run and with --nms; the record gains `segments`, the options and
+the mean number of segments per frame, and goes to profiles/segments_eval.json unless --out says otherwise.  Figures, no threshold.
+
+    python scripts/eval_mesh_frames.py --procedural --weights bottle=... --weights can=... --weights camera=... --frames 20 --objects 4 --mask-free --segments
 """
 import argparse
 import json
@@ -123,6 +131,23 @@ def _mask_free_record(fr, preds):
     return rec
 
 
+def _segments(args, fr, log):
+    """--segments: scene_frame's keywords for one frame -- frame_segments with the flags' options -- or {} without the flag; log: the
+    segment counts so far"""
+    if not args.segments:
+        return {}
+    from cppf_amd.segments import frame_segments
+    seg = frame_segments(fr.depth_mm, fr.intrinsics, n_planes=args.seg_planes, min_pixels=args.seg_min_pixels, tol_mm=args.seg_tol_mm,
+                         slope_permille=args.seg_slope)
+    log.append(seg["n_segments"])
+    return dict(segments=seg, intra_frac=args.intra_frac)
+
+
+def _segments_record(args, log):
+    return dict(n_planes=args.seg_planes, min_pixels=args.seg_min_pixels, tol_mm=args.seg_tol_mm, slope_permille=args.seg_slope,
+                intra_frac=args.intra_frac, segments_per_frame_mean=float(np.mean(log)) if log else 0.0) if args.segments else None
+
+
 def _mask_free(args, sampler, encs, pencs, dev):
     """the frames through scene_frame per category -> (result records, ms per frame, proposals, ground truths); with --refine also the
     records with the refined poses in place of the first pass's and how many proposals have one (else None, 0)"""
@@ -139,9 +164,10 @@ def _mask_free(args, sampler, encs, pencs, dev):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         preds = []
+        seg_kw = _segments(args, fr, args.seg_log)
         for c in sampler.categories:
             out = scene_frame(fr.depth_mm, fr.intrinsics, encs[c], pencs[c], CATEGORIES[c], n_pairs=args.scene_pairs, seed=i,
-                              thresh=args.thresh, max_proposals=args.max_proposals, **({} if runner is None else dict(refine=runner)))
+                              thresh=args.thresh, max_proposals=args.max_proposals, **({} if runner is None else dict(refine=runner)), **seg_kw)
             for p in out["poses"]:
                 if ok(p):
                     preds.append((names.index(c), p, p["diff"]))
@@ -177,7 +203,7 @@ def _detections(args, sampler, encs, pencs, dev):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         res = frame_detections(fr.depth_mm, fr.intrinsics, nets, n_pairs=args.scene_pairs, seed=i, nms_thresh=args.nms,
-                               thresh=args.thresh, max_proposals=args.max_proposals)
+                               thresh=args.thresh, max_proposals=args.max_proposals, **_segments(args, fr, args.seg_log))
         ms.append((time.perf_counter() - t0) * 1e3)
         pooled = dict(no_nms=pool_detections(res["outs"], cats, None, nms_thresh=None), nms_per_category=res)
         if args.cross_category:
@@ -347,9 +373,17 @@ def main():
                     "their box")
     ap.add_argument("--tune-frames", type=int, default=0, help="--score agreement without --min-agreement: frames of a separate sampler "
                     "(seed + 1000) on which the bound is chosen")
+    ap.add_argument("--segments", action="store_true", help="--mask-free: segment every frame on the device first and draw the pairs inside "
+                    "the segments (DESIGN.md 3.7j)")
+    ap.add_argument("--seg-planes", type=int, default=0, help="--segments: planes removed before the labelling (0 suits rendered frames)")
+    ap.add_argument("--seg-min-pixels", type=int, default=200, help="--segments: the smallest component kept")
+    ap.add_argument("--seg-tol-mm", type=int, default=10, help="--segments: the link rule's constant term")
+    ap.add_argument("--seg-slope", type=int, default=10, help="--segments: the link rule's slope, per mille of the nearer depth")
+    ap.add_argument("--intra-frac", type=float, default=1.0, help="--segments: share of the pairs drawn inside one segment")
     ap.add_argument("--out", default=None, help="default profiles/mesh_frames_eval.json (profiles/scene_poses_eval.json with --mask-free, "
                     "profiles/scene_detections_eval.json with --nms, profiles/scene_verify_eval.json with --score agreement)")
     args = ap.parse_args()
+    args.seg_log = []
     verify_mode = args.score == "agreement" or args.min_agreement is not None or args.min_fill is not None
     if (args.cross_category or verify_mode) and args.nms is None:
         args.nms = 0.3
@@ -361,6 +395,10 @@ def main():
         sys.exit("--nms / --cross-category belong to --mask-free")
     if args.refine and (not args.mask_free or args.nms is not None or verify_mode):
         sys.exit("--refine belongs to the plain --mask-free run (no --nms, no --score agreement)")
+    if args.segments and (not args.mask_free or verify_mode):
+        sys.exit("--segments belongs to --mask-free (plain, --nms or --refine)")
+    if args.segments and args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "segments_eval.json")
     if args.refine and args.out is None:
         args.out = os.path.join(ROOT, "profiles", "refine_eval.json")
     if args.out is None:
@@ -407,6 +445,8 @@ def main():
                    procedural=bool(args.procedural), trained=trained, weights=weights, ground_truths=n_gt, proposals=n_prop,
                    ms_per_frame_median=float(np.median(ms[min(1, len(ms) - 1):])), variants={},
                    note="a first figure: no threshold is attached to these APs")
+        if args.segments:
+            rec["segments"] = _segments_record(args, args.seg_log)
         print(f"{args.frames} frames, {n_gt} ground truths, {n_prop} proposals; {rec['ms_per_frame_median']:.1f} ms per frame (all categories, NMS included)")
         for v, recs in results.items():
             iou_aps, pose_aps, _, _ = E.compute_degree_cm_mAP(recs, sampler.synset_names, None, deg, sh, iou, 0.1, True, device=dev)
@@ -458,6 +498,8 @@ def main():
                    categories={c: len(p) for c, p in cat_paths.items()}, procedural=bool(args.procedural), trained=trained, weights=weights,
                    ground_truths=n_gt, proposals=n_prop, ms_per_frame_median=float(np.median(ms[min(1, len(ms) - 1):])), iou_ap={}, pose_ap={},
                    note="a first figure: no threshold is attached to these APs")
+        if args.segments:
+            rec["segments"] = _segments_record(args, args.seg_log)
         print(f"{args.frames} frames, {n_gt} ground truths, {n_prop} proposals; {rec['ms_per_frame_median']:.1f} ms per frame (all categories)")
         _tables(iou_aps, pose_aps, sampler.synset_names, list(cat_paths), deg, sh, rec)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
