@@ -120,8 +120,8 @@ def frame_detections(depth, intrinsics, networks, n_pairs=5_000_000, seed=0, jit
     """One depth frame with no instance masks -> the detections of all categories (pool_detections' dict, plus outs: the categories'
     scene_frame dicts).
     networks: an ordered mapping name -> (point_encoder, encoder, cfg), modules on one HIP device, in either precision (what the
-    encoders are set to is what runs).  scene_frame runs once per category with the same `seed` (and jitter); the dense cloud and its
-    normals are computed once per distinct (cfg.res, cfg.knn) and shared (scene_frame's cloud=: the same bits as without sharing).
+    encoders are set to is what runs).  scene_frame runs once per category with the same `seed` (and jitter); the frame's SceneCloud
+    is computed once per distinct (cfg.res, cfg.knn) and shared (scene_frame's cloud=: the same bits as without sharing).
     The NMS runs on the networks' device.  score="agreement" / min_agreement / min_fill / min_within: pool_detections'; scene_frame
     then runs with verify=True (only then).  scene_kw: scene_poses' options (thresh, max_proposals, ...).
     refine (opt-in, default None: the same launches and the same bits as ever): a BatchPoseRunner that holds every category's two
@@ -129,25 +129,23 @@ def frame_detections(depth, intrinsics, networks, n_pairs=5_000_000, seed=0, jit
     voxel-owner map is computed once per shared cloud) and pooled with use_refined=True: box, RT and scales from `refined` where it
     exists, the first pass's under `coarse`; score, verification and filters stay the first pass's.  refine_kw: refine_poses' options.
     segments (opt-in, default None: the same launches and the same bits as ever): segments.frame_segments' dict for this frame, handed
-    to every category's scene_frame with intra_frac -- each network's pairs are drawn inside the same segments.  The labelled dense
-    cloud is computed once per distinct (res, knn), beside the shared cloud."""
+    to every category's scene_frame with intra_frac -- each network's pairs are drawn inside the same segments.  The shared cloud
+    is then the labelled one (segments.labelled_frame_cloud)."""
     from .scene_poses import frame_cloud, scene_frame
     if not networks:
         raise ValueError("frame_detections needs at least one category network")
-    names, outs, cfgs, clouds, owners, labelled, dev = [], [], [], {}, {}, {}, None
+    from .segments import labelled_frame_cloud
+    names, outs, cfgs, clouds, owners, dev = [], [], [], {}, {}, None
     if _needs_verify(score, min_agreement, min_fill, min_within):
         scene_kw = dict(scene_kw, verify=True)
     for name, (point_encoder, encoder, cfg) in networks.items():
         key = (float(cfg.res), int(cfg.knn))
-        if segments is not None and key not in labelled:
-            from .segments import labelled_frame_cloud
-            labelled[key] = labelled_frame_cloud(depth, intrinsics, cfg, segments, jitter)
-            clouds[key] = labelled[key][:2]                                   # (frame_cloud's pair, bit for bit)
         if key not in clouds:
-            clouds[key] = frame_cloud(depth, intrinsics, cfg, jitter)
+            clouds[key] = (frame_cloud(depth, intrinsics, cfg, jitter) if segments is None else
+                           labelled_frame_cloud(depth, intrinsics, cfg, segments, jitter))
         extra = {}
         if segments is not None:
-            extra = dict(segments=segments, intra_frac=intra_frac, segment_cloud=labelled[key])
+            extra = dict(segments=segments, intra_frac=intra_frac)
         if refine is not None:
             extra.update(refine=refine[name] if isinstance(refine, dict) else refine, refine_kw=dict(refine_kw or {}, owner=owners.get(key)))
         out = scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=n_pairs, seed=seed, jitter=jitter, cloud=clouds[key],

@@ -11,14 +11,11 @@ from .utils.util import backproject, estimate_normals, fibonacci_sphere, num_sph
 NOCS_INTRINSICS = np.array([[591.0125, 0, 322.525], [0, 590.16775, 244.11084], [0, 0, 1]])      # nocs/inference.py:98
 
 
-def instance_cloud(depth_dev, intrinsics, mask, cfg, jitter=None):
-    """nocs/inference.py:131-142 for one instance, on the device: (pc f32[N,3], normals f32[N,3]) device tensors.
-    depth_dev: the frame's depth (int16 bits of the uint16 millimetres, uploaded once per frame); mask: [H,W] bool/uint8 (numpy
-    or device); jitter: f32[n_masked,3] standard-normal draws for :134 (None: no augmentation; the reference draws
-    np.random.randn)."""
-    pts, _ = backproject(depth_dev, intrinsics, mask, return_device=True)          # :131  (fp64, masked pixels with depth > 0)
+def _cloud_and_pixels(depth_dev, intrinsics, mask, cfg, jitter=None):
+    """instance_cloud's pair and the flat pixel index (i32[N], row * W + col) of every kept point; all empty for an empty mask"""
+    pts, pix = backproject(depth_dev, intrinsics, mask, return_device=True)        # :131  (fp64, masked pixels with depth > 0)
     if pts.shape[0] == 0:                                                          # (an empty mask: nothing to de-duplicate or fit)
-        return pts.float(), pts.float()
+        return pts.float(), pts.float(), pix
     pc = pts / 1000.0                                                              # :132
     if jitter is not None:                                                         # :134
         j = torch.as_tensor(jitter, dtype=torch.float64, device=pc.device)[:pc.shape[0]]
@@ -26,7 +23,15 @@ def instance_cloud(depth_dev, intrinsics, mask, cfg, jitter=None):
     pc = torch.stack([-pc[:, 0], -pc[:, 1], pc[:, 2]], -1)                         # :136-137
     _, keep = sparse_quantize(pc.float(), return_index=True, quantization_size=cfg.res)   # :140 (ME.utils.sparse_quantize)
     pc = pc[keep].float().contiguous()                                             # :141
-    return pc, estimate_normals(pc, cfg.knn)                                       # :142
+    return pc, estimate_normals(pc, cfg.knn), pix[keep]                            # :142
+
+
+def instance_cloud(depth_dev, intrinsics, mask, cfg, jitter=None):
+    """nocs/inference.py:131-142 for one instance, on the device: (pc f32[N,3], normals f32[N,3]) device tensors.
+    depth_dev: the frame's depth (int16 bits of the uint16 millimetres, uploaded once per frame); mask: [H,W] bool/uint8 (numpy
+    or device); jitter: f32[n_masked,3] standard-normal draws for :134 (None: no augmentation; the reference draws
+    np.random.randn)."""
+    return _cloud_and_pixels(depth_dev, intrinsics, mask, cfg, jitter)[:2]
 
 
 def pair_seed(seed, i):

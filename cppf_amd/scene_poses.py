@@ -225,13 +225,13 @@ def refine_poses(out, runner, cfg, n_pairs=100_000, seed=0, min_points=None, own
 
 
 def scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=5_000_000, seed=0, jitter=None, cloud=None, refine=None,
-                refine_kw=None, segments=None, intra_frac=1.0, segment_cloud=None, **kw):
-    """One depth frame with NO instance masks -> scene_poses' dict: zero_shot_frame's pre-processing (nocs/zero_shot.ipynb cells 3-6:
-    the cloud de-duplicated at res, the sparse cloud at 4 res, SPRIN features on the dense cloud, frames.draw_pairs(seed, 0, ...) --
-    whose uniforms feed the bin decode -- and the "indistinguishable" pair filter), then scene_poses with the bin-head encoder.
+                refine_kw=None, segments=None, intra_frac=1.0, **kw):
+    """One depth frame with NO instance masks -> scene_poses' dict: scene_stage.frame_inputs (nocs/zero_shot.ipynb cells 3-6: the cloud
+    de-duplicated at res, the sparse cloud at 4 res, SPRIN features on the dense cloud, frames.draw_pairs(seed, 0, ...) -- whose
+    uniforms feed the bin decode -- and the "indistinguishable" pair filter), then scene_poses with the bin-head encoder.
     depth [H,W] in millimetres (numpy uint16 or device); jitter: f32[n_pixels,3] standard-normal draws (None: none); cloud: the
-    (hi, hi_nrm) pair frame_cloud returned for this depth, intrinsics, jitter and a config with the same (res, knn) -- it replaces the
-    back-projection, the de-duplication and the normals (None: they are computed here: the same bits); kw: scene_poses' options.
+    SceneCloud frame_cloud (with segments=: segments.labelled_frame_cloud) returned for this depth, intrinsics, jitter and a config
+    with the same (res, knn) (None: it is computed here: the same bits); kw: scene_poses' options.
     Adds hi_pc / hi_normals, indices, pc / normals, feat, idx, n_pairs (after the filter).
     refine (opt-in; None: nothing below runs and the dict has the keys and the bits it always had): a BatchPoseRunner with both
     encoders of cfg.category.  Every pose then gains `refined` (refine_poses: the proposal's dense points through the instance path)
@@ -240,8 +240,7 @@ def scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=5_000_00
     segments (opt-in; None: the uniform draw above, the same launches and the same bits as ever): segments.frame_segments' dict for
     this frame.  The pairs are then drawn INSIDE segments (segments.segment_inputs replaces frame_inputs: the same clouds, features
     and bin uniforms; the first round(intra_frac n_pairs) pairs join two points of one segment, the rest are uniform) and the dict
-    gains segment_ids, the segment of every point of pc (-1: none).  segment_cloud: segments.labelled_frame_cloud's tuple for this
-    frame when the caller has it (categories that share (res, knn) share it); `cloud` is not read then."""
+    gains segment_ids, the segment of every point of pc (-1: none).  A `cloud` without labels is then refused (ValueError)."""
     check_encoder(encoder, cfg)
     check_args(kw.get("max_proposals", 32), kw.get("thresh", 50), kw.get("margin", 10), kw.get("max_iters"))
     require_cuda()
@@ -251,7 +250,7 @@ def scene_frame(depth, intrinsics, encoder, point_encoder, cfg, n_pairs=5_000_00
     else:
         from .segments import segment_inputs
         hi, hi_nrm, ind, pc, nrm, feat, idx, (u_tr, u_rot), seg_ids = segment_inputs(depth, intrinsics, point_encoder, cfg, n_pairs, seed, segments,
-                                                                                     intra_frac, jitter=jitter, cloud=segment_cloud)
+                                                                                     intra_frac, jitter=jitter, cloud=cloud)
     if refine is not None:
         kw = dict(kw, keep_masks=True)
     out = scene_poses(encoder, pc, nrm, feat, idx, u_tr, u_rot, cfg, **kw)

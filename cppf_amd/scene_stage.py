@@ -1,7 +1,10 @@
 """The proposal stage of a scene with no instance masks, shared by the notebook's path (zero_shot.py, 9-wide regression head) and
 the mask-free path (scene_poses.py, bin head): the callers' input forms, the frame pre-processing of nocs/zero_shot.ipynb cells
 3-6, the scene vote with its proposals (cells 8-9) and cell 11's back-vote and segmentation of ALL proposals in one pass over the
-pair list (csrc/scene_multi.hip).  What the heads do with each proposal's kept pairs stays in the two modules."""
+pair list (csrc/scene_multi.hip).  What the heads do with each proposal's kept pairs stays in the two modules.  The pre-processing is
+scene_cloud (every caller's clouds, labelled or not) and cloud_inputs (features, draw, filter: frame_inputs' and segment_inputs' body)."""
+from typing import NamedTuple, Optional
+
 import numpy as np
 import torch
 
@@ -58,32 +61,55 @@ def sphere_tables(angle_tol, dev):
     return sph64, torch.from_numpy(s32).to(dev), torch.from_numpy(sph64).to(dev), sorted_y
 
 
-def frame_cloud(depth, intrinsics, cfg, jitter=None):
-    """the dense cloud of a whole frame and its normals, (hi f32[N,3], hi_nrm f32[N,3]) device tensors: frames.instance_cloud with
-    every pixel in the mask.  A function of (depth, intrinsics, cfg.res, cfg.knn, jitter) alone, so categories whose configs agree in
-    (res, knn) can share it (frame_inputs' cloud=)."""
-    from .frames import instance_cloud
+class SceneCloud(NamedTuple):
+    """scene_cloud's record, device tensors: the dense cloud (res), the sparse cloud (4 res), their labels (None: no label image)"""
+    hi: torch.Tensor                      # f32[M,3]
+    hi_nrm: torch.Tensor                  # f32[M,3]
+    hi_labels: Optional[torch.Tensor]     # i32[M]
+    ind: torch.Tensor                     # i64[N]
+    pc: torch.Tensor                      # f32[N,3] = hi[ind]
+    nrm: torch.Tensor                     # f32[N,3] = hi_nrm[ind]
+    labels: Optional[torch.Tensor]        # i32[N] = hi_labels[ind]
+
+
+def scene_cloud(depth, intrinsics, cfg, jitter=None, labels=None):
+    """Cell 3 on the device, a SceneCloud: frames._cloud_and_pixels with every pixel in the mask (jitter: f32[n_pixels,3] standard-normal
+    draws, None: none), then sparse_quantize at 4 res.  labels: an integer image [H,W] (tensor; -1 = none), read at each dense point's
+    own pixel.  A function of (depth, intrinsics, cfg.res, cfg.knn, jitter, labels) alone: categories whose configs agree in (res, knn)
+    can share it (cloud= of frame_inputs, segments.segment_inputs, scene_poses.scene_frame).  No valid pixel: ValueError."""
+    from .frames import _cloud_and_pixels
+    from .utils.util import sparse_quantize
     d = np.asarray(depth) if not isinstance(depth, torch.Tensor) else depth
-    return instance_cloud(depth, intrinsics, np.ones(tuple(d.shape), bool), cfg, jitter)
+    hi, hi_nrm, pix = _cloud_and_pixels(depth, intrinsics, np.ones(tuple(d.shape), bool), cfg, jitter)
+    if hi.shape[0] == 0:
+        raise ValueError("the depth frame has no valid pixels")
+    _, ind = sparse_quantize(hi, return_index=True, quantization_size=4 * cfg.res)
+    lab = None if labels is None else labels.to(hi.device).reshape(-1)[pix.long()].to(I32).contiguous()
+    return SceneCloud(hi, hi_nrm, lab, ind, hi[ind].contiguous(), hi_nrm[ind].contiguous(), None if lab is None else lab[ind].contiguous())
+
+
+def frame_cloud(depth, intrinsics, cfg, jitter=None):
+    """scene_cloud without labels"""
+    return scene_cloud(depth, intrinsics, cfg, jitter)
+
+
+def cloud_inputs(cloud, point_encoder, n_pairs, seed, pairs=None):
+    """Cells 5-7 on a SceneCloud: SPRIN features on the dense cloud (its own kNN) taken at `ind`, frames.draw_pairs(seed, 0, ...) and the
+    "indistinguishable" filter.  pairs: an i64[n_pairs,2] list to filter in place of the draw's (the bin uniforms stay the draw's).
+    Returns hi, hi_nrm, ind, pc, nrm, feat, idx, (u_tr, u_rot): the filter keeps a subset in order, the uniforms go through its positions."""
+    from .frames import draw_pairs
+    hi, hi_nrm, _, ind, pc, nrm, _ = cloud
+    with torch.no_grad():
+        feat = point_encoder(hi[None], hi_nrm[None])[0][ind].contiguous()                        # cell 7
+    idx, u = draw_pairs(seed, 0, int(n_pairs), pc.device, pc.shape[0])                            # cell 5
+    idx = idx if pairs is None else pairs
+    pos = kept_positions(pc, nrm, idx)                                                            # cell 6
+    return hi, hi_nrm, ind, pc, nrm, feat, idx[pos].contiguous(), (u[0][pos].contiguous(), u[1][pos].contiguous())
 
 
 def frame_inputs(depth, intrinsics, point_encoder, cfg, n_pairs, seed, jitter=None, cloud=None):
-    """Cells 3-6 on the device: the cloud de-duplicated at res (cloud=: frame_cloud's pair for this frame instead), the sparse cloud
-    at 4 res, SPRIN features on the dense cloud (its kNN is the dense cloud's), frames.draw_pairs(seed, 0, ...) and the
-    "indistinguishable" filter.  Returns hi, hi_nrm, ind, pc, nrm, feat, idx, (u_tr, u_rot): the filter keeps a subset in order,
-    and the draw's uniforms (which feed a bin decode) go through the same positions."""
-    from .frames import draw_pairs
-    from .utils.util import sparse_quantize
-    hi, hi_nrm = frame_cloud(depth, intrinsics, cfg, jitter) if cloud is None else cloud          # cell 3: res
-    if hi.shape[0] == 0:
-        raise ValueError("the depth frame has no valid pixels")
-    _, ind = sparse_quantize(hi, return_index=True, quantization_size=4 * cfg.res)                # cell 3: 4 res
-    pc, nrm = hi[ind].contiguous(), hi_nrm[ind].contiguous()
-    with torch.no_grad():
-        feat = point_encoder(hi[None], hi_nrm[None])[0][ind].contiguous()                        # cell 7 (kNN on the hi-res cloud)
-    idx, u = draw_pairs(seed, 0, int(n_pairs), pc.device, pc.shape[0])                            # cell 5
-    pos = kept_positions(pc, nrm, idx)                                                            # cell 6
-    return hi, hi_nrm, ind, pc, nrm, feat, idx[pos].contiguous(), (u[0][pos].contiguous(), u[1][pos].contiguous())
+    """Cells 3-6 on the device: scene_cloud (cloud=: the SceneCloud of this frame instead), then cloud_inputs with its own draw"""
+    return cloud_inputs(scene_cloud(depth, intrinsics, cfg, jitter) if cloud is None else cloud, point_encoder, n_pairs, seed)
 
 
 def vote_proposals(pc, outputs, idx32, cfg, num_rots, sigma, thresh, margin, max_proposals, max_iters):

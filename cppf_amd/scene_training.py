@@ -3,7 +3,7 @@ training.train and train_on_meshes show the networks one object at a time; scene
 whole-frame cloud whose SPRIN neighbourhoods cross object boundaries and whose pairs mostly join two different objects.  Here a step
 is one rendered multi-object frame (mesh_frames.MeshFrameSampler):
 
-  labelled_cloud       scene_stage.frame_cloud / frame_inputs' clouds bit for bit, plus the instance label of every point
+  labelled_cloud       scene_stage.scene_cloud with the frame's label image: the clouds and the instance label of every point
   sample_scene_pairs   cppf_sample_scene_pairs: a stratified draw -- the first n_pos_pairs pairs join two points of ONE instance of
                        the target category, the rest are uniform over the cloud
   scene_pair_targets   cppf_scene_pair_targets: training.targets for every instance of a frame in one pass, in compact form (the
@@ -18,7 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from ._torch_util import call, canon, require_cuda
-from .scene_stage import kept_positions, on_device, pairs_tensor
+from .scene_stage import kept_positions, on_device, pairs_tensor, scene_cloud
 
 F32, I32, U8 = torch.float32, torch.int32, torch.uint8
 MAX_INSTANCES = 32                        # include/cppf.h: CPPF_SCENE_TRAIN_MAX_INSTANCES
@@ -27,28 +27,10 @@ HEADS = ("mu", "nu", "up", "right")       # the order of low / w_low's columns
 
 
 def labelled_cloud(frame, cfg, jitter=None):
-    """A MeshFrame's clouds with labels: (hi f32[N_hi,3], hi_nrm, hi_inst i32[N_hi], ind i64[N], pc f32[N,3], nrm, inst i32[N]) on the
-    device.  hi, hi_nrm, ind, pc, nrm are scene_stage.frame_cloud's and frame_inputs' for (frame.depth_mm, frame.intrinsics, cfg,
-    jitter), bit for bit -- frames.instance_cloud's steps with every pixel in the mask, then sparse_quantize at 4 res; hi_inst is the
+    """A MeshFrame's clouds with labels: scene_stage.scene_cloud(frame.depth_mm, frame.intrinsics, cfg, jitter, frame.labels), the
+    SceneCloud (hi f32[N_hi,3], hi_nrm, hi_inst i32[N_hi], ind i64[N], pc f32[N,3], nrm, inst i32[N]) on the device; hi_inst is the
     label image read at each kept point's own pixel (-1 = background), inst = hi_inst[ind]."""
-    from .utils.util import backproject, estimate_normals, sparse_quantize
-    depth = frame.depth_mm
-    pts, pix = backproject(depth, frame.intrinsics, np.ones(tuple(depth.shape), bool), return_device=True)
-    if pts.shape[0] == 0:
-        raise ValueError("the depth frame has no valid pixels")
-    dev = pts.device
-    p = pts / 1000.0
-    if jitter is not None:
-        j = torch.as_tensor(jitter, dtype=torch.float64, device=dev)[:p.shape[0]]
-        p = p + torch.clamp(cfg.res / 4 * j, -cfg.res / 2, cfg.res / 2)
-    p = torch.stack([-p[:, 0], -p[:, 1], p[:, 2]], -1)
-    _, keep = sparse_quantize(p.float(), return_index=True, quantization_size=cfg.res)
-    hi = p[keep].float().contiguous()
-    hi_nrm = estimate_normals(hi, cfg.knn)
-    labels = frame.labels.to(dev).reshape(-1)
-    hi_inst = labels[pix[keep].long()].to(I32).contiguous()
-    _, ind = sparse_quantize(hi, return_index=True, quantization_size=4 * cfg.res)
-    return hi, hi_nrm, hi_inst, ind, hi[ind].contiguous(), hi_nrm[ind].contiguous(), hi_inst[ind].contiguous()
+    return scene_cloud(frame.depth_mm, frame.intrinsics, cfg, jitter, labels=frame.labels)
 
 
 def instance_table(centers, Rs, half_extents, is_target, cfg):

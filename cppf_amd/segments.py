@@ -8,14 +8,15 @@ points of a pair from ONE segment.  Everything here is opt-in.
   depth_segments   cppf_depth_segments: connected components of the depth image (4-neighbours, a depth-discontinuity rule), the
                    components of min_pixels..max_pixels pixels numbered by their smallest pixel index
   frame_segments   support_mask, then depth_segments: one dict a caller hands to scene_frame / frame_detections (segments=)
-  segment_inputs   scene_stage.frame_inputs with the pairs drawn inside segments
+  segment_inputs   scene_stage.cloud_inputs on labelled_frame_cloud's cloud (scene_stage.scene_cloud with the segments' label image),
+                   the pairs drawn inside segments (scene_training.sample_scene_pairs)
 
 The kernels are csrc/segments.hip's; the distance tests and compactions of support_mask are torch."""
 import numpy as np
 import torch
 
 from ._torch_util import call, canon, require_cuda
-from .scene_stage import kept_positions, on_device
+from .scene_stage import SceneCloud, cloud_inputs, on_device, scene_cloud
 
 F32, I32, I16, U8 = torch.float32, torch.int32, torch.int16, torch.uint8
 SEGMENTS_MAX = 1024                       # include/cppf.h: CPPF_SEGMENTS_MAX
@@ -188,13 +189,6 @@ def frame_segments(depth, intrinsics, n_planes=2, n_hyp=256, thresh=0.01, band=0
                 valid=valid, planes=planes, options=options)
 
 
-class _LabelledFrame:
-    """what scene_training.labelled_cloud reads of a frame"""
-
-    def __init__(self, depth_mm, intrinsics, labels):
-        self.depth_mm, self.intrinsics, self.labels = depth_mm, intrinsics, labels
-
-
 def segment_labels(segments):
     """the label image of `segments` (frame_segments' dict, or anything with labels [H,W] integers, device or numpy) as a tensor"""
     labels = segments["labels"] if isinstance(segments, dict) else segments
@@ -206,15 +200,13 @@ def segment_labels(segments):
 
 
 def labelled_frame_cloud(depth, intrinsics, cfg, segments, jitter=None):
-    """scene_training.labelled_cloud for (depth, segments' label image): (hi, hi_nrm, hi_inst, ind, pc, nrm, inst) -- the clouds are
-    scene_stage.frame_cloud's and frame_inputs' bit for bit, hi_inst the label image at each dense point's own pixel.  A function of
-    (depth, intrinsics, cfg.res, cfg.knn, jitter, labels): categories whose configs agree in (res, knn) can share it."""
-    from .scene_training import labelled_cloud
+    """scene_stage.scene_cloud with segments' label image (checked here to be an integer image of the depth frame's shape): the
+    SceneCloud (hi, hi_nrm, hi_labels, ind, pc, nrm, labels) that segment_inputs, scene_frame and frame_detections take as cloud="""
     labels = segment_labels(segments)
     d = np.asarray(depth) if not isinstance(depth, torch.Tensor) else depth
     if tuple(labels.shape) != tuple(d.shape):
         raise ValueError(f"segments: labels {tuple(labels.shape)} for a depth frame {tuple(d.shape)}")
-    return labelled_cloud(_LabelledFrame(depth, intrinsics, labels), cfg, jitter)
+    return scene_cloud(depth, intrinsics, cfg, jitter, labels=labels)
 
 
 def segment_members(inst, n_segments, min_points=8):
@@ -230,29 +222,25 @@ def segment_members(inst, n_segments, min_points=8):
 
 
 def segment_inputs(depth, intrinsics, point_encoder, cfg, n_pairs, seed, segments, intra_frac=1.0, min_points=8, jitter=None, cloud=None):
-    """scene_stage.frame_inputs with the pairs drawn inside segments.  Returns frame_inputs' tuple plus the per-point segment ids of
-    the sparse cloud: hi, hi_nrm, ind, pc, nrm, feat, idx, (u_tr, u_rot), inst.
-    The clouds, the features and the bin uniforms (frames.draw_pairs(seed, 0, ...)'s) are frame_inputs' bit for bit.  The pair list
-    is scene_training.sample_scene_pairs(members, seg_off, inst, n_pairs, round(intra_frac n_pairs), seed): the first round(intra_frac
-    n_pairs) pairs join two points of ONE segment, a segment drawn in proportion to its points; the rest are uniform over the cloud
-    (the scene draw's uniform rule on Philox stream 4 -- not draw_pairs' pairs).  members: the points of the segments with at least
-    min_points sparse points; when no segment qualifies every pair is uniform.  The "indistinguishable" filter runs as in
-    frame_inputs.  segments: frame_segments' dict; cloud: labelled_frame_cloud's tuple for this frame and a config with the same
-    (res, knn) (None: computed here)."""
-    from .frames import draw_pairs
+    """scene_stage.cloud_inputs on the labelled cloud with the pairs drawn inside segments.  Returns frame_inputs' tuple plus the
+    per-point segment ids of the sparse cloud: hi, hi_nrm, ind, pc, nrm, feat, idx, (u_tr, u_rot), inst.
+    The pair list is scene_training.sample_scene_pairs(members, seg_off, inst, n_pairs, round(intra_frac n_pairs), seed): the first
+    round(intra_frac n_pairs) pairs join two points of ONE segment, a segment drawn in proportion to its points; the rest are uniform
+    over the cloud (the scene draw's uniform rule on Philox stream 4 -- not draw_pairs' pairs).  members: the points of the segments
+    with at least min_points sparse points; when no segment qualifies every pair is uniform.  segments: frame_segments' dict; cloud:
+    labelled_frame_cloud's for this frame and a config with the same (res, knn) (None: computed here); one without labels is refused."""
     from .scene_training import sample_scene_pairs
     if not 0.0 <= float(intra_frac) <= 1.0:
         raise ValueError(f"intra_frac must be in [0, 1], got {intra_frac}")
-    hi, hi_nrm, _, ind, pc, nrm, inst = labelled_frame_cloud(depth, intrinsics, cfg, segments, jitter) if cloud is None else cloud
-    with torch.no_grad():
-        feat = point_encoder(hi[None], hi_nrm[None])[0][ind].contiguous()
-    P = int(n_pairs)
-    _, u = draw_pairs(seed, 0, P, pc.device, pc.shape[0])
+    if cloud is None:
+        cloud = labelled_frame_cloud(depth, intrinsics, cfg, segments, jitter)
+    if not isinstance(cloud, SceneCloud) or cloud.labels is None:
+        raise ValueError("segments= needs a cloud with labels (segments.labelled_frame_cloud's SceneCloud), got one without")
+    P, inst = int(n_pairs), cloud.labels
     n_seg = int(inst.max().item()) + 1 if inst.numel() else 0
     members, seg_off, _ = segment_members(inst, n_seg, min_points)
     idx = sample_scene_pairs(members, seg_off, inst, P, int(round(float(intra_frac) * P)), seed).long()
-    pos = kept_positions(pc, nrm, idx)
-    return hi, hi_nrm, ind, pc, nrm, feat, idx[pos].contiguous(), (u[0][pos].contiguous(), u[1][pos].contiguous()), inst
+    return (*cloud_inputs(cloud, point_encoder, P, seed, pairs=idx), inst)
 
 
 __all__ = ["plane_ransac", "support_mask", "depth_segments", "frame_segments", "segment_inputs", "labelled_frame_cloud", "segment_members",

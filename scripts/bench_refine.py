@@ -25,7 +25,7 @@ from cppf_amd import scene_poses, scene_stage, training       # noqa: E402
 from cppf_amd.batch import BatchPoseRunner                     # noqa: E402
 from cppf_amd.config import CATEGORIES                         # noqa: E402
 from cppf_amd.frames import NOCS_INTRINSICS                    # noqa: E402
-from cppf_amd.utils.util import read_depth_png, sparse_quantize  # noqa: E402
+from cppf_amd.utils.util import read_depth_png  # noqa: E402
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
@@ -135,8 +135,8 @@ def main():
     dev = torch.device("cuda", 0)
     depth = read_depth_png(os.path.join(GOLDEN, "demo_0000_depth.png"))
     cfg = CATEGORIES["bottle"]
-    hi, hi_nrm = scene_stage.frame_cloud(depth, NOCS_INTRINSICS, cfg)
-    _, ind = sparse_quantize(hi, return_index=True, quantization_size=4 * cfg.res)
+    cloud = scene_stage.frame_cloud(depth, NOCS_INTRINSICS, cfg)
+    hi, hi_nrm, ind = cloud.hi, cloud.hi_nrm, cloud.ind
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     owner = scene_stage.voxel_owner(hi, ind, 4 * cfg.res)

@@ -12,6 +12,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mesh_ref as MR  # noqa: E402
+import scene_cloud_ref as C  # noqa: E402
 import scene_poses_ref as SP  # noqa: E402
 import scene_training_ref as R  # noqa: E402
 from cppf_amd import mesh_frames as MF  # noqa: E402
@@ -245,7 +246,9 @@ def test_labelled_cloud_equals_frame_inputs(dev):
     cfg = CATEGORIES["bottle"]
     fr = MF.MeshFrameSampler(_meshes(), 2, device=dev, seed=3, z_range=(0.6, 1.0)).sample()
     assert len(fr.visible(200)) == 2
-    hi, hi_nrm, hi_inst, ind, pc, nrm, inst = ST.labelled_cloud(fr, cfg)
+    hi, hi_nrm, hi_inst, ind, pc, nrm, inst = got = ST.labelled_cloud(fr, cfg)
+    # the independent side: the single public calls composed in tests/scene_cloud_ref.py (labelled_cloud and frame_inputs share code)
+    C.assert_same_cloud(got, C.hand_scene_cloud(fr.depth_mm, fr.intrinsics, cfg, labels=fr.labels))
     penc, _ = training.new_encoders(cfg, dev, seed=0)
     want = scene_stage.frame_inputs(fr.depth_mm, fr.intrinsics, penc.eval(), cfg, 16, 0)
     for got, ref in zip((hi, hi_nrm, ind, pc, nrm), want[:5]):
@@ -264,6 +267,7 @@ def test_labelled_cloud_equals_frame_inputs(dev):
     hj = ST.labelled_cloud(fr, cfg, jitter=jit)
     wj = scene_stage.frame_cloud(fr.depth_mm, fr.intrinsics, cfg, jit)
     assert torch.equal(hj[0], wj[0]) and torch.equal(hj[1], wj[1]) and hj[2].shape[0] == hj[0].shape[0]
+    C.assert_same_cloud(hj, C.hand_scene_cloud(fr.depth_mm, fr.intrinsics, cfg, jit, fr.labels))
 
 
 STEPS = 40

@@ -10,6 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import mesh_frames_ref as FR  # noqa: E402
+import scene_cloud_ref as C  # noqa: E402
 import scene_poses_ref as S  # noqa: E402
 import scene_training_ref as TR  # noqa: E402
 import segments_ref as R  # noqa: E402
@@ -95,8 +96,14 @@ def test_segment_inputs_clouds_labels_and_draw(dev, frame, bottle):
     hi, hi_nrm, ind, pc, nrm, feat, idx, (u_tr, u_rot), inst = got
     for name, a, b in zip(("hi", "hi_nrm", "ind", "pc", "nrm", "feat"), got[:6], ref[:6]):
         assert _eq(a, b), name
+    # the independent side (segment_inputs and frame_inputs share code): the single public calls composed in tests/scene_cloud_ref.py
+    hand = C.hand_scene_cloud(fr.depth_mm, fr.intrinsics, cfg, labels=seg["labels"])
+    C.assert_same_cloud((hi, hi_nrm, None, ind, pc, nrm, inst), hand, ("hi", "hi_nrm", "ind", "pc", "nrm", "labels"))
+    with torch.no_grad():
+        assert _eq(feat, penc(hand[0][None], hand[1][None])[0][hand[3]])
     # labels: the label image at each point's own pixel (the point projects back into it), inst = hi_inst[ind]
     cloud = SG.labelled_frame_cloud(fr.depth_mm, fr.intrinsics, cfg, seg)
+    C.assert_same_cloud(cloud, hand)
     K_ = fr.intrinsics
     p = hi.double().cpu().numpy()
     col = np.rint(p[:, 0] / p[:, 2] * K_[0, 0] + K_[0, 2]).astype(np.int64)
