@@ -22,34 +22,6 @@ __host__ __device__ inline int vote_fixed_bits_of(int64_t chunk_pairs, int n_rot
     return kk;
 }
 
-
-static int v3_fixed_bits_bound(int64_t n_ppfs, int n_rots, int gx, int gy, int gz);
-static bool v3_eligible(int64_t n_ppfs, int n_rots, int gx, int gy, int gz);
-static size_t v3_workspace_bytes(int64_t n_ppfs, int gx, int gy, int gz);
-static size_t v3_workspace_bytes_dyn(int many_tiles, int64_t n_ppfs);
-static int v3_fused_tiles();
-// fixed-point bits of the largest weight in the tiled vote of this launch: exact for < 4 tiles; a LOWER bound for the binned path,
-// whose scale follows the queues' lengths (a finer quantum than reported, never a coarser one); 0: global fp32 atomics, no quantisation
-extern "C" int cppf_vote_fixed_point_bits(int64_t n_ppfs, int n_rots, int gx, int gy, int gz)
-{
-    if (n_rots < 1 || n_rots > CPPF_MAX_ROTS || gx < 1 || gy < 1 || gz < 1 || n_ppfs < 0) return -1;
-    return v3_eligible(n_ppfs, n_rots, gx, gy, gz) ? v3_fixed_bits_bound(n_ppfs, n_rots, gx, gy, gz) : 0;
-}
-
-extern "C" size_t cppf_vote_workspace_bytes(int64_t n_ppfs, int n_rots, int gx, int gy, int gz)
-{
-    if (n_rots < 1 || n_rots > CPPF_MAX_ROTS || gx < 1 || gy < 1 || gz < 1 || n_ppfs < 0) return 0;
-    // (global-atomics path and empty pair lists: the arg-max keys only -- but never less than the state a later tiled call on the same
-    // allocation would need to find zeroed, so that one allocation sized for its largest call is always valid)
-    if (!v3_eligible(n_ppfs, n_rots, gx, gy, gz)) return cppf_vote_workspace_init_bytes();
-    return v3_workspace_bytes(n_ppfs, gx, gy, gz);
-}
-// the *_dyn launch: room for the pair -> tile queues (n_ppfs pairs, every tile of the class) and one partial tile per workgroup
-extern "C" size_t cppf_vote_workspace_bytes_dyn_pairs(int many_tiles, int64_t n_ppfs)
-{
-    if (n_ppfs < 0) return 0;
-    return v3_workspace_bytes_dyn(many_tiles, n_ppfs);
-}
 // ----------------------------------------------------------------------------- centre vote
 // Reference: CUDA ppf_voting, models/voting.py:8-66.
 // LDS accumulation is 32-bit FIXED POINT: on gfx950 ds_add_f32 costs ~195 cycles per wave instruction (3 cycles/lane, any address
@@ -363,14 +335,13 @@ struct V3Plan { V3Tiling t; int wgs, slot; size_t pool_off, frames_off, part_off
 // pool: T queues of `cap` records (12 B) each -- every pair can visit every tile, and the HBM is there (288 GB) -- and, behind them,
 // one 48-byte FRAME per pair (V3_FRAME_BYTES: the bin kernel computes a pair's exact frame once, every tile's consumer loads it)
 #define V3_FRAME_BYTES 48
-static V3Plan v3_plan(int64_t n_ppfs, const V3Tiling& t, int gz, int wgs, int64_t cap, int64_t cells)
+static V3Plan v3_plan(int64_t n_ppfs, const V3Tiling& t, int gz, int wgs, int64_t cap)
 {
     V3Plan p;
     p.t = t; p.wgs = wgs; p.slot = v3_slot_words(t, gz); p.pool_cap = cap;
     // (the extra plane has a FIXED place and size -- the most cells a tiled grid can have -- whatever the grid: a workspace serves
     // calls with different grids, and the plane's "zero between launches" invariant must not depend on the previous layout)
     p.pool_off = VOTE_WS_PART + V3_HDR_BYTES + V3_PLANE_BYTES;
-    (void)cells;
     p.frames_off = p.pool_off + align_up((size_t)t.T * (size_t)cap * 12, 256);
     p.part_off = p.frames_off + (cap > 0 ? align_up((size_t)n_ppfs * V3_FRAME_BYTES, 256) : 0);
     p.total = p.part_off + (size_t)wgs * p.slot * sizeof(uint32_t);   // one partial tile per workgroup
@@ -1611,6 +1582,21 @@ extern "C" size_t cppf_vote_workspace_init_bytes(void)
     return VOTE_WS_PART + V3_HDR_BYTES + V3_PLANE_BYTES;
 }
 
+// Grids of fewer than this many tiles take the fused kernel (every tile's workgroups cull and screen the pair list themselves),
+// the others bin first.  CPPF_FUSED_MAX_TILES (development knob, read once) moves the boundary for by-value launches; the queues'
+// room in the workspace is always sized for the default boundary, so the knob can only be RAISED.
+#define V3_FUSED_TILES 4
+static int v3_fused_tiles()
+{
+    static int v = 0;
+    if (v == 0) {
+        const char* e = getenv("CPPF_FUSED_MAX_TILES");
+        const int w = e ? atoi(e) : V3_FUSED_TILES;
+        v = w < V3_FUSED_TILES ? V3_FUSED_TILES : (w > VOTE_MAX_TILES + 1 ? VOTE_MAX_TILES + 1 : w);
+    }
+    return v;
+}
+
 // host side of the binned path; returns a negative CPPF_E* / positive hipError_t, or 0
 static bool v3_eligible(int64_t n_ppfs, int n_rots, int gx, int gy, int gz)
 {
@@ -1633,7 +1619,7 @@ static int v3_fixed_bits_bound(int64_t n_ppfs, int n_rots, int gx, int gy, int g
 static size_t v3_workspace_bytes(int64_t n_ppfs, int gx, int gy, int gz)
 {
     const V3Tiling t = v3_tiling(gx, gy, gz);
-    return v3_plan(n_ppfs, t, gz, v3_wgs(n_ppfs, t.T), t.T < 4 ? 0 : n_ppfs, (int64_t)gx * gy * gz).total;   // (< 4 tiles: no queues)
+    return v3_plan(n_ppfs, t, gz, v3_wgs(n_ppfs, t.T), t.T < 4 ? 0 : n_ppfs).total;   // (< 4 tiles: no queues)
 }
 // tiles a *_dyn launch of class `many_tiles` serves: 0 -> 3 (the fused kernel), 1 -> 64 (any tiled grid), 4..64 -> that many (queues and
 // the reduce launch sized for them: a posed NOCS object needs 9-12 tiles, the C5 grid 16 -- a quarter of the 64-tile footprint)
@@ -1647,6 +1633,28 @@ static size_t v3_workspace_bytes_dyn(int many_tiles, int64_t n_ppfs)
     return VOTE_WS_PART + V3_HDR_BYTES + V3_PLANE_BYTES +
            (many_tiles ? align_up((size_t)t_cap * (size_t)n_ppfs * 12, 256) + align_up((size_t)n_ppfs * V3_FRAME_BYTES, 256) : 0) +
            (size_t)wgs * V3_TILE_FLOATS * sizeof(uint32_t);
+}
+// fixed-point bits of the largest weight in the tiled vote of this launch: exact for < 4 tiles; a LOWER bound for the binned path,
+// whose scale follows the queues' lengths (a finer quantum than reported, never a coarser one); 0: global fp32 atomics, no quantisation
+extern "C" int cppf_vote_fixed_point_bits(int64_t n_ppfs, int n_rots, int gx, int gy, int gz)
+{
+    if (n_rots < 1 || n_rots > CPPF_MAX_ROTS || gx < 1 || gy < 1 || gz < 1 || n_ppfs < 0) return -1;
+    return v3_eligible(n_ppfs, n_rots, gx, gy, gz) ? v3_fixed_bits_bound(n_ppfs, n_rots, gx, gy, gz) : 0;
+}
+
+extern "C" size_t cppf_vote_workspace_bytes(int64_t n_ppfs, int n_rots, int gx, int gy, int gz)
+{
+    if (n_rots < 1 || n_rots > CPPF_MAX_ROTS || gx < 1 || gy < 1 || gz < 1 || n_ppfs < 0) return 0;
+    // (global-atomics path and empty pair lists: the arg-max keys only -- but never less than the state a later tiled call on the same
+    // allocation would need to find zeroed, so that one allocation sized for its largest call is always valid)
+    if (!v3_eligible(n_ppfs, n_rots, gx, gy, gz)) return cppf_vote_workspace_init_bytes();
+    return v3_workspace_bytes(n_ppfs, gx, gy, gz);
+}
+// the *_dyn launch: room for the pair -> tile queues (n_ppfs pairs, every tile of the class) and one partial tile per workgroup
+extern "C" size_t cppf_vote_workspace_bytes_dyn_pairs(int many_tiles, int64_t n_ppfs)
+{
+    if (n_ppfs < 0) return 0;
+    return v3_workspace_bytes_dyn(many_tiles, n_ppfs);
 }
 // What a by-value launch will do for this problem (tests, tools): out = {path, T, tx, ty, ntx, nty, hx, hy, workgroups, bits};
 // path 0: global fp32 atomics (> 64 tiles), 2: fused kernel (< 4 tiles), 3: binned; (1 was round 2's kernels, gone); for n_rots > 72
@@ -1666,31 +1674,79 @@ extern "C" int cppf_vote_plan_query(int64_t n_ppfs, int n_rots, int gx, int gy, 
     return 0;   // path 0: everything else stays 0
 }
 
-// what cppf_vote_grid_raw adds to a vote: the exact integer image of the grid, its quantum, and bits fixed by the caller
-struct VoteExtras { long long* grid_raw; float* quantum_out; int fixed_bits; };
-
-// Grids of fewer than this many tiles take the fused kernel (every tile's workgroups cull and screen the pair list themselves),
-// the others bin first.  CPPF_FUSED_MAX_TILES (development knob, read once) moves the boundary for by-value launches; the queues'
-// room in the workspace is always sized for the default boundary, so the knob can only be RAISED.
-#define V3_FUSED_TILES 4
-static int v3_fused_tiles()
+// ---- the host side: every entry point states its vote as one VoteRequest per object and one VoteCall, vote_check decides what
+// becomes of a request, v3_prepare / v3_launch / vote_impl act on it
+// One object's vote.  The first eleven members are what every entry point has; the rest is zero unless the entry point sets it.
+struct VoteRequest {
+    const float *points, *outputs, *probs;                  // (probs may be null: all ones)
+    const void* point_idxs; int idx_is_i64;
+    const float* corner; float res;
+    int64_t n_points, n_ppfs;
+    void* workspace; size_t workspace_bytes;
+    float* grid; int gx, gy, gz;                            // (grid may be null when grid_raw is not)
+    long long* out_idx; float* out_val;                     // both null: no arg-max is wanted
+    // shape_dev != null: gx, gy, gz are 1 and n_points, grid_cap are CAPACITIES (grid_cap = cells of grid); the real values come from
+    // the device record, for a grid of the tile class many_tiles (v3_dyn_tcap).  Only the tiled path exists in that mode.
+    const int32_t* shape_dev; int64_t grid_cap; int many_tiles;
+    // what cppf_vote_grid_raw adds to a vote: the exact integer image of the grid, its quantum, and bits fixed by the caller
+    long long* grid_raw; float* quantum_out; int fixed_bits;
+};
+static void request_dynamic(VoteRequest& r, const int32_t* shape_dev, int64_t grid_cap, int many_tiles)
 {
-    static int v = 0;
-    if (v == 0) {
-        const char* e = getenv("CPPF_FUSED_MAX_TILES");
-        const int w = e ? atoi(e) : V3_FUSED_TILES;
-        v = w < V3_FUSED_TILES ? V3_FUSED_TILES : (w > VOTE_MAX_TILES + 1 ? VOTE_MAX_TILES + 1 : w);
+    r.shape_dev = shape_dev; r.grid_cap = grid_cap; r.many_tiles = many_tiles;
+    r.gx = r.gy = r.gz = 1;
+}
+static VoteRequest request_of(const CppfVoteItem& it)
+{
+    VoteRequest r = {it.points, it.outputs, it.probs, it.point_idxs, it.idx_is_i64, it.corner, it.res, it.n_points, it.n_ppfs,
+                     it.workspace, it.workspace_bytes, it.grid, it.gx, it.gy, it.gz, it.out_idx, it.out_val};
+    if (it.shape_dev) request_dynamic(r, it.shape_dev, it.grid_capacity, it.many_tiles);
+    return r;
+}
+
+// What a call shares across its objects.  The entry points' `accumulate` / `flags` argument is a flags word (include/cppf.h): bit 0 =
+// add to the grid, CPPF_VOTE_WORKGROUPS(n) in bits 8..16 = launch at most n vote workgroups (a scheduling hint for callers that keep
+// several instances in flight; 0 = one per CU); flags_ok: no other bit was set.
+struct VoteCall { int n_rots, adaptive, accumulate, wg_cap; bool flags_ok; hipStream_t st; };
+static VoteCall vote_call(int n_rots, int adaptive, int flags, void* stream)
+{
+    return {n_rots, adaptive, flags & 1, (flags >> 8) & 0x1ff, (flags & ~(1 | (0x1ff << 8))) == 0, (hipStream_t)stream};
+}
+
+// Every argument and workspace check of a vote, in the order a caller sees them: the refusal (a negative CPPF_E*), or 0 with the path
+// the request takes and the workspace bytes that path needs (both are also set when the workspace is what is refused).
+enum VotePath { VOTE_TILED_DYN, VOTE_TILED, VOTE_EMPTY_IMAGE, VOTE_GLOBAL };
+static int vote_check(const VoteRequest& r, const VoteCall& c, VotePath* path, size_t* need)
+{
+    const bool image = r.grid_raw != nullptr;
+    if (!c.flags_ok) return CPPF_EINVAL;
+    if (c.wg_cap != 0 && image) return CPPF_EINVAL;   // (integer images fix their bits from the default plan: no hint there)
+    if (!r.points || (!r.grid && !image) || !r.corner) return CPPF_EINVAL;
+    if (r.n_ppfs > 0 && (!r.outputs || !r.point_idxs)) return CPPF_EINVAL;
+    if (c.n_rots < 1 || c.n_rots > CPPF_MAX_ROTS || r.gx < 1 || r.gy < 1 || r.gz < 1 || r.n_ppfs < 0 || r.n_points < 1) return CPPF_EINVAL;
+    if ((int64_t)r.gx * r.gy * r.gz > 0x7fffffffll) return CPPF_EINVAL;
+    if (r.shape_dev) {
+        if (r.n_ppfs < 1 || r.n_ppfs > 0xffffffffll || r.grid_cap < 1 || r.grid_cap > 0x7fffffffll) return CPPF_EINVAL;
+        *path = VOTE_TILED_DYN; *need = v3_workspace_bytes_dyn(r.many_tiles, r.n_ppfs);
+    } else if (v3_eligible(r.n_ppfs, c.n_rots, r.gx, r.gy, r.gz)) {
+        *path = VOTE_TILED; *need = v3_workspace_bytes(r.n_ppfs, r.gx, r.gy, r.gz);
+    } else if (image) {
+        if (r.n_ppfs > 0) return CPPF_EUNSUPPORTED;   // the integer image exists on the tiled integer path only (<= 64 tiles)
+        *path = VOTE_EMPTY_IMAGE; *need = 0;
+    } else {
+        *path = VOTE_GLOBAL; *need = 256;             // no pairs, or a grid beyond 64 tiles: the arg-max keys only
     }
-    return v;
+    if (*need > 0 && (!r.workspace || r.workspace_bytes < *need)) return CPPF_EWORKSPACE;
+    // (no integer image in the dynamic mode; a grid of the class has at most that many cells)
+    if (r.shape_dev && (image || r.grid_cap > (int64_t)v3_dyn_tcap(r.many_tiles) * V3_TILE_FLOATS)) return CPPF_EINVAL;
+    return 0;
 }
 
 struct V3Launch { V3Args A; int red_blocks, bps; };
 
-// the by-value arguments of the three kernels for one object: plan, workspace layout, fixed-point bits (see the comment on widths below)
-static int v3_prepare(V3Launch& Lc, const float* points, const float* outputs, const float* probs, const void* point_idxs, int idx_is_i64,
-                      float* grid_obj, const float* corner, float res, int64_t n_points, int64_t n_ppfs, int n_rots, int gx, int gy,
-                      int gz, int adaptive, int accumulate, bool want_argmax, long long* out_idx, float* out_val, void* workspace,
-                      const int32_t* shape_dev, int64_t grid_cap, int many_tiles, const VoteExtras* ex, int wg_cap, int wg_floor = V3_BITS_WGS)
+// the by-value arguments of the three kernels for one object that passed vote_check on a tiled path: plan, workspace layout, fixed-point
+// bits (see the comment on widths below)
+static void v3_prepare(V3Launch& Lc, const VoteRequest& r, const VoteCall& c)
 {
     // Workgroups of the vote launch.  One per CU is the fastest launch on an idle chip, but every workgroup pays for its tile whatever
     // it deposits -- zeroed, dumped (113 KB) and read back by the reduce kernel: 27 of the 72 MB a C2 call moves -- so a caller that
@@ -1698,44 +1754,43 @@ static int v3_prepare(V3Launch& Lc, const float* points, const float* outputs, c
     // streams (profiles/r4_vote_workgroups.txt: 128 instead of 256 at C2, three instances in flight: +5 % pairs/s, the instance alone
     // 7 % slower).  The hint never goes below 64 or the number of tiles; chunking follows it, the grid does NOT change with it: the
     // fixed-point scale of the fused vote is that of a 64-wide launch whatever the width (v3_fused_bits_pairs).
-    const int wgs_max = wg_cap > 0 ? (wg_cap < wg_floor ? wg_floor : (wg_cap > V3_WGS ? V3_WGS : wg_cap)) : V3_WGS;
-    char* ws = static_cast<char*>(workspace);
+    const int wgs_max = c.wg_cap > 0 ? (c.wg_cap < V3_BITS_WGS ? V3_BITS_WGS : (c.wg_cap > V3_WGS ? V3_WGS : c.wg_cap)) : V3_WGS;
+    char* ws = static_cast<char*>(r.workspace);
+    const int64_t n_ppfs = r.n_ppfs;
     V3Args& A = Lc.A;
     A = V3Args{};
-    if (ex) { A.grid_raw = ex->grid_raw; A.quantum_out = ex->quantum_out; A.kk_force = ex->fixed_bits; }
-    A.points = points; A.outputs = outputs; A.probs = probs; A.point_idxs = point_idxs; A.idx64 = idx_is_i64;
-    A.corner = corner; A.res = res; A.n_ppfs = n_ppfs; A.n_points = n_points; A.n_rots = n_rots; A.adaptive = adaptive;
-    A.gx = gx; A.gy = gy; A.gz = gz; A.shape = shape_dev; A.grid_cap = grid_cap;
+    A.grid_raw = r.grid_raw; A.quantum_out = r.quantum_out; A.kk_force = r.fixed_bits;
+    A.points = r.points; A.outputs = r.outputs; A.probs = r.probs; A.point_idxs = r.point_idxs; A.idx64 = r.idx_is_i64;
+    A.corner = r.corner; A.res = r.res; A.n_ppfs = n_ppfs; A.n_points = r.n_points; A.n_rots = c.n_rots; A.adaptive = c.adaptive;
+    A.gx = r.gx; A.gy = r.gy; A.gz = r.gz; A.shape = r.shape_dev; A.grid_cap = r.grid_cap;
     A.hdr = reinterpret_cast<V3Hdr*>(ws + VOTE_WS_PART);
     A.packed = reinterpret_cast<unsigned long long*>(ws);
-    A.grid = grid_obj; A.accumulate = accumulate;
-    A.out_idx = want_argmax ? out_idx : nullptr; A.out_val = want_argmax ? out_val : nullptr;
-    const bool wide = n_rots > VOTE_WIN;
-    A.tab_entries = wide ? 0 : tri(n_rots);
+    A.grid = r.grid; A.accumulate = c.accumulate;
+    A.out_idx = r.out_idx; A.out_val = r.out_val;
+    A.tab_entries = c.n_rots > VOTE_WIN ? 0 : tri(c.n_rots);
     A.pool_cap = n_ppfs;
     A.plane = reinterpret_cast<unsigned long long*>(ws + VOTE_WS_PART + V3_HDR_BYTES);
-    if (shape_dev) {
+    if (r.shape_dev) {
+        const int many_tiles = r.many_tiles;
         A.t_cap = v3_dyn_tcap(many_tiles);
         A.wgs = wgs_max;
         A.fused = many_tiles ? 0 : 1;
-        if (ex && ex->grid_raw) return CPPF_EINVAL;
-        if (grid_cap > (int64_t)A.t_cap * V3_TILE_FLOATS) return CPPF_EINVAL;   // (a grid of the class has at most that many cells)
         A.pool = reinterpret_cast<uint32_t*>(ws + VOTE_WS_PART + V3_HDR_BYTES + V3_PLANE_BYTES);
         A.frames = reinterpret_cast<float4*>(A.pool + (many_tiles ? align_up((size_t)A.t_cap * (size_t)n_ppfs * 12, 256) / 4 : 0));
         A.partials = reinterpret_cast<uint32_t*>(A.frames) + (many_tiles ? align_up((size_t)n_ppfs * V3_FRAME_BYTES, 256) / 4 : 0);
         const int bps = ((V3_TILE_FLOATS + RED_CELLS - 1) / RED_CELLS + RED_FANIN - 1) / RED_FANIN * RED_FANIN;
         Lc.red_blocks = A.t_cap * bps;
     } else {
-        A.t = v3_tiling(gx, gy, gz);
+        A.t = v3_tiling(r.gx, r.gy, r.gz);
         A.wgs = v3_wgs(n_ppfs, A.t.T);
         if (A.wgs > wgs_max) A.wgs = wgs_max > A.t.T ? wgs_max : A.t.T;
         A.fused = A.t.T < v3_fused_tiles() ? 1 : 0;
         if (A.fused) {   // static chunks: the same number for every tile
             A.wgs = (A.wgs / A.t.T) * A.t.T;
-            A.kk = v3_bits((unsigned)v3_fused_bits_pairs(n_ppfs, A.wgs / A.t.T, A.t.T), n_rots);
+            A.kk = v3_bits((unsigned)v3_fused_bits_pairs(n_ppfs, A.wgs / A.t.T, A.t.T), c.n_rots);
         }
         A.t_cap = A.t.T;
-        const V3Plan pl = v3_plan(n_ppfs, A.t, gz, v3_wgs(n_ppfs, A.t.T), A.fused ? 0 : n_ppfs, (int64_t)gx * gy * gz);
+        const V3Plan pl = v3_plan(n_ppfs, A.t, r.gz, v3_wgs(n_ppfs, A.t.T), A.fused ? 0 : n_ppfs);
         A.pool = reinterpret_cast<uint32_t*>(ws + pl.pool_off);
         A.frames = reinterpret_cast<float4*>(ws + pl.frames_off);
         A.partials = reinterpret_cast<uint32_t*>(ws + pl.part_off);
@@ -1743,7 +1798,6 @@ static int v3_prepare(V3Launch& Lc, const float* points, const float* outputs, c
         Lc.red_blocks = A.t.T * bps;
     }
     Lc.bps = Lc.red_blocks / A.t_cap;
-    return 0;
 }
 
 static size_t v3_vote_lds(const V3Args& A) { return V3_LDS_HEAD + (size_t)(A.tab_entries + 2) * sizeof(float2) + (size_t)V3_TILE_FLOATS * sizeof(float); }
@@ -1771,47 +1825,49 @@ static size_t v3_bin_geometry(V3Args& A, dim3& bin_grid)
     return (size_t)V3_STAGE * 16 + VOTE_BELOW_N * 16 + 2 * VOTE_MAX_TILES * 4 + 64 + (V3_BIN_THREADS / 64) * (V3_IRING * 2 + (64 * V3_BIN_SR + 64) * 4);
 }
 
-static int v3_launch(const float* points, const float* outputs, const float* probs, const void* point_idxs, int idx_is_i64,
-                     float* grid_obj, const float* corner, float res, int64_t n_points, int64_t n_ppfs, int n_rots, int gx, int gy,
-                     int gz, int adaptive, int accumulate, bool want_argmax, long long* out_idx, float* out_val, void* workspace,
-                     hipStream_t st, const int32_t* shape_dev, int64_t grid_cap, int many_tiles, const VoteExtras* ex = nullptr,
-                     int wg_cap = 0)
+// the kernels of one pass, by what the launch is: WIDE = a window of more than 72 rotations, fused = no queues
+static int v3_launch_bin(const V3Args& A, bool wide, const dim3& bin_grid, size_t lds_bin, hipStream_t st)
+{
+    if (wide) hipLaunchKernelGGL(v3_bin_kernel<true>, bin_grid, dim3(V3_BIN_THREADS), lds_bin, st, A);
+    else hipLaunchKernelGGL(v3_bin_kernel<false>, bin_grid, dim3(V3_BIN_THREADS), lds_bin, st, A);
+    CPPF_CHECK_LAUNCH();
+    return 0;
+}
+static int v3_launch_vote(const V3Args& A, bool wide, size_t lds_vote, hipStream_t st)
+{
+    const dim3 grid((unsigned)A.wgs), block(V3_THREADS);
+    if (A.fused && wide) hipLaunchKernelGGL((v3_vote_kernel<true, true>), grid, block, lds_vote, st, A);
+    else if (A.fused) hipLaunchKernelGGL((v3_vote_kernel<true, false>), grid, block, lds_vote, st, A);
+    else if (wide) hipLaunchKernelGGL((v3_vote_kernel<false, true>), grid, block, lds_vote, st, A);
+    else hipLaunchKernelGGL((v3_vote_kernel<false, false>), grid, block, lds_vote, st, A);
+    CPPF_CHECK_LAUNCH();
+    return 0;
+}
+
+static int v3_launch(const VoteRequest& r, const VoteCall& c)
 {
     V3Launch Lc;
-    const int rc = v3_prepare(Lc, points, outputs, probs, point_idxs, idx_is_i64, grid_obj, corner, res, n_points, n_ppfs, n_rots, gx, gy, gz,
-                              adaptive, accumulate, want_argmax, out_idx, out_val, workspace, shape_dev, grid_cap, many_tiles, ex, wg_cap);
-    if (rc != 0) return rc;
+    v3_prepare(Lc, r, c);
     V3Args& A = Lc.A;
-    const int red_blocks = Lc.red_blocks;
-    const bool wide = n_rots > VOTE_WIN;
+    const bool wide = c.n_rots > VOTE_WIN;
     v3_set_attrs();
     const size_t lds_vote = v3_vote_lds(A);
     dim3 bin_grid;
     const size_t lds_bin = v3_bin_geometry(A, bin_grid);
-    const int bps = Lc.bps;
     // (two workgroups of 16 waves fill a CU: at most one round of blocks, each looping over its items)
-    const dim3 red_grid((unsigned)(red_blocks < 2 * V3_WGS ? red_blocks : 2 * V3_WGS));
+    const dim3 red_grid((unsigned)(Lc.red_blocks < 2 * V3_WGS ? Lc.red_blocks : 2 * V3_WGS));
     // n_rots <= 72: one pass.  More (a reference knob, nocs/inference.py:39 --num_rots): pass w votes rotations [72 w, 72 w + 72) of
     // every pair with the WIDE kernels and ADDS to the grid of the passes before it; the arg-max the last pass reports is the
     // arg-max of the whole vote (a pass that gives up makes the call's report -1 / NaN / quantum 0: sticky, see v3_reduce_body).
     // Integer images (grid_raw) need one scale for all passes: fixed here unless the caller fixed it.
-    if (wide && A.grid_raw && !A.kk_force) A.kk_force = v3_fixed_bits_bound(n_ppfs, n_rots, gx, gy, gz);
-    for (int wb = 0; wb < n_rots; wb += VOTE_WIN) {
+    if (wide && A.grid_raw && !A.kk_force) A.kk_force = v3_fixed_bits_bound(r.n_ppfs, c.n_rots, r.gx, r.gy, r.gz);
+    for (int wb = 0; wb < c.n_rots; wb += VOTE_WIN) {
         A.win_base = wb;
         if (wb > 0) A.accumulate = 1;
-        if (A.fused) {
-            if (wide) hipLaunchKernelGGL((v3_vote_kernel<true, true>), dim3((unsigned)A.wgs), dim3(V3_THREADS), lds_vote, st, A);
-            else hipLaunchKernelGGL((v3_vote_kernel<true, false>), dim3((unsigned)A.wgs), dim3(V3_THREADS), lds_vote, st, A);
-            CPPF_CHECK_LAUNCH();
-        } else {
-            if (wide) hipLaunchKernelGGL(v3_bin_kernel<true>, bin_grid, dim3(V3_BIN_THREADS), lds_bin, st, A);
-            else hipLaunchKernelGGL(v3_bin_kernel<false>, bin_grid, dim3(V3_BIN_THREADS), lds_bin, st, A);
-            CPPF_CHECK_LAUNCH();
-            if (wide) hipLaunchKernelGGL((v3_vote_kernel<false, true>), dim3((unsigned)A.wgs), dim3(V3_THREADS), lds_vote, st, A);
-            else hipLaunchKernelGGL((v3_vote_kernel<false, false>), dim3((unsigned)A.wgs), dim3(V3_THREADS), lds_vote, st, A);
-            CPPF_CHECK_LAUNCH();
-        }
-        hipLaunchKernelGGL(v3_reduce_kernel, red_grid, dim3(64 * RED_GROUPS), 0, st, A, bps);
+        int rc = A.fused ? 0 : v3_launch_bin(A, wide, bin_grid, lds_bin, c.st);
+        if (rc == 0) rc = v3_launch_vote(A, wide, lds_vote, c.st);
+        if (rc != 0) return rc;
+        hipLaunchKernelGGL(v3_reduce_kernel, red_grid, dim3(64 * RED_GROUPS), 0, c.st, A, Lc.bps);
         CPPF_CHECK_LAUNCH();
     }
     return 0;
@@ -1861,68 +1917,43 @@ __global__ __launch_bounds__(256) void vote_global_kernel(const float* __restric
     }
 }
 
-// shape_dev != null: gx, gy, gz, n_points are CAPACITIES (gx*gy*gz = cells of grid_obj) and the real values come from the
-// device record; only the tiled path exists in that mode.
-static int vote_impl(const float* points, const float* outputs, const float* probs, const void* point_idxs, int idx_is_i64,
-                     float* grid_obj, const float* corner, float res, int64_t n_points, int64_t n_ppfs, int n_rots,
-                     int gx, int gy, int gz, int adaptive, int accumulate, bool want_argmax, long long* out_idx, float* out_val,
-                     void* workspace, size_t workspace_bytes, hipStream_t st, const int32_t* shape_dev = nullptr,
-                     int64_t grid_cap = 0, int many_tiles = 0, const VoteExtras* ex = nullptr)
+static int vote_impl(const VoteRequest& r, const VoteCall& c)
 {
-    // `accumulate` is a flags word (include/cppf.h): bit 0 = add to the grid, CPPF_VOTE_WORKGROUPS(n) in bits 8..16 = launch at most n
-    // vote workgroups (a scheduling hint for callers that keep several instances in flight; 0 = one per CU)
-    const int wg_cap = (accumulate >> 8) & 0x1ff;
-    if ((accumulate & ~(1 | (0x1ff << 8))) != 0) return CPPF_EINVAL;
-    accumulate &= 1;
-    if (wg_cap != 0 && ex) return CPPF_EINVAL;   // (integer images fix their bits from the default plan: no hint there)
-    if (!points || (!grid_obj && !(ex && ex->grid_raw)) || !corner) return CPPF_EINVAL;   // (probs may be null: all ones)
-    if (n_ppfs > 0 && (!outputs || !point_idxs)) return CPPF_EINVAL;
-    if (n_rots < 1 || n_rots > CPPF_MAX_ROTS || gx < 1 || gy < 1 || gz < 1 || n_ppfs < 0 || n_points < 1) return CPPF_EINVAL;
-    if ((int64_t)gx * gy * gz > 0x7fffffffll) return CPPF_EINVAL;
-    if (shape_dev) {
-        if (n_ppfs < 1 || n_ppfs > 0xffffffffll || grid_cap < 1 || grid_cap > 0x7fffffffll) return CPPF_EINVAL;
-        if (!workspace || workspace_bytes < v3_workspace_bytes_dyn(many_tiles, n_ppfs)) return CPPF_EWORKSPACE;
-        return v3_launch(points, outputs, probs, point_idxs, idx_is_i64, grid_obj, corner, res, n_points, n_ppfs, n_rots, gx, gy, gz,
-                         adaptive, accumulate, want_argmax, out_idx, out_val, workspace, st, shape_dev, grid_cap, many_tiles, ex, wg_cap);
-    }
-    if (v3_eligible(n_ppfs, n_rots, gx, gy, gz)) {
-        if (!workspace || workspace_bytes < v3_workspace_bytes(n_ppfs, gx, gy, gz)) return CPPF_EWORKSPACE;
-        return v3_launch(points, outputs, probs, point_idxs, idx_is_i64, grid_obj, corner, res, n_points, n_ppfs, n_rots, gx, gy, gz,
-                         adaptive, accumulate, want_argmax, out_idx, out_val, workspace, st, nullptr, 0, 0, ex, wg_cap);
-    }
-    if (ex) {
-        if (n_ppfs > 0) return CPPF_EUNSUPPORTED;   // the integer image exists on the tiled integer path only (<= 64 tiles)
+    VotePath path; size_t need;
+    const int rc = vote_check(r, c, &path, &need);
+    if (rc != 0) return rc;
+    if (path == VOTE_TILED_DYN || path == VOTE_TILED) return v3_launch(r, c);
+    const int64_t G = (int64_t)r.gx * r.gy * r.gz;
+    if (path == VOTE_EMPTY_IMAGE) {
         // an empty pair list (a rank's slice of a short list): nothing was voted -- an all-zero image whose quantum is +inf, which
         // the MIN over the ranks' quanta ignores and cppf_grid_from_raw converts to an all-zero grid
-        if (!accumulate) {
-            hipError_t e = hipMemsetAsync(ex->grid_raw, 0, (size_t)gx * gy * gz * sizeof(long long), st);
+        if (!c.accumulate) {
+            hipError_t e = hipMemsetAsync(r.grid_raw, 0, (size_t)G * sizeof(long long), c.st);
             if (e != hipSuccess) return (int)e;
         }
-        hipLaunchKernelGGL(set_f32_kernel, dim3(1), dim3(1), 0, st, ex->quantum_out, HUGE_VALF);
+        hipLaunchKernelGGL(set_f32_kernel, dim3(1), dim3(1), 0, c.st, r.quantum_out, HUGE_VALF);
         CPPF_CHECK_LAUNCH();
         return 0;
     }
     // ---- no pairs, or a grid beyond 64 tiles: global atomics (+ the plain arg-max kernel)
-    if (!workspace || workspace_bytes < 256) return CPPF_EWORKSPACE;
-    const int64_t G = (int64_t)gx * gy * gz;
-    if (!accumulate) {
-        hipError_t e = hipMemsetAsync(grid_obj, 0, (size_t)G * sizeof(float), st);
+    if (!c.accumulate) {
+        hipError_t e = hipMemsetAsync(r.grid, 0, (size_t)G * sizeof(float), c.st);
         if (e != hipSuccess) return (int)e;
     }
-    if (n_ppfs > 0) {
-        int64_t nb = (n_ppfs + 255) / 256;
+    if (r.n_ppfs > 0) {
+        int64_t nb = (r.n_ppfs + 255) / 256;
         if (nb > 4096) nb = 4096;
-        hipLaunchKernelGGL(vote_global_kernel, dim3((unsigned)nb), dim3(256), 0, st, points, outputs, probs, point_idxs, idx_is_i64, grid_obj,
-                           corner, res, n_ppfs, n_rots, gx, gy, gz, adaptive);
+        hipLaunchKernelGGL(vote_global_kernel, dim3((unsigned)nb), dim3(256), 0, c.st, r.points, r.outputs, r.probs, r.point_idxs,
+                           r.idx_is_i64, r.grid, r.corner, r.res, r.n_ppfs, c.n_rots, r.gx, r.gy, r.gz, c.adaptive);
         CPPF_CHECK_LAUNCH();
     }
-    if (want_argmax) {
-        unsigned long long* packed = static_cast<unsigned long long*>(workspace);
-        hipLaunchKernelGGL(zero_u64x2_kernel, dim3(1), dim3(1), 0, st, packed);
+    if (r.out_idx || r.out_val) {
+        unsigned long long* packed = static_cast<unsigned long long*>(r.workspace);
+        hipLaunchKernelGGL(zero_u64x2_kernel, dim3(1), dim3(1), 0, c.st, packed);
         int64_t nb = (G + 63) / 64;
         if (nb > RED_MAX_BLOCKS) nb = RED_MAX_BLOCKS;
-        hipLaunchKernelGGL(reduce_argmax_kernel, dim3((unsigned)nb), dim3(64 * RED_GROUPS), 0, st, grid_obj, (const float*)nullptr, 0, G,
-                           packed, 1, 0, out_idx, out_val);
+        hipLaunchKernelGGL(reduce_argmax_kernel, dim3((unsigned)nb), dim3(64 * RED_GROUPS), 0, c.st, r.grid, (const float*)nullptr, 0, G,
+                           packed, 1, 0, r.out_idx, r.out_val);
         CPPF_CHECK_LAUNCH();
     }
     return 0;
@@ -1933,8 +1964,9 @@ extern "C" int cppf_ppf_voting(const float* points, const float* outputs, const 
                                int64_t n_points, int64_t n_ppfs, int n_rots, int gx, int gy, int gz, int adaptive,
                                void* workspace, size_t workspace_bytes, void* stream)
 {
-    return vote_impl(points, outputs, probs, point_idxs, 0, grid_obj, corner, res, n_points, n_ppfs, n_rots, gx, gy, gz,
-                     adaptive, 1, false, nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
+    const VoteRequest r = {points, outputs, probs, point_idxs, 0, corner, res, n_points, n_ppfs, workspace, workspace_bytes,
+                           grid_obj, gx, gy, gz};
+    return vote_impl(r, vote_call(n_rots, adaptive, CPPF_VOTE_ACCUMULATE, stream));
 }
 
 extern "C" int cppf_vote_argmax(const float* points, const float* outputs, const float* probs,
@@ -1943,8 +1975,9 @@ extern "C" int cppf_vote_argmax(const float* points, const float* outputs, const
                                 int accumulate, long long* out_idx, float* out_val, void* workspace,
                                 size_t workspace_bytes, void* stream)
 {
-    return vote_impl(points, outputs, probs, point_idxs, idx_is_i64, grid_obj, corner, res, n_points, n_ppfs, n_rots, gx, gy, gz,
-                     adaptive, accumulate, true, out_idx, out_val, workspace, workspace_bytes, (hipStream_t)stream);
+    const VoteRequest r = {points, outputs, probs, point_idxs, idx_is_i64, corner, res, n_points, n_ppfs, workspace, workspace_bytes,
+                           grid_obj, gx, gy, gz, out_idx, out_val};
+    return vote_impl(r, vote_call(n_rots, adaptive, accumulate, stream));
 }
 
 extern "C" int cppf_vote_argmax_dyn(const float* points, const float* outputs, const float* probs, const void* point_idxs,
@@ -1954,9 +1987,10 @@ extern "C" int cppf_vote_argmax_dyn(const float* points, const float* outputs, c
                                     size_t workspace_bytes, void* stream)
 {
     if (!shape_dev) return CPPF_EINVAL;
-    return vote_impl(points, outputs, probs, point_idxs, idx_is_i64, grid_obj, corner, res, n_points_cap, n_ppfs, n_rots, 1, 1, 1,
-                     adaptive, accumulate, true, out_idx, out_val, workspace, workspace_bytes, (hipStream_t)stream, shape_dev,
-                     grid_capacity, many_tiles);
+    VoteRequest r = {points, outputs, probs, point_idxs, idx_is_i64, corner, res, n_points_cap, n_ppfs, workspace, workspace_bytes,
+                     grid_obj, 0, 0, 0, out_idx, out_val};
+    request_dynamic(r, shape_dev, grid_capacity, many_tiles);
+    return vote_impl(r, vote_call(n_rots, adaptive, accumulate, stream));
 }
 
 // ---- the votes of several objects in one launch ----
@@ -1974,79 +2008,49 @@ extern "C" int cppf_vote_batch_workgroups(int n_items, int flags)
     return w;
 }
 
-// whether the item's own call would refuse its workspace (vote_impl's checks, in their order): the batch asks before its first launch
-static bool v3_item_workspace_short(const CppfVoteItem& it, int n_rots)
-{
-    const bool dyn = it.shape_dev != nullptr;
-    const int gx = dyn ? 1 : it.gx, gy = dyn ? 1 : it.gy, gz = dyn ? 1 : it.gz;
-    if (!it.points || !it.grid || !it.corner) return false;
-    if (it.n_ppfs > 0 && (!it.outputs || !it.point_idxs)) return false;
-    if (gx < 1 || gy < 1 || gz < 1 || it.n_ppfs < 0 || it.n_points < 1 || (int64_t)gx * gy * gz > 0x7fffffffll) return false;
-    size_t need = 256;
-    if (dyn) {
-        if (it.n_ppfs < 1 || it.n_ppfs > 0xffffffffll || it.grid_capacity < 1 || it.grid_capacity > 0x7fffffffll) return false;
-        need = v3_workspace_bytes_dyn(it.many_tiles, it.n_ppfs);
-    } else if (v3_eligible(it.n_ppfs, n_rots, gx, gy, gz)) {
-        need = v3_workspace_bytes(it.n_ppfs, gx, gy, gz);
-    }
-    return !it.workspace || it.workspace_bytes < need;
-}
-
 extern "C" int cppf_vote_argmax_batch(int n_items, const CppfVoteItem* items, int n_rots, int adaptive, int flags, void* stream)
 {
+    const VoteCall call = vote_call(n_rots, adaptive, flags, stream);
     if (n_items < 1 || n_items > V3_BATCH_MAX || !items) return CPPF_EINVAL;
-    if ((flags & ~(1 | (0x1ff << 8))) != 0) return CPPF_EINVAL;
+    if (!call.flags_ok) return CPPF_EINVAL;
     if (n_rots < 1 || n_rots > CPPF_MAX_ROTS) return CPPF_EINVAL;
+    hipStream_t st = call.st;
     // a short workspace refuses the whole batch before anything is launched: the loop below launches as it goes (an item's own
-    // launches, a many-tile item's binning), so a later item's refusal would otherwise find earlier items half run
-    for (int i = 0; i < n_items; ++i)
-        if (v3_item_workspace_short(items[i], n_rots)) return CPPF_EWORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    const int accumulate = flags & 1;
-    auto shares_the_launch = [&](const CppfVoteItem& it) -> bool {
-        const bool dyn = it.shape_dev != nullptr;
-        bool batched = n_rots <= VOTE_WIN && it.n_ppfs >= 1 && it.points && it.grid && it.corner && it.outputs && it.point_idxs &&
-                       it.out_idx && it.out_val && it.workspace && it.n_points >= 1;
-        if (batched && dyn) batched = it.n_ppfs <= 0xffffffffll && it.grid_capacity >= 1 &&
-                                      it.grid_capacity <= (int64_t)v3_dyn_tcap(it.many_tiles) * V3_TILE_FLOATS &&
-                                      it.workspace_bytes >= v3_workspace_bytes_dyn(it.many_tiles, it.n_ppfs);
-        if (batched && !dyn) batched = it.gx >= 1 && it.gy >= 1 && it.gz >= 1 && v3_eligible(it.n_ppfs, n_rots, it.gx, it.gy, it.gz) &&
-                                       it.workspace_bytes >= v3_workspace_bytes(it.n_ppfs, it.gx, it.gy, it.gz);
-        return batched;
-    };
+    // launches, a many-tile item's binning), so a later item's refusal would otherwise find earlier items half run.  An item that
+    // vote_check refuses for another reason is refused when the loop reaches it.  Items the check passes on a tiled path share the
+    // launch when they have at most 72 rotations and want the arg-max (a tiled path has at least one pair).
+    VoteRequest req[V3_BATCH_MAX];
+    bool shares_the_launch[V3_BATCH_MAX];
+    int n_shared = 0;
+    for (int i = 0; i < n_items; ++i) {
+        VotePath path; size_t need;
+        req[i] = request_of(items[i]);
+        const int rc = vote_check(req[i], call, &path, &need);
+        if (rc == CPPF_EWORKSPACE) return rc;
+        shares_the_launch[i] = rc == 0 && (path == VOTE_TILED_DYN || path == VOTE_TILED) && n_rots <= VOTE_WIN && req[i].out_idx && req[i].out_val;
+        n_shared += shares_the_launch[i] ? 1 : 0;
+    }
     // the default width divides the chip between the objects that SHARE the launch (a chain of four with one many-tile member, which
     // takes its own launches, used to leave a quarter of the CUs idle during the other three's vote)
-    int n_shared = 0;
-    for (int i = 0; i < n_items; ++i) n_shared += shares_the_launch(items[i]) ? 1 : 0;
-    const int width = cppf_vote_batch_workgroups(n_shared > 0 ? n_shared : n_items, flags);
+    VoteCall shared = call;
+    shared.wg_cap = cppf_vote_batch_workgroups(n_shared > 0 ? n_shared : n_items, flags);
     V3Batch B = {};
     int vote_wgs = 0, red_blocks = 0;
     size_t lds_vote = 0;
     for (int i = 0; i < n_items; ++i) {
-        const CppfVoteItem& it = items[i];
-        const bool dyn = it.shape_dev != nullptr;
-        const bool batched = shares_the_launch(it);
-        if (!batched) {   // its own launches (and its own argument checks)
-            const int rc = dyn ? cppf_vote_argmax_dyn(it.points, it.outputs, it.probs, it.point_idxs, it.idx_is_i64, it.grid, it.grid_capacity,
-                                                      it.corner, it.res, it.n_points, it.n_ppfs, n_rots, it.shape_dev, it.many_tiles, adaptive,
-                                                      flags, it.out_idx, it.out_val, it.workspace, it.workspace_bytes, stream)
-                               : cppf_vote_argmax(it.points, it.outputs, it.probs, it.point_idxs, it.idx_is_i64, it.grid, it.corner, it.res,
-                                                  it.n_points, it.n_ppfs, n_rots, it.gx, it.gy, it.gz, adaptive, flags, it.out_idx, it.out_val,
-                                                  it.workspace, it.workspace_bytes, stream);
+        if (!shares_the_launch[i]) {   // its own launches (or its refusal)
+            const int rc = vote_impl(req[i], call);
             if (rc != 0) return rc;
             continue;
         }
         V3Launch Lc;
-        const int rc = v3_prepare(Lc, it.points, it.outputs, it.probs, it.point_idxs, it.idx_is_i64, it.grid, it.corner, it.res, it.n_points,
-                                  it.n_ppfs, n_rots, dyn ? 1 : it.gx, dyn ? 1 : it.gy, dyn ? 1 : it.gz, adaptive, accumulate, true, it.out_idx,
-                                  it.out_val, it.workspace, it.shape_dev, dyn ? it.grid_capacity : 0, dyn ? it.many_tiles : 0, nullptr, width);
-        if (rc != 0) return rc;
+        v3_prepare(Lc, req[i], shared);
         if (!Lc.A.fused) {   // a grid of >= 4 tiles: its own bin launch first; its consumer and its reduce share the launches below
             v3_set_attrs();
             dim3 bin_grid;
             const size_t lds_bin = v3_bin_geometry(Lc.A, bin_grid);
-            hipLaunchKernelGGL(v3_bin_kernel<false>, bin_grid, dim3(V3_BIN_THREADS), lds_bin, st, Lc.A);
-            CPPF_CHECK_LAUNCH();
+            const int rc = v3_launch_bin(Lc.A, false, bin_grid, lds_bin, st);
+            if (rc != 0) return rc;
         }
         const int k = B.n++;
         B.item[k] = Lc.A;
@@ -2079,9 +2083,10 @@ extern "C" int cppf_vote_grid_raw(const float* points, const float* outputs, con
                                   int fixed_bits, void* workspace, size_t workspace_bytes, void* stream)
 {
     if (!grid_raw || !quantum_out || fixed_bits < 0 || (fixed_bits != 0 && (fixed_bits < 8 || fixed_bits > 24))) return CPPF_EINVAL;
-    const VoteExtras ex = {grid_raw, quantum_out, fixed_bits};
-    return vote_impl(points, outputs, probs, point_idxs, idx_is_i64, nullptr, corner, res, n_points, n_ppfs, n_rots, gx, gy, gz,
-                     adaptive, accumulate, false, nullptr, nullptr, workspace, workspace_bytes, (hipStream_t)stream, nullptr, 0, 0, &ex);
+    VoteRequest r = {points, outputs, probs, point_idxs, idx_is_i64, corner, res, n_points, n_ppfs, workspace, workspace_bytes,
+                     nullptr, gx, gy, gz};
+    r.grid_raw = grid_raw; r.quantum_out = quantum_out; r.fixed_bits = fixed_bits;
+    return vote_impl(r, vote_call(n_rots, adaptive, accumulate, stream));
 }
 
 // grid = raw * quantum (one rounding per cell: the conversion v3_reduce_kernel applies), then the arg-max

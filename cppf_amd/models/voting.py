@@ -68,30 +68,48 @@ def _dims(gx, gy, gz, grid=None):
     return gx, gy, gz
 
 
+def _vote_inputs(points, outputs, probs, point_idxs, corner, dev=None, dropin=False):
+    """The tensor contract the vote wrappers share: points f32[N,3] (on `dev` when given), outputs f32[P,2], probs f32[N] or None
+    (all ones, nocs/inference.py:201: no tensor is read), point_idxs i32[P,2] (as the reference passes it) or the original i64[P,2],
+    corner f32, all on the device of points.  dropin: the reference kernel's own arguments -- probs required, int32 indices only.
+    Returns (device, whether the indices are int64, P)."""
+    dev = dev_tensor(points, F32, "points", (3,), dev).device
+    dev_tensor(outputs, F32, "outputs", (2,), dev)
+    if probs is not None or dropin:
+        dev_tensor(probs, F32, "probs", None, dev)
+    i64 = not dropin and isinstance(point_idxs, torch.Tensor) and point_idxs.dtype == torch.int64
+    dev_tensor(point_idxs, torch.int64 if i64 else I32, "point_idxs", (2,), dev)
+    dev_tensor(corner, F32, "corner", None, dev)
+    if probs is not None and probs.numel() != points.shape[0]:
+        raise ValueError("probs must have one entry per point")
+    return dev, i64, point_idxs.shape[0]
+
+
+def _vote_scratch(dev, tag, n_ppfs, n_rots=None, dims=None, tiles=0):
+    """the zeroed vote workspace `tag` of a by-value vote (n_rots, dims) or, dims None, of a *_dyn vote of tile class `tiles`"""
+    if dims is None:
+        need = _lib.lib().cppf_vote_workspace_bytes_dyn_pairs(tiles, n_ppfs)
+    else:
+        need = _lib.lib().cppf_vote_workspace_bytes(n_ppfs, int(n_rots), *dims)
+        if need == 0:
+            raise ValueError(f"n_rots must be in 1..360, got {n_rots}")
+    return scratch(workspace(need, dev, tag, zero=True))
+
+
 def _ppf_voting(points, outputs, probs, point_idxs, grid_obj, corner, res, n_ppfs, n_rots, gx, gy, gz, adaptive):
     """models/voting.py:8-66 (launch: nocs/inference.py:197-205)"""
-    dev = dev_tensor(points, F32, "points", (3,)).device
+    dev, _, _ = _vote_inputs(points, outputs, probs, point_idxs, corner, dropin=True)
     n_ppfs, n_rots = int(scalar(n_ppfs)), int(scalar(n_rots))
-    dev_tensor(outputs, F32, "outputs", (2,), dev)
-    dev_tensor(probs, F32, "probs", None, dev)
-    dev_tensor(point_idxs, I32, "point_idxs", (2,), dev)
     dev_tensor(grid_obj, F32, "grid_obj", None, dev)
-    dev_tensor(corner, F32, "corner", None, dev)
     gx, gy, gz = _dims(gx, gy, gz, grid_obj)
-    if probs.numel() != points.shape[0]:
-        raise ValueError("probs must have one entry per point")
     if outputs.shape[0] < n_ppfs or point_idxs.shape[0] < n_ppfs or n_ppfs < 0:
         raise ValueError("n_ppfs exceeds the outputs/point_idxs arrays")
-    need = _lib.lib().cppf_vote_workspace_bytes(n_ppfs, n_rots, gx, gy, gz)
-    if need == 0:
-        raise ValueError(f"n_rots must be in 1..360, got {n_rots}")
-    ws = workspace(need, dev, "vote", zero=True)
     call("cppf_ppf_voting", dev, points, outputs, probs, point_idxs, grid_obj, corner, float(scalar(res)), points.shape[0], n_ppfs, n_rots,
-         gx, gy, gz, bool(scalar(adaptive)), scratch(ws))
+         gx, gy, gz, bool(scalar(adaptive)), _vote_scratch(dev, "vote", n_ppfs, n_rots, (gx, gy, gz)))
 
 
 def _vote_flags(accumulate, workgroups):
-    """the flags word of cppf_vote_argmax / _dyn (include/cppf.h): CPPF_VOTE_ACCUMULATE | CPPF_VOTE_WORKGROUPS(n)"""
+    """the flags word of cppf_vote_argmax / _dyn / _batch (include/cppf.h): CPPF_VOTE_ACCUMULATE | CPPF_VOTE_WORKGROUPS(n)"""
     w = int(workgroups or 0)
     if w and not 64 <= w <= 256:
         raise ValueError(f"workgroups must be 0 (one per CU) or in 64..256, got {workgroups}")
@@ -107,30 +125,18 @@ def vote_argmax(points, outputs, probs, point_idxs, grid_obj, corner, res, n_rot
     callers that keep several instances in flight on different streams (cppf.h: CPPF_VOTE_WORKGROUPS).
     point_idxs may be int32 (as the reference passes it) or the original int64 pair list.
     Returns (out_idx i64[1], out_val f32[1]) device tensors."""
-    dev = dev_tensor(points, F32, "points", (3,)).device
-    dev_tensor(outputs, F32, "outputs", (2,), dev)
-    if probs is not None:                         # None: all ones (nocs/inference.py:201), no tensor is read
-        dev_tensor(probs, F32, "probs", None, dev)
-    i64 = isinstance(point_idxs, torch.Tensor) and point_idxs.dtype == torch.int64
-    dev_tensor(point_idxs, torch.int64 if i64 else I32, "point_idxs", (2,), dev)
+    dev, i64, n_ppfs = _vote_inputs(points, outputs, probs, point_idxs, corner)
     dev_tensor(grid_obj, F32, "grid_obj", None, dev)
-    dev_tensor(corner, F32, "corner", None, dev)
     if grid_obj.dim() != 3:
         raise ValueError("grid_obj must be [gx,gy,gz]")
-    if probs is not None and probs.numel() != points.shape[0]:
-        raise ValueError("probs must have one entry per point")
     gx, gy, gz = grid_obj.shape
-    n_ppfs = point_idxs.shape[0]
     if out_idx is None:
         out_idx = torch.empty(1, dtype=torch.int64, device=dev)
     if out_val is None:
         out_val = torch.empty(1, dtype=F32, device=dev)
-    need = _lib.lib().cppf_vote_workspace_bytes(n_ppfs, int(n_rots), gx, gy, gz)
-    if need == 0:
-        raise ValueError(f"n_rots must be in 1..360, got {n_rots}")
-    ws = workspace(need, dev, "vote", zero=True)
     call("cppf_vote_argmax", dev, points, outputs, probs, point_idxs, i64, grid_obj, corner, float(scalar(res)), points.shape[0], n_ppfs,
-         int(n_rots), gx, gy, gz, bool(adaptive), _vote_flags(accumulate, workgroups), out_idx, out_val, scratch(ws))
+         int(n_rots), gx, gy, gz, bool(adaptive), _vote_flags(accumulate, workgroups), out_idx, out_val,
+         _vote_scratch(dev, "vote", n_ppfs, n_rots, (gx, gy, gz)))
     return out_idx, out_val
 
 
@@ -140,31 +146,21 @@ def vote_argmax_dyn(points, outputs, probs, point_idxs, grid_flat, shape, corner
     {n_points, gx, gy, gz}; `points`/`probs` are capacity-sized (rows beyond n_points are never read), `grid_flat` is a
     flat f32 buffer whose first gx*gy*gz cells receive the grid in the usual C order.  Same results as vote_argmax on
     the real shape.  A record exceeding a capacity yields out_idx = -1."""
-    dev = dev_tensor(points, F32, "points", (3,)).device
-    dev_tensor(outputs, F32, "outputs", (2,), dev)
-    if probs is not None:
-        dev_tensor(probs, F32, "probs", None, dev)
-    i64 = point_idxs.dtype == torch.int64
-    dev_tensor(point_idxs, torch.int64 if i64 else I32, "point_idxs", (2,), dev)
+    dev, i64, n_ppfs = _vote_inputs(points, outputs, probs, point_idxs, corner)
     dev_tensor(grid_flat, F32, "grid_flat", None, dev)
     dev_tensor(shape, I32, "shape", None, dev)
-    dev_tensor(corner, F32, "corner", None, dev)
-    if shape.numel() < 4 or (probs is not None and probs.numel() != points.shape[0]):
-        raise ValueError("shape must be i32[4]; probs must have one entry per (capacity) point")
+    if shape.numel() < 4:
+        raise ValueError("shape must be i32[4]")
     many_tiles = _lib.tile_class(many_tiles)
-    ws = workspace(_lib.lib().cppf_vote_workspace_bytes_dyn_pairs(many_tiles, int(point_idxs.shape[0])), dev, "vote_dyn", zero=True)
     call("cppf_vote_argmax_dyn", dev, points, outputs, probs, point_idxs, i64, grid_flat, grid_flat.numel(), corner, float(scalar(res)),
-         points.shape[0], point_idxs.shape[0], int(n_rots), shape, many_tiles, bool(adaptive), _vote_flags(accumulate, workgroups),
-         out_idx, out_val, scratch(ws))
+         points.shape[0], n_ppfs, int(n_rots), shape, many_tiles, bool(adaptive), _vote_flags(accumulate, workgroups),
+         out_idx, out_val, _vote_scratch(dev, "vote_dyn", n_ppfs, tiles=many_tiles))
     return out_idx, out_val
 
 
 def vote_batch_workgroups(n_items, workgroups=0):
     """vote workgroups each object of a vote_argmax_batch call gets (256 / n_items, at least 64, unless `workgroups` says otherwise)"""
-    w = int(workgroups or 0)
-    if w and not 64 <= w <= 256:
-        raise ValueError(f"workgroups must be 0 or in 64..256, got {workgroups}")
-    return int(_lib.lib().cppf_vote_batch_workgroups(int(n_items), w << 8))
+    return int(_lib.lib().cppf_vote_batch_workgroups(int(n_items), _vote_flags(False, workgroups)))
 
 
 def vote_argmax_batch(items, n_rots, adaptive, accumulate=False, workgroups=0, ws_tag="vote_b", workspaces_out=None):
@@ -177,49 +173,32 @@ def vote_argmax_batch(items, n_rots, adaptive, accumulate=False, workgroups=0, w
     any width (the fixed-point scale does not follow the width)."""
     if not 1 <= len(items) <= 8:
         raise ValueError("1 to 8 objects per call")
-    L = _lib.lib()
-    w = int(workgroups or 0)
-    if w and not 64 <= w <= 256:
-        raise ValueError(f"workgroups must be 0 or in 64..256, got {workgroups}")
-    flags = (1 if accumulate else 0) | (w << 8)
+    flags = _vote_flags(accumulate, workgroups)
     arr = (_lib.VoteItem * len(items))()
     keep = []
     dev = items[0]["points"].device
     for i, it in enumerate(items):
-        points = dev_tensor(it["points"], F32, "points", (3,), dev)
-        outputs = dev_tensor(it["outputs"], F32, "outputs", (2,), dev)
-        probs = it.get("probs")
-        if probs is not None:
-            dev_tensor(probs, F32, "probs", None, dev)
-            if probs.numel() != points.shape[0]:
-                raise ValueError("probs must have one entry per point")
-        idx = it["point_idxs"]
-        i64 = isinstance(idx, torch.Tensor) and idx.dtype == torch.int64
-        dev_tensor(idx, torch.int64 if i64 else I32, "point_idxs", (2,), dev)
+        points, outputs, probs, idx, corner = it["points"], it["outputs"], it.get("probs"), it["point_idxs"], it["corner"]
+        _, i64, n_ppfs = _vote_inputs(points, outputs, probs, idx, corner, dev)
         grid = dev_tensor(it["grid"], F32, "grid", None, dev)
-        corner = dev_tensor(it["corner"], F32, "corner", None, dev)
         out_idx = dev_tensor(it["out_idx"], torch.int64, "out_idx", None, dev)
         out_val = dev_tensor(it["out_val"], F32, "out_val", None, dev)
         shape = it.get("shape")
-        n_ppfs = idx.shape[0]
         a = arr[i]
         if shape is not None:
             dev_tensor(shape, I32, "shape", None, dev)
             many = _lib.tile_class(it.get("many_tiles") or 0)
-            ws = workspace(L.cppf_vote_workspace_bytes_dyn_pairs(many, int(n_ppfs)), dev, f"{ws_tag}dyn{i}", zero=True)
+            ws = _vote_scratch(dev, f"{ws_tag}dyn{i}", n_ppfs, tiles=many)
             fill(a, dev, shape_dev=shape, grid_capacity=grid.numel(), many_tiles=many, gx=1, gy=1, gz=1)
         else:
             if grid.dim() != 3:
                 raise ValueError("grid must be [gx,gy,gz] (or pass `shape` for a capacity buffer)")
             gx, gy, gz = (int(v) for v in grid.shape)
-            need = L.cppf_vote_workspace_bytes(n_ppfs, int(n_rots), gx, gy, gz)
-            if need == 0:
-                raise ValueError(f"n_rots must be in 1..360, got {n_rots}")
-            ws = workspace(need, dev, f"{ws_tag}{i}", zero=True)
+            ws = _vote_scratch(dev, f"{ws_tag}{i}", n_ppfs, n_rots, (gx, gy, gz))
             fill(a, shape_dev=None, grid_capacity=0, many_tiles=0, gx=gx, gy=gy, gz=gz)
         fill(a, dev, points=points, outputs=outputs, probs=probs, point_idxs=idx, idx_is_i64=i64, grid=grid, corner=corner, out_idx=out_idx,
-             out_val=out_val, workspace=scratch(ws), n_points=points.shape[0], n_ppfs=n_ppfs, res=float(scalar(it["res"])))
-        keep.append(ws)
+             out_val=out_val, workspace=ws, n_points=points.shape[0], n_ppfs=n_ppfs, res=float(scalar(it["res"])))
+        keep.append(ws.buf)
     call("cppf_vote_argmax_batch", dev, len(items), arr, int(n_rots), bool(adaptive), flags)
     if workspaces_out is not None:  # (the back-vote loads the rotation table a vote left in its workspace)
         workspaces_out[:] = keep
@@ -237,25 +216,15 @@ def vote_grid_raw(points, outputs, probs, point_idxs, grid_raw, quantum, corner,
     quanta, quantum f32[1] = value of one quantum (0: not valid).  Ranks voting slices of one pair list pass the same
     fixed_bits, all-reduce grid_raw as integers and convert once (grid_from_raw): the multi-GPU grid is then the
     single-GPU grid bit for bit (cppf_amd/sharding.py)."""
-    dev = dev_tensor(points, F32, "points", (3,)).device
-    dev_tensor(outputs, F32, "outputs", (2,), dev)
-    if probs is not None:
-        dev_tensor(probs, F32, "probs", None, dev)
-    i64 = point_idxs.dtype == torch.int64
-    dev_tensor(point_idxs, torch.int64 if i64 else I32, "point_idxs", (2,), dev)
+    dev, i64, n_ppfs = _vote_inputs(points, outputs, probs, point_idxs, corner)
     dev_tensor(grid_raw, torch.int64, "grid_raw", None, dev)
     dev_tensor(quantum, F32, "quantum", None, dev)
-    dev_tensor(corner, F32, "corner", None, dev)
     if grid_raw.dim() != 3:
         raise ValueError("grid_raw must be [gx,gy,gz]")
     gx, gy, gz = grid_raw.shape
-    n_ppfs = point_idxs.shape[0]
-    need = _lib.lib().cppf_vote_workspace_bytes(n_ppfs, int(n_rots), gx, gy, gz)
-    if need == 0:
-        raise ValueError(f"n_rots must be in 1..360, got {n_rots}")
-    ws = workspace(need, dev, "vote", zero=True)
     call("cppf_vote_grid_raw", dev, points, outputs, probs, point_idxs, i64, grid_raw, quantum, corner, float(scalar(res)), points.shape[0],
-         n_ppfs, int(n_rots), gx, gy, gz, bool(adaptive), bool(accumulate), int(fixed_bits), scratch(ws))
+         n_ppfs, int(n_rots), gx, gy, gz, bool(adaptive), bool(accumulate), int(fixed_bits),
+         _vote_scratch(dev, "vote", n_ppfs, n_rots, (gx, gy, gz)))
 
 
 def grid_from_raw(grid_raw, quantum, grid=None, out_idx=None, out_val=None):
