@@ -83,6 +83,16 @@ def gather_ref(hi, nrm, owner, masks, capacity=None, poison=True):
     return dict(out, member=member, offsets=offsets, bad=False)
 
 
+def chunk_counts_ref(member, K, chunk=1024):
+    """i64[K, ceil(M / chunk)]: the members of proposal k among the dense points [c chunk, (c + 1) chunk) -- the table
+    gi_count_kernel writes and every workgroup of gi_scatter_kernel sums"""
+    member = np.asarray(member, np.uint32)
+    n_chunks = (member.shape[0] + chunk - 1) // chunk
+    padded = np.zeros(n_chunks * chunk, np.uint32)
+    padded[:member.shape[0]] = member
+    return np.stack([((padded >> np.uint32(k)) & 1).reshape(n_chunks, chunk).sum(-1) for k in range(K)]).astype(np.int64)
+
+
 def gather_loop(hi, nrm, owner, masks):
     """member, offsets and the packed rows by plain loops (roomy capacity, owners in range)"""
     K, N = np.asarray(masks).shape

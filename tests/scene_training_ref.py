@@ -32,6 +32,39 @@ def draw_ref(members, seg_off, inst, n_points, n_pairs, n_pos_pairs, seed):
     return np.stack([a, b], -1).astype(np.int32)
 
 
+def draw_ref_lenient(members, members_cap, seg_off, inst, n_points, n_pairs, n_pos_pairs, seed):
+    """cppf_sample_scene_pairs on lists that need not keep their promises: (idx i32[n_pairs,2], kept bool[n_pairs]: the pairs of the
+    positive stratum that keep the UNIFORM draw because a lookup failed one of st_draw_kernel's guards).  members: the entries the
+    list claims (at least seg_off[K] of them where that does not pass members_cap); the guards, in the kernel's order: 0 < M =
+    seg_off[K] <= members_cap; the member drawn for a lies in [0, n_points); its label k lies in [0, K); 0 <= seg_off[k] < seg_off[k+1]
+    <= M.  b is whatever the list holds at the drawn position: it is not looked at."""
+    members, seg_off, inst = (np.asarray(x, np.int64) for x in (members, seg_off, inst))
+    K = seg_off.shape[0] - 1
+    p = np.arange(int(n_pairs), dtype=np.uint64)
+    w = syn.philox4x32_10([p, np.zeros_like(p), np.full_like(p, STREAM), np.zeros_like(p)], seed)
+    N, M = np.uint64(int(n_points)), int(seg_off[K])
+    a = ((w[0] * N) >> _s32).astype(np.int64)
+    b = ((w[1] * N) >> _s32).astype(np.int64)
+    kept = np.zeros(int(n_pairs), bool)
+    n_pos = int(n_pos_pairs)
+    if n_pos and not (0 < M <= int(members_cap)):
+        kept[:n_pos] = True
+    elif n_pos:
+        am = members[((w[0][:n_pos] * np.uint64(M)) >> _s32).astype(np.int64)]
+        ok = (am >= 0) & (am < int(n_points))
+        k = np.where(ok, inst[np.where(ok, am, 0)], -1)
+        ok &= (k >= 0) & (k < K)
+        kc = np.where(ok, k, 0)
+        s0, s1 = seg_off[kc], seg_off[kc + 1]
+        ok &= (s0 >= 0) & (s1 > s0) & (s1 <= M)
+        L = np.where(ok, s1 - s0, 1).astype(np.uint64)
+        pos = np.where(ok, s0, 0) + ((w[1][:n_pos] * L) >> _s32).astype(np.int64)
+        a[:n_pos] = np.where(ok, am, a[:n_pos])
+        b[:n_pos] = np.where(ok, members[pos], b[:n_pos])
+        kept[:n_pos] = ~ok
+    return np.stack([a, b], -1).astype(np.int32), kept
+
+
 def members_ref(inst, flags):
     """(members, seg_off) of the instances with bit 0 of flags set: grouped by instance, ascending within a group"""
     inst, flags = np.asarray(inst), np.asarray(flags)
@@ -46,11 +79,12 @@ def _bin(v, interval, bins):
     return low.astype(np.int64), 1.0 - (x - low)
 
 
-def targets_ref(pc, nrm, inst, idx, table, flags, vote_range, tr_bins, rot_bins):
-    """cppf_scene_pair_targets in fp64 (the inputs are the float32 values the device reads).  dict: kind u8[P], pair_inst i32[P], low
+def targets_ref(pc, nrm, inst, idx, table, flags, vote_range, tr_bins, rot_bins, dtype=np.float64):
+    """cppf_scene_pair_targets in fp64 (the inputs are the float32 values the device reads; dtype=np.float32: every operation in fp32
+    with the kernel's constants -- for scenes of exact coordinates, where |a - b| + 1e-7 must round as it does on the device).  dict: kind u8[P], pair_inst i32[P], low
     i64[P,4], w_low f64[P,4], aux u8[P,2] as the kernel writes them, and for the positives (0 elsewhere) d_len = |a - b|, cos f64[P,2] =
     (u.up, u.right), aux_margin f64[P,2] = (|n.up|, |n.right|)."""
-    pc, nrm, table = np.asarray(pc, np.float64), np.asarray(nrm, np.float64), np.asarray(table, np.float64)
+    pc, nrm, table = np.asarray(pc, dtype), np.asarray(nrm, dtype), np.asarray(table, dtype)
     inst, idx, flags = np.asarray(inst, np.int64), np.asarray(idx, np.int64), np.asarray(flags, np.int64)
     N, P, K = pc.shape[0], idx.shape[0], flags.shape[0]
     v0, v1 = float(vote_range[0]), float(vote_range[1])
@@ -67,33 +101,35 @@ def targets_ref(pc, nrm, inst, idx, table, flags, vote_range, tr_bins, rot_bins)
     kc = np.clip(k, 0, K - 1)
     pos = inside & (k >= 0) & (k < K) & (inst[ib] == k) & ((flags[kc] & 1) != 0)
     q = np.nonzero(pos)[0]
-    if q.size:
-        r = table[kc[q]]
-        c, up, right = r[:, 0:3], r[:, 3:6], r[:, 6:9]
-        a, b = pc[ia[q]] - c, pc[ib[q]] - c
-        d = a - b
-        L = np.linalg.norm(d, axis=-1)
-        u = d / (L[:, None] + 1e-7)
-        proj = (a * u).sum(-1)
-        dist2o = np.linalg.norm(a - proj[:, None] * u, axis=-1)
-        cu, cr = (u * up).sum(-1), (u * right).sum(-1)
-        th_up = np.arccos(np.clip(cu, -1, 1))
-        th_up = np.where(flags[kc[q]] & 2, np.minimum(th_up, np.arccos(np.clip(-cu, -1, 1))), th_up)
-        th_r = np.arccos(np.clip(cr, -1, 1))
-        th_r = np.where(flags[kc[q]] & 4, np.minimum(th_r, np.arccos(np.clip(-cr, -1, 1))), th_r)
-        n = nrm[ia[q]].copy()
-        n[(n * u).sum(-1) < 0] *= -1
-        n_up, n_r = (n * up).sum(-1), (n * right).sum(-1)
-        vals = [np.clip(proj + v0, 0, 2 * v0), np.clip(dist2o, 0, v1), th_up, th_r]
-        spans = [(2 * v0, tr_bins), (v1, tr_bins), (np.pi, rot_bins), (np.pi, rot_bins)]
-        fin = np.isfinite(proj) & np.isfinite(dist2o) & np.isfinite(cu) & np.isfinite(cr) & np.isfinite(n_up) & np.isfinite(n_r)
-        q, sel = q[fin], fin
-        for h, (v, (mx, bins)) in enumerate(zip(vals, spans)):
-            low[q, h], w_low[q, h] = _bin(v[sel], mx / (bins - 1), bins)
-        aux[q, 0], aux[q, 1] = n_up[sel] > 0, n_r[sel] > 0
-        kind[q], pair_inst[q] = 1, kc[q]
-        d_len[q], cos[q, 0], cos[q, 1] = L[sel], cu[sel], cr[sel]
-        margin[q, 0], margin[q, 1] = np.abs(n_up[sel]), np.abs(n_r[sel])
+    # (a coordinate that is not finite makes a quantity below NaN / inf; such a pair is set aside by `fin`: kind 0, the fill values)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        if q.size:
+            r = table[kc[q]]
+            c, up, right = r[:, 0:3], r[:, 3:6], r[:, 6:9]
+            a, b = pc[ia[q]] - c, pc[ib[q]] - c
+            d = a - b
+            L = np.linalg.norm(d, axis=-1)
+            u = d / (L[:, None] + dtype(1e-7))
+            proj = (a * u).sum(-1)
+            dist2o = np.linalg.norm(a - proj[:, None] * u, axis=-1)
+            cu, cr = (u * up).sum(-1), (u * right).sum(-1)
+            th_up = np.arccos(np.clip(cu, -1, 1))
+            th_up = np.where(flags[kc[q]] & 2, np.minimum(th_up, np.arccos(np.clip(-cu, -1, 1))), th_up)
+            th_r = np.arccos(np.clip(cr, -1, 1))
+            th_r = np.where(flags[kc[q]] & 4, np.minimum(th_r, np.arccos(np.clip(-cr, -1, 1))), th_r)
+            n = nrm[ia[q]].copy()
+            n[(n * u).sum(-1) < 0] *= -1
+            n_up, n_r = (n * up).sum(-1), (n * right).sum(-1)
+            vals = [np.clip(proj + dtype(v0), 0, dtype(2 * v0)), np.clip(dist2o, 0, dtype(v1)), th_up, th_r]
+            spans = [(2 * v0, tr_bins), (v1, tr_bins), (np.pi, rot_bins), (np.pi, rot_bins)]
+            fin = np.isfinite(proj) & np.isfinite(dist2o) & np.isfinite(cu) & np.isfinite(cr) & np.isfinite(n_up) & np.isfinite(n_r)
+            q, sel = q[fin], fin
+            for h, (v, (mx, bins)) in enumerate(zip(vals, spans)):
+                low[q, h], w_low[q, h] = _bin(v[sel], dtype(mx / (bins - 1)), bins)       # (the width: fp64, then rounded once)
+            aux[q, 0], aux[q, 1] = n_up[sel] > 0, n_r[sel] > 0
+            kind[q], pair_inst[q] = 1, kc[q]
+            d_len[q], cos[q, 0], cos[q, 1] = L[sel], cu[sel], cr[sel]
+            margin[q, 0], margin[q, 1] = np.abs(n_up[sel]), np.abs(n_r[sel])
     return dict(kind=kind, pair_inst=pair_inst, low=low, w_low=w_low, aux=aux, d_len=d_len, cos=cos, aux_margin=margin)
 
 

@@ -68,13 +68,13 @@ def test_draw_equals_the_restatement(dev, P):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the targets
-@pytest.fixture(scope="module")
-def scene3():
+def scene3_case(**bins):
     """bottle, can, bottle and 60 background points: instances 0 and 2 are of the target category, instance 0 alone is up_sym; one list
-    of 1000 pairs (half from the positive stratum) with its fp64 restatement and what torch fp32 deviates from it -- computed once, the
-    cases below are slices of the list"""
+    of 1000 pairs (half from the positive stratum) with its fp64 restatement and what torch fp32 deviates from it.  bins: tr_num_bins
+    / rot_num_bins other than the config's (tests/test_gpu_scene_limits.py: the ends of the accepted range)"""
     s = R.posed_scene(["bottle", "can", "bottle"], "bottle", N, seed=21, n_background=60, up_sym=False)
     s["flags"] = np.array([TARGET | UP, 0, TARGET], np.int32)
+    s["cfg"] = dataclasses.replace(s["cfg"], **bins)
     cfg, n = s["cfg"], s["pc"].shape[0]
     members, seg_off = R.members_ref(s["inst"], s["flags"])
     idx = R.draw_ref(members, seg_off, s["inst"], n, 1000, 500, seed=22)
@@ -91,6 +91,12 @@ def scene3():
     print(f"torch fp32 against fp64 on {int(pos.sum())} positives: mu/nu {s['dev_tr']:.3g}, angles {s['dev_rot']:.3g}, "
           f"{100 * hard.mean():.2f} % of the pairs set aside")
     return s
+
+
+@pytest.fixture(scope="module")
+def scene3():
+    """scene3_case at the config's bins, computed once: the cases below are slices of its list"""
+    return scene3_case()
 
 
 def _device_targets(s, dev, idx, inst=None, table=None, flags=None):
