@@ -16,7 +16,7 @@ from collections import OrderedDict, deque
 import numpy as np
 import torch
 
-from . import sharding
+from . import chains, sharding
 from ._torch_util import copy_words, lane_streams
 from .inference import PoseChain, PosePipeline, assemble_batch, grid_class, grid_shape
 from .utils.util import fibonacci_sphere, num_sphere_bins
@@ -64,15 +64,12 @@ class BatchPoseRunner:
         neighbours in flight half the chip per vote moves more instances per second (profiles/r4_vote_workgroups.txt) -- and one
         workgroup per CU otherwise (longer pair lists, many-tile grids, a single lane).
         chain_len: instances whose launches are SHARED (inference.PoseChain: one pair-kernel launch, one vote + one reduce launch and
-        six tail launches for the whole chain instead of ~15 launches per instance).  None = chains only when the batch is large
-        enough to keep every lane two chains deep -- min(8, instances / (2 n_lanes)) -- because a small batch is bounded by the host
-        staging it, and a chain cannot start before its last member is staged (measured on 8 / 16 / 32 / 64 C2-size objects:
-        no chains 0.189 / 0.163 / 0.164 / 0.158 ms per object, chains 0.193 / 0.164 / 0.161 / 0.140); 1 = every instance its own
+        six tail launches for the whole chain instead of ~15 launches per instance).  None = the measured policies
+        chains.host_chain_len (objects staged one by one) and chains.resident_chain_len (staged batches); 1 = every instance its own
         captured pipeline (round 4).  A pipeline serves one (category, point bucket, pair count, grid class, lane, chain position):
         `max_pipelines` / `max_scratch_bytes` bound the cache (a mixed batch of six categories in chains of 8 on 3 lanes wants up to
         144 pipelines of ~0.1 GB at C2 size; a cache that is too small re-captures on every batch).  A chain is captured the SECOND time
-        its combination of pipelines (category, point bucket, pair count, grid class per position) comes up -- a one-off combination
-        runs its members' own graphs -- and at most `max_chains` captured chains are kept (least recently used first out).
+        its combination of pipelines comes up; at most `max_chains` are kept, least recently used first out (chains.ChainCache).
         staged_host: host objects WITHOUT their own pair lists (pairs drawn on the device: `n_pairs`) are uploaded with one copy each and
         take the chains of device-resident objects (put(), _run_resident): records assembled on the device, nothing read back -- the
         batch's records are then returned on the device whatever the world size.  False: round 5's per-instance path for them too.
@@ -95,7 +92,8 @@ class BatchPoseRunner:
         self.n_bucket, self.max_pipelines, self.dynamic = int(n_bucket), int(max_pipelines), bool(dynamic)
         self.max_scratch_bytes, self._bytes = int(max_scratch_bytes), {}
         self.chain_len, self.max_chains = (None if chain_len is None else max(1, min(8, int(chain_len)))), int(max_chains)
-        self._chains, self._chain_seen = OrderedDict(), {}     # LRU: tuple of member ids -> PoseChain; sightings of a combination
+        make = lambda pipes, tag: PoseChain(pipes, use_graph=self.kw["use_graph"], staged=bool(tag), vote_workgroups=self.vote_workgroups or 0)
+        self._chains = chains.ChainCache(self.max_chains, make, lambda: torch.cuda.synchronize(device))     # (tag: ("staged",) or ())
         self._pipes = OrderedDict()    # LRU: key -> PosePipeline
         self._staging = {}         # pinned host staging sets for the small per-instance arrays, see _stage()
         self.staged_host, self.overlap_batches, self.idx_i32 = bool(staged_host), bool(overlap_batches), bool(idx_i32)
@@ -125,8 +123,7 @@ class BatchPoseRunner:
                 torch.cuda.synchronize(self.device)
                 old_key, old = self._pipes.popitem(last=False)
                 self._bytes.pop(old_key, None)
-                for ck in [ck for ck in self._chains if id(old) in ck]:      # chains the victim is a member of go with it
-                    self._chains.pop(ck).release()
+                self._chains.drop_member(id(old))
                 old.release()
             width = self.vote_workgroups
             if width is None:
@@ -158,32 +155,15 @@ class BatchPoseRunner:
         return self._lane_set
 
     def _chain_for(self, pipes, staged=False):
-        """the captured chain of these pipelines, or None (a single instance; a member the chain cannot take; a combination seen for
-        the first time: its members run their own graphs).  staged=True (objects resident on the device, _run_resident): always a
-        chain -- of one member too -- returned with `capture`: False on a combination's first sighting (it then runs eagerly)."""
-        if any(not p._split_ok or p.rot_order is not None or p._sph[2] == 0 for p in pipes):
-            if staged:
-                raise ValueError("device-resident objects need the standard pair encoder and sphere bins sorted by y (PoseChain)")
-            return None
-        if len(pipes) < 2 and not staged:
-            return None
-        key = tuple(id(p) for p in pipes) + (("staged",) if staged else ())
-        chain = self._chains.get(key)
-        if chain is not None:
-            self._chains.move_to_end(key)
-            return (chain, True) if staged else chain
-        seen = self._chain_seen.get(key, 0) + 1
-        if len(self._chain_seen) > 4096:
-            self._chain_seen.clear()
-        self._chain_seen[key] = seen
-        if seen < 2 and not staged:
-            return None
-        while len(self._chains) >= self.max_chains:
-            torch.cuda.synchronize(self.device)
-            self._chains.popitem(last=False)[1].release()
-        chain = self._chains[key] = PoseChain(pipes, use_graph=self.kw["use_graph"], staged=staged,
-                                              vote_workgroups=0 if self.vote_workgroups is None else self.vote_workgroups)
-        return (chain, seen >= 2) if staged else chain
+        """-> (the captured chain of these pipelines, capture), or (None, False): a single instance; a member the chain cannot take; a
+        combination seen for the first time (chains.ChainCache): its members run their own graphs.  staged=True (objects resident on the
+        device, _run_resident): always a chain -- of one member too -- with capture=False on a first sighting (it then runs eagerly)."""
+        taken = all(PoseChain.takes(p, pipes[0]) for p in pipes)
+        if staged and not taken:
+            raise ValueError("device-resident objects need the standard pair encoder and sphere bins sorted by y (PoseChain)")
+        if not taken or (len(pipes) < 2 and not staged):
+            return None, False
+        return self._chains.lookup(pipes, ("staged",) if staged else (), always=staged)
 
     @staticmethod
     def footprint_bytes(n_points, n_pairs, many_tiles, dims):
@@ -345,11 +325,7 @@ class BatchPoseRunner:
         if self._streams is None:
             self._streams = self._lanes()[0]
         main = torch.cuda.current_stream(dev)
-        for cat in {objects[j]["cfg"].category for j in mine}:
-            if cat in self.encoders:
-                self.encoders[cat]._packed_weights(dev)
-            if cat in self.point_encoders:
-                self.point_encoders[cat]._packed_weights(dev)
+        chains.refresh_images(self.encoders, self.point_encoders, {objects[j]["cfg"].category for j in mine}, dev)
         blk = None
         if host_dims is not None:           # host objects: one packed copy for the whole batch, on the copy stream (_upload_batch)
             uploaded, blk = self._upload_batch(objects, mine, host_dims)
@@ -367,11 +343,7 @@ class BatchPoseRunner:
                 st.wait_stream(main)
             if blk is not None:
                 st.wait_event(blk["sent"])
-        # chains of 1, 2, 4 or 8 members -- lists of equal length in those numbers keep each list on its own XCDs in the pair kernel
-        # (cppf_pair_mlp_batch_plan) -- the smallest such length that gives every lane at most one chain, capped at 8: 8 objects on 3
-        # lanes run as 4 + 4 (0.145 ms per object; 3 + 3 + 2: 0.151, 2 + 2 + 2 + 2: 0.161), 16 as 8 + 8, 24 as 8 + 8 + 8
-        # (profiles/r6_resident_probe.txt)
-        L = self.chain_len or min(8, 1 << max(0, (-(-n // self.n_lanes) - 1).bit_length()))
+        L = self.chain_len or chains.resident_chain_len(n, self.n_lanes)
         groups = [list(range(g, min(g + L, n))) for g in range(0, n, L)]
         ran = []
         for gi, slots in enumerate(groups):
@@ -445,7 +417,7 @@ class BatchPoseRunner:
             refused = [int(c["mine"][s]) for _, slots in c["ran"] for s in slots if host[s, 12] < 0]
             for chain, slots in c["ran"]:
                 if all(host[s, 12] >= 0 for s in slots):           # (a refused member's survivor count is no pose's)
-                    chain.adapt([host[s, 14] for s in slots])
+                    chains.adapt_group(chain, chain.pipes, [host[s, 14] for s in slots])
             if refused:
                 from ._lib import CppfError
                 err = CppfError(f"batch {c['batch']}: object(s) {refused} did not fit the shape-polymorphic pipeline they ran on (arg-max "
@@ -516,17 +488,10 @@ class BatchPoseRunner:
         if self._streams is None:
             self._streams = self._lanes()[0]
         main = torch.cuda.current_stream(self.device)
-        # weight images: looked at ONCE per batch, here on the caller's stream, before the lanes fan out -- a parameter update
-        # since the last batch is re-packed (in place) now, and every lane's replays are ordered after it by the wait below
-        # (a lane that found the change itself would rebuild the image on its own stream while its neighbours replay)
-        for cat in {objects[j]["cfg"].category for j in mine}:
-            if cat in self.encoders:
-                self.encoders[cat]._packed_weights(self.device)
-            if cat in self.point_encoders:
-                self.point_encoders[cat]._packed_weights(self.device)
+        chains.refresh_images(self.encoders, self.point_encoders, {objects[j]["cfg"].category for j in mine}, self.device)
         for st in self._streams:
             st.wait_stream(main)
-        L = self.chain_len or max(1, min(8, len(mine) // (2 * self.n_lanes)))
+        L = self.chain_len or chains.host_chain_len(len(mine), self.n_lanes)
         groups = [list(range(g, min(g + L, len(mine)))) for g in range(0, len(mine), L)]     # consecutive instances share a chain
         ran = []                 # (chain or None, pipelines, slots) per group, for adapt()
         for gi, slots in enumerate(groups):
@@ -549,23 +514,14 @@ class BatchPoseRunner:
                         pipe.sample_inputs(int(seed) * 1000003 + j, n_points=obj["pc"].shape[0])      # a function of (seed, object index)
                     pipes.append(pipe)
                     cfgs.append(obj["cfg"])
-                chain = self._chain_for(pipes)
-                # (check_weights=None: the images were refreshed above, once per batch; a pipeline only compares their addresses)
-                if chain is not None:
-                    chain.run_async([raw[slot] for slot in slots], check_weights=None)
-                else:
-                    for pipe, slot in zip(pipes, slots):
-                        pipe.run_async(raw[slot], check_weights=None)
+                chain = self._chain_for(pipes)[0]
+                chains.run_group(chain, pipes, [raw[slot] for slot in slots])
                 ran.append((chain, pipes, slots))
         for st in self._streams:
             main.wait_stream(st)
         host = raw.cpu().numpy()                       # the batch's only synchronisation
-        for chain, pipes, slots in ran:                # split / full-first form of the next run (PosePipeline.adapt / PoseChain.adapt)
-            if chain is not None:
-                chain.adapt([host[slot, 18] for slot in slots])
-            else:
-                for pipe, slot in zip(pipes, slots):
-                    pipe.adapt(host[slot, 18])
+        for chain, pipes, slots in ran:                # split / full-first form of the next run
+            chains.adapt_group(chain, pipes, [host[slot, 18] for slot in slots])
         local = torch.from_numpy(assemble_batch(host[:len(mine)], cfgs, mine, sharding.RECORD))
         if world > 1 or sharding.dist.is_initialized():       # the gather needs them on the device; a single rank returns them as they are
             local = local.to(self.device)

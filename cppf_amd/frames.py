@@ -4,8 +4,9 @@ pose.  The detector that makes the masks (Mask R-CNN results pickles, :92-97) is
 import numpy as np
 import torch
 
+from . import chains
 from .config import CATEGORIES
-from .inference import estimate_pose
+from .inference import PoseChain, estimate_pose
 from .utils.util import backproject, estimate_normals, fibonacci_sphere, num_sphere_bins, sparse_quantize
 
 NOCS_INTRINSICS = np.array([[591.0125, 0, 322.525], [0, 590.16775, 244.11084], [0, 0, 1]])      # nocs/inference.py:98
@@ -94,9 +95,8 @@ class FrameRunner:
                  cfgs=None, n_lanes=3, chain_len=None, cap_bucket=4096, max_members=48, max_chains=32, batch_prestage=True):
         """max_members: pipelines kept (each with its captured graph and ~0.1 GB of buffers at 100 000 pairs); max_chains: captured
         chains kept (at least the groups of one frame: a chain of the running frame is never evicted).
-        chain_len: instances per captured chain (None: two chains of equal length from four instances on, at most 8 members each);
-        batch_prestage=False: round 5's form, every member's own frame stage (a batch of one) at the head of its chain and chains
-        of ceil(n / n_lanes)."""
+        chain_len: instances per captured chain (None: chains.frame_chain_len, the measured policy);
+        batch_prestage=False: round 5's form, every member's own frame stage (a batch of one) at the head of its chain."""
         from collections import OrderedDict
         self.encoders, self.point_encoders, self.device = encoders, point_encoders, device
         self.intrinsics = np.asarray(intrinsics, np.float64)
@@ -113,7 +113,8 @@ class FrameRunner:
         # so a video whose instance count, order or mask sizes change keeps replaying the graphs it has
         self._members, self.max_members = OrderedDict(), int(max_members)          # id(pipe) -> member, least recently used first
         self._pool = {}                                                            # class key -> [member, ...]
-        self._chains, self._seen, self.max_chains = OrderedDict(), {}, max(1, int(max_chains))
+        self.max_chains = max(1, int(max_chains))
+        self._chains = chains.ChainCache(self.max_chains, self._make_chain, lambda: torch.cuda.synchronize(device))
         self._many_tile_cats = set()
         self._hw = None
         from ._torch_util import lane_streams
@@ -139,13 +140,11 @@ class FrameRunner:
             self._set_pos = 0
             self._depth = torch.empty((H, W), dtype=torch.int16, device=self.device)
             self._labels = torch.empty((H, W), dtype=torch.int32, device=self.device)
-            for ch in self._chains.values():
-                ch.release()
+            self._chains.clear()
             for mem in self._members.values():
                 mem["pipe"].release()
             self._members.clear()
             self._pool.clear()
-            self._chains.clear()
             self._free_rows = list(range(self._slot_rows - 1, -1, -1))
 
     def _member(self, cat, n_mask, used):
@@ -169,8 +168,7 @@ class FrameRunner:
             old = self._members.pop(victim)
             self._free_rows.append(old["row"])
             self._pool[old["key"]].remove(old)
-            for ck in [ck for ck in self._chains if victim in ck]:
-                self._chains.pop(ck).release()
+            self._chains.drop_member(victim)
             old["pipe"].release()
         cfg, H, W = self.cfgs[cat], self._hw[0], self._hw[1]
         pipe = PosePipeline(self.encoders[cat], cfg, cap, self.n_pairs, key[2], self.device, self.sphere, num_rots=self.num_rots,
@@ -209,30 +207,11 @@ class FrameRunner:
             call("cppf_frame_cloud_dyn_batch", dev, n, arr, depth, 1, labels, 4, H, W, kinv, 1000.0)
         return prestage
 
-    def _chain_for(self, pipes, pres, busy):
-        """the captured chain of this combination of members (second sighting on), or None: its members run their own graphs.
-        `busy`: chains of the running frame, which an eviction must not touch."""
-        from .inference import PoseChain
-        key = tuple(id(p) for p in pipes)
-        ch = self._chains.get(key)
-        if ch is not None:
-            self._chains.move_to_end(key)
-            busy.add(key)
-            return ch
-        n = self._seen[key] = self._seen.get(key, 0) + 1
-        if len(self._seen) > 4096:
-            self._seen.clear()
-        if n < 2:
-            return None
-        while len(self._chains) >= self.max_chains:
-            victim = next((k for k in self._chains if k not in busy), None)
-            if victim is None:
-                return None                              # (more groups in this frame than max_chains)
-            torch.cuda.synchronize(self.device)
-            self._chains.pop(victim).release()
-        ch = self._chains[key] = PoseChain(pipes, prestages=pres() if callable(pres) else pres)
-        busy.add(key)
-        return ch
+    def _make_chain(self, pipes, tag):
+        """a chain's members share the launches of their frame stage (batch_prestage), or each keeps its own at the chain's head"""
+        mems = [self._members[id(p)] for p in pipes]
+        pres = [self._batch_prestage(mems)] + [None] * (len(mems) - 1) if self.batch_prestage else [m["pre"] for m in mems]
+        return PoseChain(pipes, prestages=pres)
 
     def run(self, depth, instances, seed=0):
         """-> the frame's poses (list of pose dicts / None, as frame_poses): submit() + result()"""
@@ -269,19 +248,11 @@ class FrameRunner:
         # (on the caller's stream, i.e. behind the previous frame's join: the chains' launches have these two buffers' addresses baked in)
         self._depth.copy_(hs["depth"], non_blocking=True)               # one upload per frame (two images)
         self._labels.copy_(hs["labels"], non_blocking=True)
-        for cat in {instances[i][0] for i in on_chain}:
-            self.encoders[cat]._packed_weights(dev)
-            self.point_encoders[cat]._packed_weights(dev)
+        chains.refresh_images(self.encoders, self.point_encoders, {instances[i][0] for i in on_chain}, dev)
         # (zero-filled on the caller's stream BEFORE the lanes fork from it: a lane's record copy must not race the fill)
         raw = torch.zeros((max(len(on_chain), 1), 21), dtype=torch.float64, device=dev)
         shapes = torch.zeros((max(len(on_chain), 1), 4), dtype=torch.int32, device=dev)
-        if self.chain_len:
-            Lc = self.chain_len
-        elif self.batch_prestage:          # two chains of equal length on two lanes (measured on 6 instances: 3 + 3 1.48 ms per
-            n_ch = max(2 if len(on_chain) >= 4 and self.n_lanes > 1 else 1, -(-len(on_chain) // 8))     # frame, one chain 1.58, 2 + 2 + 2 1.50)
-            Lc = max(1, -(-len(on_chain) // n_ch))
-        else:
-            Lc = max(1, min(8, -(-len(on_chain) // self.n_lanes)))
+        Lc = self.chain_len or chains.frame_chain_len(len(on_chain), self.n_lanes, self.batch_prestage)
         groups = [on_chain[g:g + Lc] for g in range(0, len(on_chain), Lc)]
         ran, used, busy = [], set(), set()
         # which member serves which instance of this frame: decided for the whole frame first, written to the members' rows of the
@@ -303,17 +274,10 @@ class FrameRunner:
         for gi, (slots_g, mems) in enumerate(zip(groups, members_of)):
             lane = gi % self.n_lanes
             with torch.cuda.stream(self._streams[lane]):
-                pipes, pres = [m["pipe"] for m in mems], [m["pre"] for m in mems]
-                # (a chain's members share the launches of their frame stage; without a chain every member runs its own)
-                ch = self._chain_for(pipes, (lambda: [self._batch_prestage(mems)] + [None] * (len(mems) - 1)) if self.batch_prestage else pres, busy)
-                # (check_weights=None: the images were refreshed above, once per frame; a pipeline compares their addresses, so a
-                # weight image that moved -- an encoder re-created or resized -- re-captures instead of reading a stale address)
-                if ch is not None:
-                    ch.run_async(None, check_weights=None)
-                else:
-                    for pipe, pre in zip(pipes, pres):
-                        pre()
-                        pipe.run_async(None, check_weights=None)
+                pipes = [m["pipe"] for m in mems]
+                # (`busy`: the chains of this frame, which an eviction must not touch; without a chain every member runs its own stage)
+                ch = self._chains.lookup(pipes, busy=busy)[0]
+                chains.run_group(ch, pipes, None, [m["pre"] for m in mems])
                 # the members' records and shape words, each in its own pipeline's buffers: one launch each into the frame's arrays
                 gather_words(raw[slots_g[0]:slots_g[-1] + 1], [p.ws.rec for p in pipes], dev)
                 gather_words(shapes[slots_g[0]:slots_g[-1] + 1], [p.shape for p in pipes], dev)
@@ -342,11 +306,8 @@ class FrameRunner:
         eager = list(range(len(on_chain), n_inst))
         self.last = {"captured": 0, "eager": len(eager), "skipped": 0}   # how the last frame's instances were served
         for ch, pipes, slots in ran:
-            if ch is not None:
-                ch.adapt([host[i, 18] for i in slots])
+            chains.adapt_group(ch, pipes, [host[i, 18] for i in slots])
             for pipe, i in zip(pipes, slots):
-                if ch is None:
-                    pipe.adapt(host[i, 18])
                 n = int(shp[i, 0])
                 if n == 0:
                     self.last["skipped"] += 1

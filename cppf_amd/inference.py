@@ -27,7 +27,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, chains
 from ._torch_util import call, canon, copy_words, fill, release_scope, require_cuda, scratch, workspace, workspace_scope
 from .models import voting
 
@@ -745,20 +745,13 @@ class PosePipeline(CenterPipeline):
     # one).  Full first: the first pass decodes every head of every pair (107 us) and there is no second pass.  Per pair the
     # arithmetic is the same, so the heads rows of the survivors, hence the pose, are identical; the choice follows the share
     # of survivors of the instance that ran last on this pipeline (break-even ~0.15, with hysteresis), seen in the record the
-    # host reads back anyway.
-    FULL_FIRST_ON, FULL_FIRST_OFF = 0.25, 0.10
+    # host reads back anyway (chains.next_form).
+    FULL_FIRST_ON, FULL_FIRST_OFF = chains.FULL_FIRST_ON, chains.FULL_FIRST_OFF
 
     def adapt(self, n_surv):
         """choose the form for the next instance from the survivors of the last one"""
-        share = float(n_surv) / max(self.idx.shape[0], 1)
-        want = self.full_first
-        if share > self.FULL_FIRST_ON:
-            want = True
-        elif share < self.FULL_FIRST_OFF:
-            want = False
-        if not self._split_ok:
-            want = True
-        self.full_first = want      # (the next run returns the tensors this form's launches write: outputs / heads / feat)
+        # (the next run returns the tensors this form's launches write: outputs / heads / feat)
+        self.full_first = chains.next_form(self.full_first, float(n_surv) / max(self.idx.shape[0], 1), self._split_ok)
 
     def _chain(self):
         self.with_heads = self.full_first
@@ -819,7 +812,14 @@ class PoseChain(_Captured):
     PosePipeline the chain has two captured forms -- split (second pass on the survivors) and full-first (every head in the first
     pass) -- chosen from the survivor share of its last run (adapt)."""
 
-    FULL_FIRST_ON, FULL_FIRST_OFF = PosePipeline.FULL_FIRST_ON, PosePipeline.FULL_FIRST_OFF
+    FULL_FIRST_ON, FULL_FIRST_OFF = chains.FULL_FIRST_ON, chains.FULL_FIRST_OFF
+
+    @staticmethod
+    def takes(p, first):
+        """can `p` be a member of a chain whose first member is `first`?  (the class docstring's "Members")"""
+        return (isinstance(p, PosePipeline) and p._split_ok and p.rot_order is None and p._sph[2] != 0
+                and (p.device, p.num_rots, p.adaptive, p.angle_tol, p.max_rot_pairs, p.ws._sph_key)
+                == (first.device, first.num_rots, first.adaptive, first.angle_tol, first.max_rot_pairs, first.ws._sph_key))
 
     def __init__(self, pipes, use_graph=True, vote_workgroups=0, prestages=None, staged=False):
         """prestages: optional list of callables, one per member (or None): launches enqueued at the head of the chain, in front of
@@ -837,12 +837,9 @@ class PoseChain(_Captured):
         if len(self.prestages) != len(pipes):
             raise ValueError("one prestage (or None) per pipeline")
         p0 = pipes[0]
-        for p in pipes:
-            if (not isinstance(p, PosePipeline) or p.device != p0.device or not p._split_ok or p.rot_order is not None
-                    or (p.num_rots, p.adaptive, p.angle_tol, p.max_rot_pairs) != (p0.num_rots, p0.adaptive, p0.angle_tol, p0.max_rot_pairs)
-                    or p.ws._sph_key != p0.ws._sph_key or p._sph[2] == 0):
-                raise _lib.CppfError("PoseChain takes PosePipelines of one device with the standard pair encoder and the same vote / "
-                                     "orientation settings (no rot_order)")
+        if not all(self.takes(p, p0) for p in pipes):
+            raise _lib.CppfError("PoseChain takes PosePipelines of one device with the standard pair encoder and the same vote / "
+                                 "orientation settings (no rot_order)")
         if len({id(p) for p in pipes}) != len(pipes):
             raise ValueError("a pipeline can be a member once")
         self.pipes, self.device = pipes, p0.device
@@ -978,10 +975,7 @@ class PoseChain(_Captured):
     def adapt(self, n_survs):
         """choose the form of the next run from the survivor shares of the last one (see PosePipeline.adapt)"""
         share = float(np.mean([float(n) / max(p.idx.shape[0], 1) for n, p in zip(n_survs, self.pipes)]))
-        if share > self.FULL_FIRST_ON:
-            self.full_first = True
-        elif share < self.FULL_FIRST_OFF:
-            self.full_first = False
+        self.full_first = chains.next_form(self.full_first, share)
 
     def release(self):
         self.tensors = None

@@ -210,3 +210,36 @@ def test_runner_chains_equal_per_instance_runs(oracle, golden, dev):
         obj = objects[j]
         o = oracle.estimate_pose(obj["pc"], obj["normals"], obj["feat"], obj["point_idxs"], sd, ocfg_of(obj["cfg"]), obj["u_tr"], obj["u_rot"], sph)
         assert int(want[j, 12]) == o["argmax"] and int(want[j, 14]) == int(o["mask"].sum())
+
+
+def test_evicted_pipelines_take_their_chains(dev):
+    """a pipeline cache smaller than one batch (six pipelines wanted, four kept): every run evicts pipelines that are members of
+    chains.  The chains go with them -- none left in the cache has a member outside the pipeline cache -- and the records stay those
+    of per-instance runs bit for bit."""
+    from cppf_amd.batch import BatchPoseRunner
+    encs = {c: make_encoder(seeded_sd(0, 4.0), dev) for c in NOCS_CATEGORIES[:3]}
+    rng = np.random.default_rng(0)
+    objects = []
+    for j in range(6):
+        n = int(rng.integers(200, 1400))
+        ob = syn.make_object(NOCS_CATEGORIES[j % 3], n, 500 + j)
+        idx = rng.integers(0, n, (4096, 2)).astype(np.int64)
+        u_tr, u_rot = syn.make_uniforms(4096, 500 + j)
+        objects.append(dict(pc=ob["pc"], normals=ob["normals"], feat=ob["feat"], point_idxs=idx, u_tr=u_tr, u_rot=u_rot, cfg=ob["cfg"]))
+    want = BatchPoseRunner(encs, dev, chain_len=1, n_bucket=512).run(objects).cpu().numpy()
+    runner = BatchPoseRunner(encs, dev, chain_len=2, max_pipelines=4, n_bucket=512)
+    def run_and_check(objs, rows, rep):
+        np.testing.assert_array_equal(runner.run(objs).cpu().numpy(), rows)
+        assert len(runner._pipes) <= 4
+        live = {id(p) for p in runner._pipes.values()}
+        assert all(id(p) in live for c in runner._chains.values() for p in c.pipes), rep
+    for rep in range(3):                        # (every pipeline is evicted before its combination comes up again)
+        run_and_check(objects, want, rep)
+    # the first four objects alone fit the cache: their two chains are captured on the second run, and the whole batch then evicts
+    # the members of the older one (the third group's two pipelines take their places)
+    for rep in (3, 4):
+        run_and_check(objects[:4], want[:4], rep)
+    captured = list(runner._chains.values())
+    assert len(captured) >= 2
+    run_and_check(objects, want, 5)
+    assert any(all(c is not kept for kept in runner._chains.values()) for c in captured)
