@@ -63,14 +63,22 @@ __device__ __forceinline__ int bv_push(uint32_t* tail, const bool pass, const ui
 // The run is a superset (approximate acos / atan2 with their error bounds, one index of margin on either side, K lowered
 // by the deviations of |offset|^2 from rho^2: roundings and the 1e-7 regulariser, which shortens ab by 1e-7 / L -- pairs
 // closer than 1e-3, L2 = |a - b|^2 < 1e-6, scan everything); each candidate still goes through the reference's exact arithmetic
-// and the first one in index order wins, so the result is the reference's.  On inputs where every pair survives stage 1 (a trained
+// and the first one in index order wins, so the result is the reference's.
+// K is lowered once more for what the loop's OWN rounding does to :101.  The loop tests |fl(fl(cc + offset) - gt)| against tol:
+// the sum is rounded at the size of the COORDINATES, half an ulp of up to cmax + rho per component (cmax = the largest |cc_i|),
+// which moves the distance by up to sqrt(3) 2^-24 (cmax + rho) < dc = 2e-7 (cmax + rho) -- an absolute error that the terms
+// relative to |w|, rho and tol above do not see: with a centre 8 away and tol = 6e-3 it is 1.5e-4 tol.  A sample whose exact
+// distance is up to tol + dc can therefore pass, tol^2 may grow by (2 tol + dc) dc, and K goes down by (tol + dc) dc.  (Without
+// this term the arc was empty for pairs whose one passing sample lay within 1e-4 tol of the cut, at |gt| = 8.5 and res <= 4e-3:
+// tests/test_gpu_backvote_edges.py, 3 to 8 pairs of 13 888.)  On inputs where every pair survives stage 1 (a trained
 // network) the full loop was the kernel: 100 us at C2, a lane walking on average 36 rotations and a wave its slowest lane's.
-__device__ __forceinline__ int2 bv_arc(const float L2, const f3 w, const f3 x, const f3 y, const float tol, const int n)
+__device__ __forceinline__ int2 bv_arc(const float L2, const f3 w, const f3 x, const f3 y, const float tol, const int n, const float cmax)
 {
     const float A_ = dot3(w, x), B_ = dot3(w, y), w2 = dot3(w, w), rho2 = dot3(x, x);
     int lo = 0, cnt = n;
     const float M = __builtin_amdgcn_sqrtf(A_ * A_ + B_ * B_);
-    const float K = 0.5f * (w2 + rho2 - tol * tol) - (3e-4f * rho2 + 4e-6f * (w2 + rho2 + tol * tol));
+    const float dc = 2e-7f * (cmax + __builtin_amdgcn_sqrtf(rho2));
+    const float K = 0.5f * (w2 + rho2 - tol * tol) - (3e-4f * rho2 + 4e-6f * (w2 + rho2 + tol * tol) + (tol + dc) * dc);
     if (n > 0 && L2 >= 1e-6f && M > 1e-30f) {
         const float c = K * __builtin_amdgcn_rcpf(M);
         if (c > 1.0005f) {
@@ -90,6 +98,9 @@ __device__ __forceinline__ int2 bv_arc(const float L2, const f3 w, const f3 x, c
     }
     return make_int2(lo, cnt);
 }
+
+// cmax of bv_arc: the largest coordinate of the circle's centre
+__device__ __forceinline__ float bv_cmax(const f3 cc) { return fmaxf(fmaxf(fabsf(cc.x), fabsf(cc.y)), fabsf(cc.z)); }
 
 // The two tests of one candidate rotation, pc = cc + offset: the reference's :101 and :103-107.  The first candidate in index
 // order that passes both ends the loop (:109) with found = -offset (:108); a survivor (nocs/inference.py:230) has found != 0.

@@ -195,7 +195,7 @@ __device__ __forceinline__ void backvote_body(const float* __restrict__ points,
         const int n = bv_rot_count(odist, res, n_rots);
         const int tbase = n * (n - 1) / 2;
         const f3 dd = sub3(a, ld3(points, ij.y));
-        const int2 arc = bv_arc(dot3(dd, dd), sub3(gt, cc), x, y, tol, n);
+        const int2 arc = bv_arc(dot3(dd, dd), sub3(gt, cc), x, y, tol, n, bv_cmax(cc));
         const int lo = arc.x, cnt = arc.y;
         const int p1 = max(0, lo + cnt - n);     // candidates that wrap past n - 1 come first in index order: 0 .. p1 - 1
         for (int kk = 0; kk < cnt; ++kk) {
@@ -265,14 +265,14 @@ __device__ __forceinline__ void backvote_body(const float* __restrict__ points,
                         pass = (odist * rinv_res * 6.2831855f >= 0.9999f) && !(dist > tol + 2e-4f * mag + 1e-6f + squash);
                         if (!pass) finish(idx, f3{0.f, 0.f, 0.f});
                     } else {   // (nearly) coincident points: the exact test decides what is degenerate
+                        // No screen here: below |a - b| = 3.2e-7 the regulariser makes ab = (a - b) / (L + 1e-7) a quarter and more
+                        // shorter than a unit vector, y = x cross ab with it, and the samples lie on an ellipse with half-axes rho and
+                        // rho |ab|: | |cc - gt| - rho | is no lower bound of their distance from gt (the test this branch used to make
+                        // lost a pair with rho = 4 tol whose sample along y passed).  Such pairs are as good as absent from real lists
+                        // and stage 2 scans their whole circle (L2 < 1e-6).
                         f3 a, ab, xd;
                         if (pair_frame(points, ij.x, ij.y, a, ab, xd)) {
-                            const float proj_len = o.x, odist = o.y;
-                            const f3 cc = sub3(a, scl3(ab, proj_len));
-                            const f3 x = scl3(xd, odist);
-                            const int n = bv_rot_count(odist, res, n_rots);
-                            const float dc = len3(sub3(cc, gt)), rho = len3(x);
-                            pass = n > 0 && !(fabsf(dc - rho) > tol + 1e-5f * (dc + rho + tol) + 1e-7f);
+                            pass = bv_rot_count(o.y, res, n_rots) > 0;
                             if (!pass) finish(idx, f3{0.f, 0.f, 0.f});
                         } else if (mask) {   // degenerate pair: out_offsets keeps the caller's value (:87 returns early)
                             const float* oo = out_offsets ? out_offsets + 3 * idx : nullptr;

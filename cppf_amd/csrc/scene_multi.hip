@@ -55,7 +55,7 @@ __global__ __launch_bounds__(256) void backvote_multi_kernel(const float* __rest
         const int n = bv_rot_count(odist, res, n_rots);
         const int tbase = n * (n - 1) / 2;
         const f3 dd = sub3(a, ld3(points, ij.y));
-        const int2 arc = bv_arc(dot3(dd, dd), sub3(gt, cc), x, y, tol, n);
+        const int2 arc = bv_arc(dot3(dd, dd), sub3(gt, cc), x, y, tol, n, bv_cmax(cc));
         const int lo = arc.x, cnt = arc.y;
         const int p1 = max(0, lo + cnt - n);     // candidates that wrap past n - 1 come first in index order
         for (int kk = 0; kk < cnt; ++kk) {
@@ -95,8 +95,9 @@ __global__ __launch_bounds__(256) void backvote_multi_kernel(const float* __rest
             for (int u = 0; u < BV_U; ++u) {
                 const int64_t idx = base + u * 64 + lane;
                 // the pair's part of stage 1, once: mode 0 = no centre can pass, 1 = the approximate circle test, 2 = (nearly)
-                // coincident points, where the exact frame decides what is degenerate.  (backvote_body's two screens, derived
-                // there, split into this part and the centre's below: a change to a formula or a bound belongs in both.)
+                // coincident points, where the exact frame decides what is degenerate and every centre goes on to stage 2.
+                // (backvote_body's two screens, derived there, split into this part and the centre's below: a change to a formula
+                // or a bound belongs in both.)
                 int mode = 0;
                 f3 cc = {0.f, 0.f, 0.f}, ax = {0.f, 0.f, 0.f};
                 float rho = 0.f, squash = 0.f;
@@ -117,13 +118,7 @@ __global__ __launch_bounds__(256) void backvote_multi_kernel(const float* __rest
                     } else {
                         const int2 ij = ij_[u];
                         f3 a, ab, xd;
-                        if (pair_frame(points, ij.x, ij.y, a, ab, xd)) {
-                            const float proj_len = o.x, odist = o.y;
-                            cc = sub3(a, scl3(ab, proj_len));
-                            const int n = bv_rot_count(odist, res, n_rots);
-                            rho = len3(scl3(xd, odist));
-                            mode = n > 0 ? 2 : 0;
-                        }
+                        if (pair_frame(points, ij.x, ij.y, a, ab, xd)) mode = bv_rot_count(o.y, res, n_rots) > 0 ? 2 : 0;
                     }
                 }
                 if (__any(mode != 0)) {
@@ -139,8 +134,7 @@ __global__ __launch_bounds__(256) void backvote_multi_kernel(const float* __rest
                             const float mag = __builtin_amdgcn_sqrtf(w2) + rho + tol;
                             pass = !(dist > tol + 2e-4f * mag + 1e-6f + squash);
                         } else if (mode == 2) {
-                            const float dc = len3(sub3(cc, gt));
-                            pass = !(fabsf(dc - rho) > tol + 1e-5f * (dc + rho + tol) + 1e-7f);
+                            pass = true;       // no screen for these: their samples lie on an ellipse (backvote_body, stage 1)
                         }
                         if (!__any(pass)) continue;
                         qn += bv_push(q + qn, pass, ((uint32_t)idx << BVM_K_BITS) | (uint32_t)k);
