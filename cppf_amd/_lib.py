@@ -139,6 +139,9 @@ _SIGS = {
     # depth segments (csrc/segments.hip): connected components of a depth frame, RANSAC plane fit; no workspace, all scratch is output
     "cppf_depth_segments": (C.c_int, [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     "cppf_plane_ransac": (C.c_int, [vp, i64, i32, f32, C.c_uint64, vp, vp, vp, vp]),
+    # concave creases of a depth frame (csrc/concave.hip): per-pixel plane fits and the edge mask; no workspace
+    "cppf_concave_edges": (C.c_int, [vp, vp, i32, i32, C.c_double, C.c_double, C.c_double, C.c_double, i32, i32, i32, i32, i32, C.c_double,
+                                     C.c_double, vp, vp, vp, vp]),
     "cppf_knn": (C.c_int, [vp, vp, i32, i32, vp, vp]),
     "cppf_frame_cloud_workspace_bytes": (sz, [i32, i32, i32, i32]),
     "cppf_frame_cloud_dyn": (C.c_int, [vp, i32, vp, i32, i32, i32, i32, vp, C.c_double, C.c_double, i32, i32, i32, vp, vp, vp, vp, vp, vp, sz, vp]),

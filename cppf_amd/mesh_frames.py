@@ -217,3 +217,150 @@ class MeshFrameSampler:
         depth, labels = M.render_instances(self._set, spec["inst_mesh"], spec["model_views"], cull=cull, fx=self.fx, fy=self.fy,
                                            width=self.width, height=self.height, znear=self.znear, device=dev)
         return self.frame(spec, depth, labels)
+
+
+MAX_INSTANCES = 65536                    # include/cppf.h: cppf_raster_instances' limit on K
+# the support of a tabletop frame in its own coordinates: the unit square of the xz plane, facing +y (counter-clockwise seen from +y)
+PLANE_MESH = (np.array([[-1.0, 0.0, -1.0], [-1.0, 0.0, 1.0], [1.0, 0.0, 1.0], [1.0, 0.0, -1.0]]), np.array([[0, 1, 2], [0, 2, 3]], np.int32))
+
+
+def footprint_radius(vertices, faces, bmin, bmax):
+    """the radius of the circle about the box centre, in the mesh's xz plane, that holds every vertex some face references"""
+    used = np.asarray(vertices, np.float64)[np.unique(np.asarray(faces))]
+    c = (np.asarray(bmin) + np.asarray(bmax)) / 2
+    return float(np.sqrt(((used[:, [0, 2]] - c[[0, 2]]) ** 2).sum(1).max()))
+
+
+def plane_quad(up, point, fx, fy, width, height, far, margin=1.1, pad=0.05):
+    """The support of a tabletop frame: (centre f64[3], e1, e2 f64[3], half f64[2]) of the rectangle centre +- half[0] e1 +- half[1]
+    e2 in the plane up . (p - point) = 0 (camera frame of the render, the camera at the origin ABOVE the plane).  The part of the
+    plane inside the view frustum up to the depth `far` is a convex polygon whose corners are the hits of the four corner rays (where
+    they reach the plane within `far`) and the crossings of the far rectangle's four sides with the plane; the rectangle is their
+    bounding box along e1 = the image's horizontal turned into the plane and e2 = up x e1, each half-side times `margin` plus `pad`
+    metres."""
+    up, point = np.asarray(up, np.float64), np.asarray(point, np.float64)
+    e1 = np.array([1.0, 0.0, 0.0]) - up[0] * up
+    e1 /= np.linalg.norm(e1)
+    e2 = np.cross(up, e1)
+    h = float(up @ point)                                                     # up . p = h on the plane; h < 0: the camera is above it
+    tx, ty = width / (2.0 * fx), height / (2.0 * fy)
+    corners = [far * np.array([sx * tx, sy * ty, -1.0]) for sx, sy in ((-1, -1), (1, -1), (1, 1), (-1, 1))]
+    pts = []
+    for k, c in enumerate(corners):
+        s = up @ c
+        if s < 0 and h / s <= 1.0:                                            # the corner ray reaches the plane within `far`
+            pts.append(c * (h / s))
+        a, b = c, corners[(k + 1) % 4]                                        # one side of the far rectangle
+        sa, sb = up @ a - h, up @ b - h
+        if (sa < 0) != (sb < 0):
+            pts.append(a + (b - a) * (sa / (sa - sb)))
+    if not pts:
+        raise ValueError("the support plane does not cross the view frustum within the far range")
+    q = np.asarray(pts) - point
+    a, b = q @ e1, q @ e2
+    mid = np.array([(a.min() + a.max()) / 2, (b.min() + b.max()) / 2])
+    half = np.array([(a.max() - a.min()) / 2, (b.max() - b.min()) / 2]) * margin + pad
+    return point + mid[0] * e1 + mid[1] * e2, e1, e2, half
+
+
+class TabletopFrameSampler(MeshFrameSampler):
+    """Frames of `n_objects` meshes STANDING on a table: one support plane under all of them, every object upright on it (its mesh's
+    +y along the table's up axis, the bottom face of its box in the plane), objects that may touch (min_gap = 0).  Constructor and
+    seeded-generator contract as MeshFrameSampler's; min_gap: the least distance in metres between two footprint circles.
+
+    draw() is host work only.  From ONE np.random.Generator(seed) it draws, in this order:
+      1. the camera tilt, once per frame: x = rng.uniform(25, 65) degrees, yy = rng.uniform(-15, 15) degrees (meshes.draw_pose's NOCS
+         ranges); Rt = roty(yy) . rotx(x), composed as draw_pose composes them (in the other order yy would only turn the table
+         about its own up axis), takes table coordinates into the render's camera frame; up = Rt (0, 1, 0);
+      2. the table: d0 = rng.uniform(the far half of z_range); the plane passes through (0, 0, -d0) on the optical axis with the
+         normal `up` (the near half would leave no room in the view for an object of a few decimetres);
+      3. object by object (j = 0 .. n_objects - 1): the category, the mesh and the scale as MeshFrameSampler draws them; the turn
+         about the table's up axis y = rng.uniform(0, 2 pi), R = Rt . roty(y); then the foot (the centre of the box's bottom face),
+         up to max_attempts times: the view ray (rng.uniform(-1, 1) W / (2 fx), rng.uniform(-1, 1) H / (2 fy), -1) -- a point drawn
+         uniformly over the image -- and foot = where it meets the plane (a ray that does not is a refusal).  When the footprint circle
+         (the scale times footprint_radius) lies closer than min_gap to the circle of an object placed before, the foot is moved away
+         from the first such object, along the line that joins the two feet, until the circles are min_gap (plus a nanometre)
+         apart: this is what makes objects touch at min_gap = 0.  The attempt is kept when every earlier circle is then at least
+         min_gap away and the bounding sphere (radius r = the scale times the mesh's bounding radius) about the box centre t = foot +
+         up . scale . (box height / 2) lies inside the view frustum to first order, as MeshFrameSampler keeps it: |t.x| <= d_t W / (2 fx)
+         - r, |t.y| <= d_t H / (2 fy) - r, d_t = -t.z in z_range.  max_attempts refusals in a row
+         raise RuntimeError.
+    The table is one more mesh (PLANE_MESH, appended to the mesh set) posed as plane_quad's rectangle with far = z_range[1]: wider
+    than the frustum at the far range.  sample() renders it as the LAST instance of the ONE render_instances call, so at equal depth
+    the objects win; afterwards its label (n_objects) becomes -1 and its depth stays.  It counts against the rasteriser's instance
+    cap: n_objects <= MAX_INSTANCES - 1.  sample() returns a MeshFrame of the n_objects objects (ground truth through
+    ground_truth) whose spec also holds `support`: the pixels the table kept (bool[H,W], device).  The same seed gives the same
+    frames bit for bit."""
+
+    def __init__(self, category_meshes, n_objects, device=None, seed=0, cfgs=None, z_range=Z_RANGE, max_attempts=100, min_gap=0.0,
+                 fx=M.FX, fy=M.FY, width=M.WIDTH, height=M.HEIGHT, znear=M.ZNEAR, synset_names=None):
+        if n_objects > MAX_INSTANCES - 1:
+            raise ValueError(f"{n_objects} objects and the table: one render takes at most {MAX_INSTANCES} instances")
+        if not (np.isfinite(min_gap) and min_gap >= 0):
+            raise ValueError(f"min_gap must be finite and >= 0, got {min_gap}")
+        super().__init__(category_meshes, n_objects, device, seed, cfgs, z_range, max_attempts, fx, fy, width, height, znear, synset_names)
+        self.min_gap = float(min_gap)
+        self.footprint = [footprint_radius(v, f, *b) for (v, f), b in zip(self.meshes, self.bounds)]
+        self.plane_mesh = len(self.meshes)                      # the table: the last mesh of the set, drawn by the last instance
+        self.meshes.append((PLANE_MESH[0].copy(), PLANE_MESH[1].copy()))
+
+    def draw(self):
+        """MeshFrameSampler.draw's dict for the n_objects objects (model_views and inst_mesh with the table's entry appended: K + 1
+        rows), plus tilt (x, yy), up, table_point, feet f64[K,3], footprints f64[K], quad (plane_quad's tuple)"""
+        rng, K = self.rng, self.n_objects
+        x, yy = rng.uniform(25 / 180 * np.pi, 65 / 180 * np.pi), rng.uniform(-15 / 180 * np.pi, 15 / 180 * np.pi)
+        Rt = M.roty(yy)[:3, :3] @ M.rotx(x)[:3, :3]
+        up = Rt[:, 1].copy()
+        d0 = rng.uniform((self.z_range[0] + self.z_range[1]) / 2, self.z_range[1])
+        o = np.array([0.0, 0.0, -d0])
+        cats, inst, scales, Rs, ts, radii, models, gts, feet, foots = [], [], [], [], [], [], [], [], [], []
+        for _ in range(K):
+            cat = self.categories[int(rng.integers(len(self.categories)))]
+            m = self.index[(cat, int(rng.integers(self.n_meshes[cat])))]
+            scale = rng.uniform(self.cfgs[cat].scale_range[0], self.cfgs[cat].scale_range[1])
+            R = Rt @ M.roty(rng.uniform(0, 2 * np.pi))[:3, :3]
+            bmin, bmax = self.bounds[m]
+            r, rho, rise = scale * self.radius[m], scale * self.footprint[m], scale * (bmax[1] - bmin[1]) / 2
+            for _ in range(self.max_attempts):
+                ray = np.array([rng.uniform(-1.0, 1.0) * self.width / (2 * self.fx), rng.uniform(-1.0, 1.0) * self.height / (2 * self.fy), -1.0])
+                if not up @ ray < 0:                                          # this ray never reaches the table
+                    continue
+                foot = ray * ((up @ o) / (up @ ray))
+                need = [rho + rho2 + self.min_gap for rho2 in foots]
+                near = [j for j, f2 in enumerate(feet) if np.linalg.norm(foot - f2) < need[j]]
+                if near:
+                    j, gap = near[0], np.linalg.norm(foot - feet[near[0]])
+                    if gap == 0.0:
+                        continue
+                    foot = feet[j] + (foot - feet[j]) * ((need[j] + 1e-9) / gap)
+                t = foot + up * rise
+                dt = -t[2]
+                if (all(np.linalg.norm(foot - f2) >= n2 for f2, n2 in zip(feet, need)) and self.z_range[0] <= dt <= self.z_range[1]
+                        and abs(t[0]) <= dt * self.width / (2 * self.fx) - r and abs(t[1]) <= dt * self.height / (2 * self.fy) - r):
+                    break
+            else:
+                raise RuntimeError(f"{self.max_attempts} placements in a row left the view or came too close to an object placed before")
+            cats.append(cat); inst.append(m); scales.append(scale); Rs.append(R); ts.append(t); radii.append(r); feet.append(foot); foots.append(rho)
+            models.append(M.model_matrix(R, t, scale, bmin, bmax))
+            gts.append(ground_truth(R, t, scale, bmin, bmax, cat in NOCS_CATEGORIES))
+        quad = plane_quad(up, o, self.fx, self.fy, self.width, self.height, self.z_range[1])
+        centre, e1, e2, half = quad
+        plane = np.eye(4)
+        # PLANE_MESH's x, y, z axes become e1, up and e1 x up = -e2 (right-handed: the winding survives), x and z scaled to the rectangle
+        plane[:3, 0], plane[:3, 1], plane[:3, 2], plane[:3, 3] = half[0] * e1, up, half[1] * np.cross(e1, up), centre
+        return dict(categories=cats, inst_mesh=np.asarray(inst + [self.plane_mesh], np.int32), scales=np.asarray(scales), Rs=np.asarray(Rs),
+                    ts=np.asarray(ts), radii=np.asarray(radii), model_views=np.asarray(models + [plane]),
+                    centers=np.asarray([g[0] for g in gts]), gt_Rs=np.asarray([g[1] for g in gts]),
+                    half_extents=np.asarray([g[2] for g in gts]), tilt=(x, yy), up=up, table_point=o, feet=np.asarray(feet),
+                    footprints=np.asarray(foots), quad=quad)
+
+    def sample(self, cull=True):
+        M.require_cuda()
+        dev = self.dev or torch.device("cuda", 0)
+        if self._set is None:
+            self._set = M.mesh_set(self.meshes, dev)
+        spec = self.draw()
+        depth, labels = M.render_instances(self._set, spec["inst_mesh"], spec["model_views"], cull=cull, fx=self.fx, fy=self.fy,
+                                           width=self.width, height=self.height, znear=self.znear, device=dev)
+        spec["support"] = labels == self.n_objects
+        return self.frame(spec, depth, torch.where(spec["support"], torch.full_like(labels, -1), labels))

@@ -7,11 +7,14 @@ points of a pair from ONE segment.  Everything here is opt-in.
   support_mask     up to n_planes dominant planes of a frame's back-projected pixels, one after the other -> the pixels off all of them
   depth_segments   cppf_depth_segments: connected components of the depth image (4-neighbours, a depth-discontinuity rule), the
                    components of min_pixels..max_pixels pixels numbered by their smallest pixel index
-  frame_segments   support_mask, then depth_segments: one dict a caller hands to scene_frame / frame_detections (segments=)
+  concave_edges    cppf_concave_edges: a plane fit per pixel and the pixels across which the fitted surfaces turn
+                   towards each other -- where an object stands on its support or leans on a neighbour; needs no plane model
+  frame_segments   support_mask and / or concave_edges, then depth_segments: one dict a caller hands to scene_frame /
+                   frame_detections (segments=)
   segment_inputs   scene_stage.cloud_inputs on labelled_frame_cloud's cloud (scene_stage.scene_cloud with the segments' label image),
                    the pairs drawn inside segments (scene_training.sample_scene_pairs)
 
-The kernels are csrc/segments.hip's; the distance tests and compactions of support_mask are torch."""
+The kernels are csrc/segments.hip's and csrc/concave.hip's; the distance tests and compactions of support_mask are torch."""
 import numpy as np
 import torch
 
@@ -22,6 +25,8 @@ F32, I32, I16, U8 = torch.float32, torch.int32, torch.int16, torch.uint8
 SEGMENTS_MAX = 1024                       # include/cppf.h: CPPF_SEGMENTS_MAX
 PLANE_MAX_HYPOTHESES = 1024               # include/cppf.h: CPPF_PLANE_MAX_HYPOTHESES
 MAX_PIXELS = 1 << 24
+CONCAVE_MAX_RADIUS, CONCAVE_MAX_STEP = 8, 16  # include/cppf.h: CPPF_CONCAVE_MAX_RADIUS, CPPF_CONCAVE_MAX_STEP
+CONCAVE_COS_MAX = float(np.cos(np.deg2rad(30.0)))
 
 
 def depth_tensor(depth, dev=None):
@@ -174,19 +179,101 @@ def depth_segments(depth, valid=None, tol_mm=10, slope_permille=10, min_pixels=2
                 n_components=n_comp, n_live=n_live)
 
 
+def concave_options(radius=3, step=4, tol_mm=10, slope_permille=10, min_count=None, cos_max=CONCAVE_COS_MAX, span_max=0.08):
+    """cppf_concave_edges' options with their defaults filled in (min_count None: a third of the window, (2 radius + 1)^2 // 3)"""
+    r = int(radius)
+    return dict(radius=r, step=int(step), tol_mm=int(tol_mm), slope_permille=int(slope_permille),
+                min_count=(2 * r + 1) ** 2 // 3 if min_count is None else int(min_count), cos_max=float(cos_max), span_max=float(span_max))
+
+
+def check_concave_args(H, W, intrinsics, radius, step, tol_mm, slope_permille, min_count, cos_max, span_max):
+    """cppf_concave_edges' refusals that need no device, as ValueError; returns (fx, fy, cx, cy) as floats"""
+    K = np.asarray(intrinsics, np.float64)
+    if K.shape != (3, 3):
+        raise ValueError(f"concave_edges: intrinsics must be a 3x3 matrix, got {K.shape}")
+    fx, fy, cx, cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+    if not (np.isfinite([fx, fy, cx, cy]).all() and fx > 0 and fy > 0):
+        raise ValueError(f"concave_edges: fx, fy finite and > 0, cx, cy finite, got {fx}, {fy}, {cx}, {cy}")
+    if int(H) < 1 or int(W) < 1 or int(H) * int(W) > MAX_PIXELS:
+        raise ValueError(f"concave_edges takes frames of 1..2^24 pixels, got {H} x {W}")
+    if not 1 <= int(radius) <= CONCAVE_MAX_RADIUS or not 1 <= int(step) <= CONCAVE_MAX_STEP:
+        raise ValueError(f"concave_edges: radius 1..{CONCAVE_MAX_RADIUS} and step 1..{CONCAVE_MAX_STEP}, got {radius}, {step}")
+    if not 0 <= int(tol_mm) <= 65535 or not 0 <= int(slope_permille) <= 1000:
+        raise ValueError(f"concave_edges: tol_mm 0..65535 and slope_permille 0..1000, got {tol_mm}, {slope_permille}")
+    if int(min_count) < 3:
+        raise ValueError(f"concave_edges: a plane takes min_count >= 3 pixels, got {min_count}")
+    if not -1.0 < float(cos_max) < 1.0:
+        raise ValueError(f"concave_edges: cos_max must lie inside (-1, 1), got {cos_max}")
+    if not (np.isfinite(float(span_max)) and float(span_max) > 0):
+        raise ValueError(f"concave_edges: span_max must be finite and > 0, got {span_max}")
+    return fx, fy, cx, cy
+
+
+def concave_edges_device(depth, intrinsics, valid=None, radius=3, step=4, tol_mm=10, slope_permille=10, min_count=None,
+                         cos_max=CONCAVE_COS_MAX, span_max=0.08, out=None):
+    """cppf_concave_edges, enqueued on the current stream with nothing read back: dict(edge u8[H,W], normal f64[H,W,3], counts i32[4] =
+    {edge pixels, pixels with a fit, live pixels, 0}) on depth's device.  depth: i16[H,W] device (depth_tensor's form), valid: u8[H,W]
+    device or None, intrinsics: the 3x3 matrix of the integer pixel coordinates; out: such a dict to write into."""
+    dev = depth.device
+    H, W = depth.shape
+    o = concave_options(radius, step, tol_mm, slope_permille, min_count, cos_max, span_max)
+    fx, fy, cx, cy = check_concave_args(H, W, intrinsics, **o)
+    out = out or dict(edge=torch.empty((H, W), dtype=U8, device=dev), normal=torch.empty((H, W, 3), dtype=torch.float64, device=dev),
+                      counts=torch.empty(4, dtype=I32, device=dev))
+    call("cppf_concave_edges", dev, depth, valid, H, W, fx, fy, cx, cy, o["radius"], o["step"], o["tol_mm"], o["slope_permille"],
+         o["min_count"], o["cos_max"], o["span_max"], out["edge"], out["normal"], out["counts"])
+    return out
+
+
+def valid_tensor(valid, d):
+    """a `valid` mask ([H,W] bool / uint8, numpy or device, or None) as u8[H,W] on the device of the depth tensor d"""
+    if valid is None:
+        return None
+    if isinstance(valid, np.ndarray):
+        valid = torch.from_numpy(np.ascontiguousarray(valid.astype(np.uint8))).to(d.device)
+    if isinstance(valid, torch.Tensor) and valid.dtype == torch.bool:
+        valid = valid.to(U8)
+    valid = canon(valid, U8, d.device, "valid")
+    if tuple(valid.shape) != tuple(d.shape):
+        raise ValueError(f"valid {tuple(valid.shape)} and depth {tuple(d.shape)} must be the same [H,W]")
+    return valid
+
+
+def concave_edges(depth, intrinsics, valid=None, **options):
+    """The concave creases of a depth frame (include/cppf.h "Concave edges"): a plane is fitted to every live pixel's (2 radius + 1)^2
+    window (pixels within tol_mm + slope_permille z / 1000 per pixel of distance; at least min_count of them), and a live pixel is an
+    edge when the fitted surfaces `step` pixels to either side of it, horizontally or vertically, are at most span_max metres apart,
+    differ by more than acos(cos_max) and turn towards each other.  depth [H,W]: numpy uint16 millimetres or the device tensor of
+    their int16 bits; valid as depth_segments takes it.  Returns dict(edge u8[H,W], normal f64[H,W,3]: device; n_edge, n_fit, n_live:
+    ints; options).  One read-back of the counts."""
+    d = depth_tensor(depth, valid.device if isinstance(valid, torch.Tensor) and valid.is_cuda and isinstance(depth, np.ndarray) else None)
+    out = concave_edges_device(d, intrinsics, valid_tensor(valid, d), **options)
+    n_edge, n_fit, n_live, _ = (int(v) for v in out["counts"].cpu().numpy())
+    return dict(edge=out["edge"], normal=out["normal"], n_edge=n_edge, n_fit=n_fit, n_live=n_live, options=concave_options(**options))
+
+
 def frame_segments(depth, intrinsics, n_planes=2, n_hyp=256, thresh=0.01, band=0.015, min_frac=0.05, seed=0, tol_mm=10, slope_permille=10,
-                   min_pixels=200, max_pixels=0, capacity=256):
+                   min_pixels=200, max_pixels=0, capacity=256, concave=None):
     """support_mask (skipped at n_planes = 0: frames with no background) and then depth_segments on what it leaves.  Returns one
     dict: labels i32[H,W], sizes, first (device), n_segments, n_components, valid (u8[H,W] device, or None at n_planes = 0), planes
-    (list of f32[4]) and options (the arguments above): what scene_frame / frame_detections take as segments=."""
+    (list of f32[4]) and options (the arguments above): what scene_frame / frame_detections take as segments=.
+    concave: None, or a dict of concave_edges' options ({} for its defaults).  The creases of the frame (concave_edges on the whole
+    frame, no mask) are then cut out as well: valid = support_mask's (all ones at n_planes = 0) AND edge == 0.  The crease pixels
+    stay unlabelled (-1); labels are not grown back over the cut band.  The dict gains edge (u8[H,W] device) and concave (the options
+    with their defaults filled in); without concave= it has exactly the keys above."""
     options = dict(n_planes=int(n_planes), n_hyp=int(n_hyp), thresh=float(thresh), band=float(band), min_frac=float(min_frac), seed=int(seed),
                    tol_mm=int(tol_mm), slope_permille=int(slope_permille), min_pixels=int(min_pixels), max_pixels=int(max_pixels),
                    capacity=int(capacity))
     d = depth_tensor(depth)
     valid, planes = (None, []) if int(n_planes) == 0 else support_mask(d, intrinsics, n_planes, n_hyp, thresh, band, min_frac, seed)
+    extra = {}
+    if concave is not None:
+        c = concave_edges_device(d, intrinsics, None, **concave)
+        valid = (c["edge"] == 0).to(U8) if valid is None else valid * (c["edge"] == 0).to(U8)
+        extra = dict(edge=c["edge"], concave=concave_options(**concave))
     s = depth_segments(d, valid, tol_mm, slope_permille, min_pixels, max_pixels, capacity)
     return dict(labels=s["labels"], sizes=s["sizes"], first=s["first"], n_segments=s["n_segments"], n_components=s["n_components"],
-                valid=valid, planes=planes, options=options)
+                valid=valid, planes=planes, options=options, **extra)
 
 
 def segment_labels(segments):
@@ -244,4 +331,4 @@ def segment_inputs(depth, intrinsics, point_encoder, cfg, n_pairs, seed, segment
 
 
 __all__ = ["plane_ransac", "support_mask", "depth_segments", "frame_segments", "segment_inputs", "labelled_frame_cloud", "segment_members",
-           "depth_tensor", "off_planes"]
+           "depth_tensor", "off_planes", "concave_edges", "concave_edges_device", "concave_options", "check_concave_args"]

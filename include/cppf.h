@@ -1327,6 +1327,50 @@ int cppf_depth_segments(const int16_t* depth, const uint8_t* valid, int H, int W
 int cppf_plane_ransac(const float* points, int64_t n_points, int n_hyp, float thresh, unsigned long long seed, float* planes,
                       int32_t* counts, int32_t* best, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Concave edges (csrc/concave.hip; additive, ABI version unchanged): the pixels of a depth frame across which the surface turns
+ * TOWARDS itself -- where an object stands on its support or leans on a neighbour; an object's own edges are convex.  `edge == 0`,
+ * ANDed into cppf_depth_segments' `valid`, cuts the components there (cppf_amd/segments.py: frame_segments(concave=)).  The
+ * reference has nothing of the kind, so the definition is this project's; tests/concave_ref.py restates it in numpy and is held to a
+ * loop-per-pixel brute force.  No workspace (`normal` carries the fits between the launches), no allocation, no host
+ * synchronisation, integer atomics only: the same inputs give the same bits, and the call can be captured in a graph.
+ *
+ * cppf_concave_edges.  depth device [H,W]: the int16 bits of the uint16 millimetres, compared as UNSIGNED; valid device u8[H,W] or
+ *   NULL; fx, fy, cx, cy: the pinhole intrinsics of the INTEGER pixel coordinates (u = column, v = row).  Outputs, device, every
+ *   byte written: edge u8[H,W] (0 / 1), normal f64[H,W,3] (unit, or 0 0 0 where there is no fit), counts i32[4] = {edge pixels,
+ *   pixels with a fit, live pixels, 0}.
+ *   1. A pixel is LIVE when depth > 0 and (valid is NULL or valid[p] != 0).  z0 = the depth of a live pixel p.
+ *   2. Window, in integers: lim = tol_mm + (slope_permille * z0) / 1000 (floor).  The pixel q at offset (du, dv), both in [-radius,
+ *      radius], is ADMITTED when it lies inside the frame, is live and |zq - z0| <= lim * max(|du|, |dv|, 1); p admits itself.
+ *      Over the admitted pixels, with dz = zq - z0: n, Su = sum du, Sv = sum dv, Suu = sum du du, Suv = sum du dv, Svv = sum dv dv,
+ *      Sz = sum dz, Szu = sum dz du, Szv = sum dz dv.
+ *   3. Least squares dz ~ c0 + a du + b dv by Cramer's rule on [[n,Su,Sv],[Su,Suu,Suv],[Sv,Suv,Svv]] (c0,a,b) = (Sz,Szu,Szv): the
+ *      determinant D and the three numerator determinants are integers.  |dz| <= 65535 whatever tol_mm and slope_permille are (two
+ *      uint16 depths), so at radius 8 |D| < 5.8e10 and every numerator is under 3.9e15 < 2^53 (tests/concave_ref.py:
+ *      numerator_bound): int64 holds them and their conversion to fp64 is exact.  p HAS A PLANE when n >= min_count and D > 0; then
+ *      c0, a, b are ONE fp64 division each, and c = ((double)z0 + c0) / 1000.0, am = a / 1000.0, bm = b / 1000.0 (metres, metres
+ *      per pixel).  Without a plane c = am = bm = 0.
+ *   4. In fp64, one rounding per operation, no contraction, in exactly this order: xu = (double)u - cx, yv = (double)v - cy;
+ *      Pu = (c / fx + (xu * am) / fx, (yv * am) / fy, am);  Pv = ((xu * bm) / fx, c / fy + (yv * bm) / fy, bm)   (the tangents);
+ *      N = Pu x Pv, each component two products and one subtraction: (Pu.y Pv.z - Pu.z Pv.y, Pu.z Pv.x - Pu.x Pv.z, Pu.x Pv.y -
+ *      Pu.y Pv.x);  P = ((xu * c) / fx, (yv * c) / fy, c)   (the fitted surface point);
+ *      N is negated when (N.x P.x + N.y P.y) + N.z P.z > 0 (so that it faces the camera);  l = sqrt((N.x N.x + N.y N.y) + N.z N.z).
+ *   5. p HAS A FIT when l is finite and > 0 (c = am = bm = 0 gives l = 0); normal[p] = N / l (three divisions) then, 0 0 0 otherwise.
+ *   6. A live pixel p is an EDGE when, for the horizontal (e = (1, 0)) or the vertical (e = (0, 1)) axis, m = p - step e and q = p +
+ *      step e both lie inside the frame and have a fit, and with d = P(q) - P(m), g = N(q) - N(m):
+ *      (d.x d.x + d.y d.y) + d.z d.z <= span_max * span_max,  (N(m).x N(q).x + N(m).y N(q).y) + N(m).z N(q).z < cos_max,  and
+ *      (d.x g.x + d.y g.y) + d.z g.z < 0 -- the normals converge: the crease is concave.  Dead pixels are never edges; p itself
+ *      needs no fit.
+ *   CPPF_EINVAL (nothing is written): H or W < 1, H * W > 2^24, radius outside 1..CPPF_CONCAVE_MAX_RADIUS, step outside
+ *   1..CPPF_CONCAVE_MAX_STEP, tol_mm outside 0..65535, slope_permille outside 0..1000, min_count < 3, cos_max outside (-1, 1),
+ *   span_max not finite and > 0, fx or fy not finite and > 0, cx or cy not finite, a null pointer (valid aside).
+ * ------------------------------------------------------------------------------------------- */
+#define CPPF_CONCAVE_MAX_RADIUS 8
+#define CPPF_CONCAVE_MAX_STEP 16
+int cppf_concave_edges(const int16_t* depth, const uint8_t* valid, int H, int W, double fx, double fy, double cx, double cy, int radius,
+                       int step, int tol_mm, int slope_permille, int min_count, double cos_max, double span_max, uint8_t* edge,
+                       double* normal, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,13 @@ frame includes the segmentation.  Works with the plain --mask-free run and with 
 the mean number of segments per frame, and goes to profiles/segments_eval.json unless --out says otherwise.  Figures, no threshold.
 
     python scripts/eval_mesh_frames.py --procedural --weights bottle=... --weights can=... --weights camera=... --frames 20 --objects 4 --mask-free --segments
+
+--tabletop [--min-gap G] (any mode but --score agreement): the frames come from mesh_frames.TabletopFrameSampler -- the objects stand
+upright on one support plane and may touch (G = 0) -- instead of floating in empty space; the record gains `tabletop`.  Next to
+--segments: --planes N (= --seg-planes) removes up to N RANSAC planes first, --concave cuts the frame at its concave creases
+(segments.frame_segments(concave={})); both may be given.
+
+    python scripts/eval_mesh_frames.py --procedural --weights ... --frames 20 --objects 4 --tabletop --mask-free --segments --planes 1 --concave
 """
 import argparse
 import json
@@ -138,14 +145,20 @@ def _segments(args, fr, log):
         return {}
     from cppf_amd.segments import frame_segments
     seg = frame_segments(fr.depth_mm, fr.intrinsics, n_planes=args.seg_planes, min_pixels=args.seg_min_pixels, tol_mm=args.seg_tol_mm,
-                         slope_permille=args.seg_slope)
+                         slope_permille=args.seg_slope, concave={} if args.concave else None)
     log.append(seg["n_segments"])
     return dict(segments=seg, intra_frac=args.intra_frac)
 
 
 def _segments_record(args, log):
-    return dict(n_planes=args.seg_planes, min_pixels=args.seg_min_pixels, tol_mm=args.seg_tol_mm, slope_permille=args.seg_slope,
-                intra_frac=args.intra_frac, segments_per_frame_mean=float(np.mean(log)) if log else 0.0) if args.segments else None
+    if not args.segments:
+        return None
+    rec = dict(n_planes=args.seg_planes, min_pixels=args.seg_min_pixels, tol_mm=args.seg_tol_mm, slope_permille=args.seg_slope,
+               intra_frac=args.intra_frac, segments_per_frame_mean=float(np.mean(log)) if log else 0.0)
+    if args.concave:                                                          # (without the flag: the record it always was)
+        from cppf_amd.segments import concave_options
+        rec["concave"] = concave_options()
+    return rec
 
 
 def _mask_free(args, sampler, encs, pencs, dev):
@@ -375,7 +388,13 @@ def main():
                     "(seed + 1000) on which the bound is chosen")
     ap.add_argument("--segments", action="store_true", help="--mask-free: segment every frame on the device first and draw the pairs inside "
                     "the segments (DESIGN.md 3.7j)")
-    ap.add_argument("--seg-planes", type=int, default=0, help="--segments: planes removed before the labelling (0 suits rendered frames)")
+    ap.add_argument("--seg-planes", "--planes", type=int, default=0, help="--segments: planes removed before the labelling (0 suits rendered "
+                    "frames without a support)")
+    ap.add_argument("--concave", action="store_true", help="--segments: cut the frame at its concave creases before the labelling "
+                    "(segments.frame_segments(concave={}), DESIGN.md 3.7l)")
+    ap.add_argument("--tabletop", action="store_true", help="frames of objects standing on a support plane (mesh_frames.TabletopFrameSampler) "
+                    "instead of objects floating in empty space")
+    ap.add_argument("--min-gap", type=float, default=0.0, help="--tabletop: the least distance between two footprints in metres (0: contact)")
     ap.add_argument("--seg-min-pixels", type=int, default=200, help="--segments: the smallest component kept")
     ap.add_argument("--seg-tol-mm", type=int, default=10, help="--segments: the link rule's constant term")
     ap.add_argument("--seg-slope", type=int, default=10, help="--segments: the link rule's slope, per mille of the nearer depth")
@@ -397,6 +416,10 @@ def main():
         sys.exit("--refine belongs to the plain --mask-free run (no --nms, no --score agreement)")
     if args.segments and (not args.mask_free or verify_mode):
         sys.exit("--segments belongs to --mask-free (plain, --nms or --refine)")
+    if args.concave and not args.segments:
+        sys.exit("--concave belongs to --segments")
+    if args.tabletop and verify_mode:
+        sys.exit("--tabletop: the verification run tunes on a second sampler of floating objects; not wired up")
     if args.segments and args.out is None:
         args.out = os.path.join(ROOT, "profiles", "segments_eval.json")
     if args.refine and args.out is None:
@@ -429,7 +452,10 @@ def main():
             print(f"{c}: trained {args.train_steps} steps on {len(paths)} meshes in {trained[c]['seconds']:.1f} s, loss {losses[-1]:.4f}")
         else:
             sys.exit(f"category {c}: --weights {c}=FILE or --train-steps N")
-    sampler = MF.MeshFrameSampler(cat_paths, args.objects, device=dev, seed=args.seed)
+    if args.tabletop:
+        sampler = MF.TabletopFrameSampler(cat_paths, args.objects, device=dev, seed=args.seed, min_gap=args.min_gap)
+    else:
+        sampler = MF.MeshFrameSampler(cat_paths, args.objects, device=dev, seed=args.seed)
     if verify_mode:
         _verify_eval(args, cat_paths, sampler, encs, pencs, trained, weights, dev)
         tmp.cleanup()
@@ -447,6 +473,8 @@ def main():
                    note="a first figure: no threshold is attached to these APs")
         if args.segments:
             rec["segments"] = _segments_record(args, args.seg_log)
+        if args.tabletop:
+            rec["tabletop"] = dict(min_gap=args.min_gap)
         print(f"{args.frames} frames, {n_gt} ground truths, {n_prop} proposals; {rec['ms_per_frame_median']:.1f} ms per frame (all categories, NMS included)")
         for v, recs in results.items():
             iou_aps, pose_aps, _, _ = E.compute_degree_cm_mAP(recs, sampler.synset_names, None, deg, sh, iou, 0.1, True, device=dev)
@@ -500,6 +528,8 @@ def main():
                    note="a first figure: no threshold is attached to these APs")
         if args.segments:
             rec["segments"] = _segments_record(args, args.seg_log)
+        if args.tabletop:
+            rec["tabletop"] = dict(min_gap=args.min_gap)
         print(f"{args.frames} frames, {n_gt} ground truths, {n_prop} proposals; {rec['ms_per_frame_median']:.1f} ms per frame (all categories)")
         _tables(iou_aps, pose_aps, sampler.synset_names, list(cat_paths), deg, sh, rec)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
@@ -535,6 +565,8 @@ def main():
                procedural=bool(args.procedural), trained=trained, weights=weights, ground_truths=n_gt, instances_run=n_inst,
                instances_skipped_by_the_frame_path=n_none, ms_per_frame_median=float(np.median(steady)),
                ms_per_frame_mean=float(np.mean(steady)), evaluation_seconds=eval_s, iou_ap={}, pose_ap={})
+    if args.tabletop:
+        rec["tabletop"] = dict(min_gap=args.min_gap)
     print(f"{args.frames} frames, {n_gt} ground truths, {n_inst} instances with >= {args.min_pixels} pixels, {n_none} skipped by the frame "
           f"path; {rec['ms_per_frame_median']:.2f} ms per frame (median after the first 3), evaluation {eval_s:.2f} s")
     _tables(iou_aps, pose_aps, names, list(cat_paths), deg, sh, rec)
