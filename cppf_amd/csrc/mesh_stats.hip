@@ -6,8 +6,10 @@
 //   ms_area_kernel    one lane per face (all meshes): fp64 triangle area; a face index outside its mesh -> NaN + status bit 2
 //   ms_sum_kernel     one 1024-lane workgroup per mesh: total area S in the blocked order of cppf.h; S not in (0, inf) -> bit 1
 //   ms_norm_kernel    one lane per face: q_t = a_t / S
-//   ms_scan_kernel    one 1024-lane workgroup per mesh: the cumulative q (blocked order), E_t = min(N, round(C_t N)), E_last = N
-//   ms_points_kernel  one lane per point: its face (the first t with E_t > k), two Philox uniforms, the barycentric point
+//   ms_scan_kernel    one 1024-lane workgroup per mesh: the cumulative q (blocked order), E_t = min(N, round(C_t N)), E_last = N,
+//                     stored as its running maximum (E can step down by one behind a block boundary)
+//   ms_points_kernel  one lane per point: its face (the first t with E_t > k: a bisection of the running maximum), two Philox
+//                     uniforms, the barycentric point
 // cppf_mesh_vote_stats_batch (generate_target's targets_tr and the maxima of gen_stats.py):
 //   ms_bbox_kernel    one workgroup per mesh: bounding box, centre, diagonal, half extents (non-finite points -> status, NaN row)
 //   ms_pairs_kernel   workgroups x meshes: Philox pairs, the per-pair fp64 arithmetic, per-workgroup maxima
@@ -121,6 +123,7 @@ __global__ __launch_bounds__(MS_SCAN_THREADS) void ms_scan_kernel(const double* 
                                                                   int64_t N, const int32_t* __restrict__ status, int32_t* __restrict__ E)
 {
     __shared__ double part[MS_SCAN_THREADS];
+    __shared__ int32_t top[MS_SCAN_THREADS];
     const int m = blockIdx.x;
     if (status[m] != 0) return;
     const int64_t f0 = foff[m], F = foff[m + 1] - f0;
@@ -141,11 +144,27 @@ __global__ __launch_bounds__(MS_SCAN_THREADS) void ms_scan_kernel(const double* 
     __syncthreads();
     const double dN = (double)N;
     double c = part[threadIdx.x];
+    int32_t last = 0;
     for (int64_t t = t0; t < t1; ++t) {
         c = c + q[f0 + t];
         const double r = round(c * dN);                       // halves away from zero (std::round)
-        E[f0 + t] = t == F - 1 ? (int32_t)N : (int32_t)(r < dN ? r : dN);
+        last = t == F - 1 ? (int32_t)N : (int32_t)(r < dN ? r : dN);
+        E[f0 + t] = last;
     }
+    // What is stored is the running maximum of E, so that "the first t with E_t > k" is a bisection whatever it probes.  Inside a
+    // block E never decreases (q >= 0), but B_l+1 can round below the last C of block l (summed from B_l, not from zero), and
+    // the lower value stays for as long as zero-area faces follow, across blocks too.  So: the maximum over the blocks before
+    // this one (a max scan of their last E; an empty block counts 0), raised into this block's leading entries.
+    top[threadIdx.x] = last;
+    __syncthreads();
+    for (int s = 1; s < MS_SCAN_THREADS; s <<= 1) {
+        const int32_t o = (int)threadIdx.x >= s ? top[threadIdx.x - s] : 0;
+        __syncthreads();
+        top[threadIdx.x] = max(top[threadIdx.x], o);
+        __syncthreads();
+    }
+    const int32_t before = threadIdx.x > 0 ? top[threadIdx.x - 1] : 0;
+    for (int64_t t = t0; t < t1 && E[f0 + t] < before; ++t) E[f0 + t] = before;
 }
 
 __global__ __launch_bounds__(MS_THREADS) void ms_points_kernel(const double* __restrict__ verts, const int32_t* __restrict__ faces,
@@ -167,7 +186,8 @@ __global__ __launch_bounds__(MS_THREADS) void ms_points_kernel(const double* __r
         return;
     }
     const int64_t f0 = foff[m];
-    int64_t lo = 0, hi = foff[m + 1] - f0 - 1;                // the first face t with E_t > k (E_last = N > k)
+    int64_t lo = 0, hi = foff[m + 1] - f0 - 1;                // the first face t with E_t > k (E_last = N > k); E holds the running
+                                                              // maximum, so "E > k" is false, then true, wherever mid falls
     while (lo < hi) {
         const int64_t mid = (lo + hi) >> 1;
         if (E[f0 + mid] > k) hi = mid; else lo = mid + 1;
@@ -197,7 +217,7 @@ extern "C" int cppf_surface_sample_batch(const double* verts, const int32_t* fac
                                          size_t workspace_bytes, void* stream)
 {
     if (!verts || !faces || !vert_off_host || !face_off_host || !points || !status || n_meshes < 1 || n_points < 1 ||
-        n_points > 0x7fffffffll || first_mesh < 0 || first_mesh + n_meshes > 0xffffffffll)
+        n_points > 0x7fffffffll || first_mesh < 0 || first_mesh + n_meshes > 0x100000000ll)
         return CPPF_EINVAL;
     if (vert_off_host[0] != 0 || face_off_host[0] != 0) return CPPF_EINVAL;
     for (int m = 0; m < n_meshes; ++m) {
@@ -222,6 +242,8 @@ extern "C" int cppf_surface_sample_batch(const double* verts, const int32_t* fac
     if (e == hipSuccess) e = hipMemsetAsync(status, 0, (size_t)n_meshes * sizeof(int32_t), st);
     if (e != hipSuccess) return (int)e;
     const int64_t nfb = (n_faces_total + MS_THREADS - 1) / MS_THREADS;
+    // at most 8192 workgroups of 256 lanes a trip (tested: 2 100 000 faces in two meshes, the second one on both sides of face
+    // 2 097 152: tests/test_gpu_mesh_stats_edges.py)
     const unsigned gf = (unsigned)(nfb < 8192 ? nfb : 8192);
     ms_area_kernel<<<gf, MS_THREADS, 0, st>>>(verts, faces, voff, foff, n_meshes, n_faces_total, area, status);
     ms_sum_kernel<<<n_meshes, MS_SCAN_THREADS, 0, st>>>(area, foff, S, status);
@@ -235,6 +257,8 @@ extern "C" int cppf_surface_sample_batch(const double* verts, const int32_t* fac
 
 // ------------------------------------------------------------------------------------------------ vote statistics
 #define MS_PAIR_BLOCKS_TARGET 4096    // workgroups of one ms_pairs_kernel launch, about (>= 16 per CU), when the pairs allow
+                                      // (tested: three trips of 8 workgroups x 512 meshes, four of 14 x 300 and three of 4096 x 1,
+                                      // each with a ragged last trip and maxima in the later trips: tests/test_gpu_mesh_stats_edges.py)
 
 static int64_t ms_pair_blocks(int M, int64_t P)
 {
@@ -374,7 +398,7 @@ extern "C" int cppf_mesh_vote_stats_batch(const double* points, int n_meshes, in
                                           void* stream)
 {
     if (!points || !stats || !status || n_meshes < 1 || n_points < 1 || n_points > 0x7fffffffll || n_pairs < 1 ||
-        n_pairs > 0xffffffffll || first_mesh < 0 || first_mesh + n_meshes > 0xffffffffll)
+        n_pairs > 0xffffffffll || first_mesh < 0 || first_mesh + n_meshes > 0x100000000ll)
         return CPPF_EINVAL;
     const int64_t nb = ms_pair_blocks(n_meshes, n_pairs);
     if (nb * n_meshes > 0x7fffffffll) return CPPF_EINVAL;

@@ -99,7 +99,8 @@ def sample_surface_packed(verts, faces, vert_off, face_off, n_points, seed=0, fi
 def sample_surface_batch(meshes, n_points, seed=0, first_mesh=0, device=None):
     """cppf_surface_sample_batch on a list of (vertices f64[V,3], faces i32[F,3]) host arrays: (points f64[M,n,3], face_ids
     i32[M,n], status i32[M]) device tensors, no host synchronisation.  Mesh m draws as mesh index first_mesh + m.  status bit 1:
-    the mesh's total area is zero or not finite, bit 2: a face index outside its vertices (that mesh's points are NaN)."""
+    the mesh's total area is zero or not finite, bit 2: a face index outside its vertices (that mesh's points are NaN).  Bit 2
+    comes with bit 1 (status 3): the offending face's area is NaN and so is the total."""
     require_cuda()
     return sample_surface_packed(*upload_meshes(meshes, device), n_points, seed, first_mesh)
 

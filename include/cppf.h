@@ -1078,12 +1078,18 @@ int cppf_depth_points(const float* depth, int H, int W, const double* kinv_host,
  *   3. q_t = a_t / S.  Cumulative area, blocked as in 2: T_l = ((0 + q) + q) ... over block l, B_0 = 0, B_l = B_l-1 + T_l-1, and
  *      within block l C_t = ((B_l + q_first) + ...) + q_t left to right.  For F <= 1024 (K = 1) this is Open3D's serial chain.
  *   4. Counts (Open3D's rule): E_t = min(N, round(C_t * N)) with round = halves away from zero (std::round, not numpy's
- *      round-half-even), E_{F-1} = N.  Face t gets the points [E_{t-1}, E_t) (E_{-1} = 0): point k lies on the first face with
- *      E_t > k.  Zero-area faces get none.
+ *      round-half-even), E_{F-1} = N.  Point k lies on the FIRST face t with E_t > k (Open3D's loop, which moves on to the next
+ *      face once its point index has reached round(C_t N)).  E may DECREASE by one behind a block boundary: B_l+1 = B_l + T_l has
+ *      T_l summed from zero while the last C of block l was summed from B_l, the two roundings can differ by an ulp, and the lower
+ *      value stays for as long as zero-area faces follow.  So "first" is meant literally and is not a bisection of E; with
+ *      R_t = max(E_0 .. E_t) face t gets the points [R_{t-1}, R_t) (R_{-1} = 0), and the device stores R.  Zero-area faces get
+ *      none.
  *   5. Point k on face (v0, v1, v2): {w} = Philox({k, mesh, 2, 0}), r1 = u53(w.x, w.y), r2 = u53(w.z, w.w), s = sqrt(r1),
  *      a = 1 - s, b = s * (1 - r2), c = s * r2, p_j = (a * v0_j + b * v1_j) + c * v2_j.
  *   points device f64[M, n_points, 3]; face_ids device i32[M, n_points] (local face index; NULL = not written); status device
- *   i32[M] (0 = sampled).  A mesh with a status bit gets NaN points and face id -1; the other meshes are unaffected.
+ *   i32[M] (0 = sampled).  A mesh with a status bit gets NaN points and face id -1; the other meshes are unaffected.  Bit 2 never
+ *   comes alone: the NaN area of the offending face makes S NaN, so such a mesh has status 3.  A NaN / inf vertex that no face
+ *   references changes nothing.
  *   n_points <= 2^31 - 1, first_mesh + M <= 2^32.  Workspace >= cppf_surface_sample_workspace_bytes(M, fo[M]).  The offsets are
  *   copied to the device inside the call.
  *

@@ -1,8 +1,8 @@
 """numpy restatement of csrc/mesh_stats.hip (include/cppf.h "Mesh statistics"), operation for operation, and of gen_stats.py's
 per-pair arithmetic and reduction:
 
-- areas, the blocked sums of the stated order, the std::round counts, the Philox uniforms and the barycentric points of
-  cppf_surface_sample_batch;
+- areas, the blocked sums of the stated order, the std::round counts, the first-face rule, the status word, the Philox uniforms
+  and the barycentric points of cppf_surface_sample_batch;
 - the bounding box, the Philox pairs, generate_target's fp64 arithmetic and the maxima of cppf_mesh_vote_stats_batch;
 - gen_stats.py's aggregation over meshes (cppf_amd.mesh_stats.aggregate is the product's; this one is typed out again)."""
 import numpy as np
@@ -79,19 +79,35 @@ def counts_end(C, n):
     return E
 
 
+def sample_status(vertices, faces):
+    """the status word of cppf_surface_sample_batch for one mesh: bit 2 = a face index outside [0, nv); bit 1 = the blocked total S
+    is not in (0, inf).  A face with an index outside has the area NaN, so S is NaN and bit 2 never comes without bit 1."""
+    return _areas_total_status(np.asarray(vertices, np.float64), np.asarray(faces, np.int64))[2]
+
+
+def _areas_total_status(v, f):
+    outside = ((f < 0) | (f >= v.shape[0])).any(1)
+    with np.errstate(over="ignore", invalid="ignore"):
+        a = areas(v, np.where(outside[:, None], 0, f))
+        a[outside] = np.nan
+        S = blocked_total(a)
+    return a, S, (0 if S > 0 and S < np.inf else 1) | (2 if outside.any() else 0)
+
+
 def sample_surface(vertices, faces, n, seed, mesh=0):
     """cppf_surface_sample_batch for one mesh at batch index `mesh`: (points f64[n,3], face ids i64[n], E i64[F], ok).  ok False:
-    the total area is not in (0, inf) and the device writes NaN."""
+    the total area is not in (0, inf) and the device writes NaN.  E is returned as step 4 defines it and may decrease by one
+    behind a block boundary; the face of point k is the first t with E_t > k, which is the first t whose running maximum exceeds
+    k -- a bisection of the running maximum, never of E itself."""
     v = np.asarray(vertices, np.float64)
     f = np.asarray(faces, np.int64)
-    a = areas(v, f)
-    S = blocked_total(a)
-    if not (S > 0 and S < np.inf):
+    a, S, status = _areas_total_status(v, f)
+    if status != 0:
         return np.full((n, 3), np.nan), np.full(n, -1), None, False
     q = a / S
     E = counts_end(blocked_cumsum(q), n)
     k = np.arange(n)
-    t = np.searchsorted(E, k, side="right")                         # the first t with E_t > k
+    t = np.searchsorted(np.maximum.accumulate(E), k, side="right")  # the first t with E_t > k
     r1, r2 = MS.surface_uniforms(seed, mesh, n)
     s = np.sqrt(r1)
     wa, wb, wc = 1.0 - s, s * (1.0 - r2), s * r2

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import mesh_ref as R
+import mesh_stats_cases as MC
 import mesh_stats_ref as SR
 from cppf_amd import config, mesh_stats as MS, training
 from cppf_amd.config import CATEGORIES
@@ -75,6 +76,15 @@ def test_counts_follow_open3d_rule_and_sum_to_n():
             assert (cnt[a == 0] == 0).all()
             pts, t, E2, ok = SR.sample_surface(v, f, n, seed=3)
             assert ok and np.array_equal(np.bincount(t, minlength=f.shape[0]), cnt)
+    # end counts that decrease behind a block boundary (tests/mesh_stats_cases.py): the counts are the steps of E's running maximum
+    for i, case in enumerate(MC.DIP_CASES):
+        v, f, Cc, E = MC.dip_case(i)
+        n = case["N"]
+        assert (np.diff(E) < 0).any()
+        cnt = np.diff(np.concatenate([[0], np.maximum.accumulate(E)]))
+        assert cnt.sum() == n and np.array_equal(cnt, SR.open3d_counts(Cc, n)), (case["F"], n)
+        assert (cnt[SR.areas(v, f) == 0] == 0).all()
+        assert np.array_equal(np.bincount(MC.dip_sample(i)[1], minlength=f.shape[0]), cnt)
     # F <= 1024: the blocked order is Open3D's serial chain; F > 1024 (the 16 384-face sphere) is blocked
     v, f = R.box()[:2]
     a = SR.areas(v, f)
