@@ -46,8 +46,13 @@ __device__ __forceinline__ f3 cross3(f3 a, f3 b)
 // reciprocal, q0, residual, q1, residual, v_div_fmas, v_div_fixup) minus the parts that only act outside the normal
 // range -- the reciprocal refinement is hoisted (refined_rcp), operands are never rescaled (|a| <= a few metres over
 // res ~ 1e-3..1e-1: no scaling would be applied) and inf/NaN/0 fix-ups are not needed because such coordinates fail
-// the bound tests either way.  Same result bit for bit on that range (checked exhaustively on the device against `/`:
-// profiles/r2_div_check.txt); 5 instructions per division instead of 9.
+// the bound tests either way.  Same result bit for bit on that range (checked exhaustively on the device against `/` for every call
+// site's operands: tests/test_gpu_device_math.py; first measured in profiles/r2_div_check.txt); 5 instructions per division instead
+// of 9.  Two exceptions, both pinned by that test.  Where the IEEE quotient is a non-zero subnormal, |a| < 2^-126 b, the result may be
+// one subnormal quantum (2^-149) off: the residuals are not representable there -- what operand scaling is for.  No metric cloud
+// has such a numerator (|a| < 2^-124), and a quotient of 1e-38 is lost in the first sum it enters.  And a numerator of -0 gives +0 where `/` gives -0 (q0 = -0, r0 = fma(-b, -0, -0) = +0, q1 = fma(+0, y, -0) = +0).
+// Every numerator here is a difference of coordinates, and x - x = +0 for every x, -0 included; only (-0) - (+0) gives -0, and the
+// quotient's sign of zero is then lost in a comparison, a truncation or a sum (tests: test_div_by_negative_zero_numerator).
 __device__ __forceinline__ float refined_rcp(float b)
 {
     const float y0 = __builtin_amdgcn_rcpf(b);
@@ -73,8 +78,8 @@ __device__ __forceinline__ f3 ld3(const float* __restrict__ p, int i)
 // so -- without the parts that only act below 2^-96 (rescaling by 2^32 and back: there the residual leaves the normal
 // range) and on infinite or NaN arguments (the class test): 10 instructions instead of 17.  x = 0: the lower neighbour is
 // kept at 0 (integer max), both residuals are zeros, the result is 0.  Checked against sqrtf for x = 0 and every float in
-// [2^-96, 2^40]: profiles/microbench/exp2_check.hip, profiles/r4_exp2_check.txt (below 2^-96 it differs by an ulp for 1.6 % of
-// the arguments; the oracle's sqrtf is exact there too -- such pairs do not occur in metric clouds).
+// [2^-96, 2^40]: tests/test_gpu_device_math.py (first measured in profiles/r4_exp2_check.txt; below 2^-96 it differs by an ulp for
+// 1.6 % of the arguments; the oracle's sqrtf is exact there too -- such pairs do not occur in metric clouds).
 __device__ __forceinline__ float sqrt_rn(float x)
 {
     const float s = __builtin_amdgcn_sqrtf(x);
@@ -88,7 +93,7 @@ __device__ __forceinline__ float sqrt_rn(float x)
 
 // 1 / sqrtf(x) as the two correctly rounded operations it is (the LayerNorm's `1.0f / sqrtf(var + eps)`), for x >= 2^-20: sqrt_rn, then the
 // quotient through refined_rcp + div_by -- 18 instructions instead of the 27 of sqrtf + the compiler's IEEE division; the same bits
-// (the square root: every float of the range, above; the reciprocal: every float in [2^-10, 2^20], profiles/r4_exp2_check.txt)
+// (every float in [2^-20, 2^20] against `1.0f / sqrtf(x)` on the device: tests/test_gpu_device_math.py)
 __device__ __forceinline__ float inv_sqrt_rn(float x)
 {
     const float s = sqrt_rn(x);
@@ -101,9 +106,10 @@ __device__ __forceinline__ float inv_sqrt_rn(float x)
 // Eight VALU per weight: the fma (max subtraction and log2e scale in one), v_fract_f32, v_cvt_flr_i32_f32, four fma, v_ldexp_f32
 // -- no clamp (ldexp underflows through the subnormals to 0 by itself) and no separate subtraction (round 1-3's form -- rint
 // through a magic add, exponent bits patched in by hand, x clamped at -86 -- took eleven).  On gfx950 fp32 MFMA and VALU
-// share one datapath, so every decode instruction is paid in full.  The three instructions are checked exhaustively against
-// their plain-arithmetic definitions (profiles/microbench/exp2_check.hip, profiles/r4_exp2_check.txt), which is what
-// oracle/cppf_oracle.c:orc_exp2w evaluates.
+// share one datapath, so every decode instruction is paid in full.  The function is held to oracle/cppf_oracle.c:orc_exp2w bit for
+// bit under both flag sets it is compiled with, and to the 2.7e-6 against 2^y, by tests/test_gpu_device_math.py (y in [-200, 2]: every
+// integer, the subnormal transition, the v_fract clamp just below 0); the three instructions were first checked exhaustively against
+// their plain-arithmetic definitions in profiles/r4_exp2_check.txt.
 #define CPPF_LOG2E 1.44269504088896341f
 __device__ __forceinline__ float det_exp2w(float l, float c)
 {

@@ -93,7 +93,12 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k)
     return k;
 }
 
-// approximate inverse trigonometry of the arc screens (vote.hip) and the back-vote's angular window (pose_tail.hip): callers budget the errors
+// approximate inverse trigonometry of the arc screens (vote.hip) and the back-vote's angular window (pose_tail.hip): callers budget the errors.
+// The bounds are held on the device by tests/test_gpu_device_math.py (measured worst cases: DESIGN.md section 4).
+//   atan2_approx: range [-pi, pi]: +pi for (+0, x < 0) and -pi for (-0, x < 0), the sign of y as it stands -- both callers (axis_arc_mask,
+//     bv_arc) reduce the angle's index modulo n, where -n/2 and +n/2 are the same rotation.  Domain: x = y = 0 (result 0, with y's
+//     sign), or max(|x|, |y|) in [1e-37, 2^126]: below, the quotient is taken against 1e-37 and the result tends to the nearer x
+//     half-axis; above, the reciprocal is subnormal.  The callers stay within [1e-30, 2^7] (coordinates of a few metres).
 __device__ __forceinline__ float atan01_approx(float t)   // atan on [0, 1], |error| < 2e-5
 {
     const float t2 = t * t;
@@ -103,11 +108,12 @@ __device__ __forceinline__ float atan01_approx(float t)   // atan on [0, 1], |er
     p = fmaf(t2, p, 0.9998660f);
     return p * t;
 }
-__device__ __forceinline__ float atan2_approx(float y, float x)   // (-pi, pi], |error| < 1e-4; atan2(0, 0) = 0
+__device__ __forceinline__ float atan2_approx(float y, float x)   // [-pi, pi] (above), |error| < 1e-4; atan2(0, 0) = 0
 {
     const float ax = fabsf(x), ay = fabsf(y);
     const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    float r = atan01_approx(mn * __builtin_amdgcn_rcpf(fmaxf(mx, 1e-30f)));
+    // (the floor was 1e-30f: a vector of LENGTH 1e-30 off the axes has mx = 0.7e-30 and came out up to 0.17 rad wrong)
+    float r = atan01_approx(mn * __builtin_amdgcn_rcpf(fmaxf(mx, 1e-37f)));
     r = ay > ax ? 1.57079633f - r : r;
     r = x < 0.f ? 3.14159265f - r : r;
     return __builtin_copysignf(r, y);

@@ -133,6 +133,9 @@ int cppf_grid_from_raw(const long long* grid_raw, int64_t n, const float* quantu
                        float* out_val, void* workspace, size_t workspace_bytes, void* stream);
 
 /* np.argmax(grid, axis=None) on device (nocs/inference.py:208).  n cells; ties -> lowest index.
+ * The tie rule is numpy's for signed zeros too: the cells are compared through keys that would order -0 below +0, but every arg-max of
+ * this library (this one, cppf_vote_argmax*) first adds a sum of votes, +0 at least, to the cell, and -0 + +0 = +0 -- a -0 and a
+ * +0 tie, the first wins, and the value reported (and an accumulated grid) holds +0 (pinned by tests/test_gpu_device_math.py).
  * workspace: >= 16 bytes of device scratch. */
 int cppf_grid_argmax(const float* grid, int64_t n, long long* out_idx, float* out_val, void* workspace,
                      size_t workspace_bytes, void* stream);

@@ -63,6 +63,15 @@ def expf(x):
     return float(lib().orc_expf(C.c_float(float(x))))
 
 
+def exp2w(l, c):
+    """orc_exp2w over arrays (broadcast): the softmax weight 2^fmaf(l, log2e, c) of csrc/cppf_math.h:det_exp2w -> float32"""
+    f = lib().orc_exp2w
+    f.restype, f.argtypes = C.c_float, [C.c_float, C.c_float]
+    l, c = np.broadcast_arrays(np.asarray(l, _f), np.asarray(c, _f))
+    out = np.fromiter((f(a, b) for a, b in zip(l.ravel().tolist(), c.ravel().tolist())), _f, count=l.size)
+    return out.reshape(l.shape)
+
+
 def sincos(x):
     s, c = C.c_double(), C.c_double()
     lib().orc_sincos(C.c_double(float(x)), C.byref(s), C.byref(c))

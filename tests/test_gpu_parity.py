@@ -96,6 +96,100 @@ def test_mlp_empty_and_dense(oracle, dev):
     np.testing.assert_array_equal(yd.reshape(-1, 141).cpu().numpy(), yo)
 
 
+def degenerate_pair_cloud(seed=11):
+    """64 points; pair slots 0 .. 12 are engineered, 13 .. 21 are further tiny pairs, the rest random:
+      0      a == b                                   1      0 and (2^-60, 2^-61, -2^-62): the radicand is below 2^-96
+      2-4    separations 2^-49, 2^-48, 2^-47 along x: around half an ulp of 1e-7f (2^-47), where d + 1e-7f rounds up or not
+      5, 6   separations 6e-8 and 2.4e-7               7-9    parallel, antiparallel and zero normals
+      10-12  one pair along each axis                  13     separation 2^-70: a subnormal radicand
+      14-21  random separations of 2^-50 .. 2^-64 per component (sqrt_rn is an ulp off sqrtf for 1.6 % of such radicands)
+    -> pc, nrm, feat, idx i64[65,2]"""
+    ob = syn.make_object("bottle", 64, seed)
+    rng = np.random.default_rng(seed)
+    pc, nrm, feat = ob["pc"].astype(np.float32).copy(), ob["normals"].astype(np.float32).copy(), ob["feat"].astype(np.float32).copy()
+    pairs = [(5, 5)]
+    nxt = [8]
+
+    def put(p, q, na=None, nb=None):
+        i = nxt[0]
+        nxt[0] += 2
+        pc[i], pc[i + 1] = p, q
+        if na is not None:
+            nrm[i], nrm[i + 1] = na, nb
+        pairs.append((i, i + 1))
+
+    put((0, 0, 0), (2.0 ** -60, 2.0 ** -61, -2.0 ** -62))
+    for e in (-49, -48, -47):
+        put((0, 2.0 ** -20, -2.0 ** -21), (2.0 ** e, 2.0 ** -20, -2.0 ** -21))
+    for sep in (6e-8, 2.4e-7):
+        put((1e-7, -2e-7, 3e-7), (1e-7 + sep * 0.6, -2e-7, 3e-7 - sep * 0.8))
+    unit = np.array([0.6, 0.0, 0.8], np.float32)
+    base = pc[40].copy()
+    put(base, base + np.float32(0.05) * unit, unit, unit)
+    put(base, base + np.float32(0.05) * unit, unit, -unit)
+    put(base, base + np.float32(0.05) * unit, np.zeros(3, np.float32), np.zeros(3, np.float32))
+    for ax in range(3):
+        q = base.copy()
+        q[ax] += np.float32(0.03125)
+        put(base, q)
+    assert len(pairs) == 13
+    put((0, 0, 0), (0, 2.0 ** -70, 0))
+    for k in range(8):
+        s = rng.choice([-1.0, 1.0], 3) * 2.0 ** -rng.integers(50, 65, 3).astype(np.float64) * rng.uniform(1, 2, 3)
+        put((0, 0, 0), s)
+    assert nxt[0] <= 64
+    rest = rng.integers(0, 64, (65 - len(pairs), 2))
+    return pc, nrm, feat, np.concatenate([np.array(pairs), rest]).astype(np.int64)
+
+
+@pytest.mark.parametrize("out_dim", [141, 9])
+def test_mlp_degenerate_and_tiny_pairs(oracle, dev, out_dim):
+    """The pairs the shortcuts of ppf_from do not claim (sqrt_rn below 2^-96, div_by by a denominator that is all regulariser):
+    coincident points, separations far below and around 1e-7, degenerate normals, axis-aligned pairs -- in a ragged tile (P = 13) and
+    a full one (P = 65), with int32 and int64 indices.  The logits are the oracle's bit for bit (its sqrtf and `/` are IEEE), within
+    2e-6 of the module's float64 composite on the device (the tolerance of test_mlp_mfma_bit_exact_vs_oracle_and_close_to_reference;
+    the fp32 composite's own distance to the fp64 one is printed beside it, and twice that distance is the bound should it exceed
+    2e-6), and the bf16 encoder meets its emulation bound (tests/test_gpu_pair_bf16.py) on the same list."""
+    import pair_bf16_ref as R
+    pc, nrm, feat, idx = degenerate_pair_cloud()
+    xy = pc[idx[:, 0]].astype(np.float64) - pc[idx[:, 1]]
+    rad = (xy * xy).sum(-1)
+    assert rad[0] == 0 and ((rad > 0) & (rad < 2.0 ** -96)).sum() >= 10 and (rad[2:5] < 1e-14 ** 2 * 4).all()
+    sd = seeded_sd(3, out_dim=out_dim)
+    enc = make_encoder(sd, [84, 32, 32, 16], out_dim, dev)
+    ref64 = PPFEncoder([84, 32, 32, 16], out_dim)
+    ref64.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
+    ref64 = ref64.double().to(dev).eval()
+    d_pc, d_nrm, d_feat = t(pc, dev), t(nrm, dev), t(feat, dev)
+    yo_all = oracle.pair_mlp(pc, nrm, feat, idx, sd, [84, 32, 32, 16], out_dim, order=1)
+    assert np.isfinite(yo_all).all()
+    with torch.no_grad():
+        c64 = ref64._composite(d_pc.double(), d_nrm.double(), d_feat.double(), t(idx, dev)).cpu().numpy()
+        c32 = enc._composite(d_pc, d_nrm, d_feat, t(idx, dev)).cpu().numpy()
+    own = float(np.abs(c32 - c64).max())
+    bound = max(2e-6, 2 * own)
+    for P in (13, 65):
+        for dt in (torch.int64, torch.int32):
+            with torch.no_grad():
+                y = enc.forward_with_idx(d_pc, d_nrm, d_feat, t(idx[:P], dev, dt)).cpu().numpy()
+            np.testing.assert_array_equal(y, yo_all[:P])
+            far = float(np.abs(y - c64[:P]).max())
+            print(f"out_dim {out_dim}, P {P}, {dt}: max |logits - fp64 composite| = {far:.3g} (fp32 composite: {own:.3g}; bound {bound:.3g})")
+            assert far <= bound
+    b = R.order_spread_and_cap(sd, pc, nrm, feat, idx)
+    e16 = PPFEncoder([84, 32, 32, 16], out_dim)
+    e16.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
+    e16 = e16.to(dev).eval().set_precision("bf16")
+    with torch.no_grad():
+        G = e16.forward_with_idx(d_pc, d_nrm, d_feat, t(idx, dev)).cpu().numpy().astype(np.float64)
+    err = np.max(np.abs(G - b["E"]), -1)
+    unmatched = err > b["tol"]
+    print(f"bf16, out_dim {out_dim}: unmatched pairs {int(unmatched.sum())} of {len(idx)} (emulation orders: {b['emu_share']:.3%}), tol {b['tol']:.3g}, cap {b['cap']:.3g}")
+    assert float(np.mean(unmatched)) <= 0.02
+    if unmatched.any():
+        assert np.max(np.abs(G - b["F"])[unmatched]) <= b["cap"]
+
+
 # ------------------------------------------------------------------------------------ decode
 @pytest.mark.parametrize("sharpen", [8, 60, 400])
 def test_fused_decode_bit_exact(oracle, dev, sharpen):
@@ -434,6 +528,13 @@ def test_grid_argmax_tie_rule_and_negatives(dev):
     g = -np.abs(rng.normal(size=5000)).astype(np.float32) - 1      # all negative
     oi, ov = voting.grid_argmax(t(g, dev))
     assert int(oi.item()) == int(np.argmax(g)) and float(ov.item()) == g.max()
+    # signed zeros tie as in numpy (include/cppf.h: the keys would order -0 below +0, but the kernel adds its +0 sum of votes first):
+    # a maximum of 0 with a -0 before a +0, the reverse, or -0 alone -> the first; the value comes back as +0
+    for zeros in ((-0.0, 0.0), (0.0, -0.0), (-0.0, -0.0)):
+        h = g.copy()
+        h[[700, 3000]] = zeros
+        oi, ov = voting.grid_argmax(t(h, dev))
+        assert int(oi.item()) == int(np.argmax(h)) == 700 and ov.cpu().numpy().view(np.uint32)[0] == 0
 
 
 # ------------------------------------------------------------------------------------ back-vote / rot
