@@ -132,6 +132,8 @@ _SIGS = {
     "cppf_box_support": (C.c_int, [vp, vp, vp, vp, vp, i64, i32, vp, vp]),
     # proposal masks -> packed instance clouds, up to 32 proposals in one pass over the dense cloud (csrc/instances.hip)
     "cppf_gather_instances": (C.c_int, [vp, vp, vp, vp, i32, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp]),
+    # segment labels -> packed segment clouds and their bounds, up to 1024 disjoint labels in one call (csrc/instances.hip)
+    "cppf_gather_segments": (C.c_int, [vp, vp, vp, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp]),
     # training on whole labelled frames (csrc/scene_train.hip): the stratified pair draw, per-pair targets of up to 32 instances
     "cppf_sample_scene_pairs": (C.c_int, [vp, i64, vp, i32, vp, i64, i64, i64, C.c_uint64, vp, vp]),
     "cppf_scene_pair_targets": (C.c_int, [vp, vp, vp, i64, vp, i64, vp, vp, i32, C.c_double, C.c_double, i32, i32, vp, vp, vp, vp, vp,

@@ -6,6 +6,8 @@
 //   gi_scatter_kernel   the same chunks again: every workgroup sums the counts table itself (compact.h's self-prefix, with one
 //                       counter per proposal and chunk) -- the rows before its proposal and the chunks before its own give the first
 //                       output row of each of its lists -- and copies its members' 12-byte rows in dense order
+// (cppf_gather_segments, the same packing by a per-point LABEL -- up to 1024 disjoint segments in one call -- is the second half of
+// this file.)
 // Both are bound by memory and by the byte gathers into the masks (n_props per point, neighbours in the dense cloud share their
 // owner).  No atomics: a count is a population count of a ballot, a position is a prefix of counts, the same words on every run.
 #include <hip/hip_runtime.h>
@@ -146,6 +148,211 @@ extern "C" int cppf_gather_instances(const float* hi, const float* hi_nrm, const
                            chunk_counts, nc);
     hipLaunchKernelGGL(gi_scatter_kernel, dim3((unsigned)(nc > 0 ? nc : 1)), dim3(GI_CHUNK), 0, st, hi, hi_nrm, member, n_props, n_dense,
                        chunk_counts, nc, capacity, offsets, pts, nrm, src);
+    if (hipError_t e = hipGetLastError()) return (int)e;
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Segment labels -> segment clouds: cppf_gather_segments, a stable partition of the dense cloud by label (include/cppf.h "Segment
+// clouds"; host side: cppf_amd/segments.py segment_clouds; restated in numpy: tests/gather_segments_ref.py).
+//   gs_count_kernel     one workgroup per chunk of CPPF_GATHER_CHUNK points: the chunk's points per label (gs_rank's per-wave counts,
+//                       summed over the waves) -> counts[chunk][label]; workgroup 0 also fills bounds with the empty values
+//   gs_scan_kernel      64 labels per workgroup, lane = label, wave = a sixteenth of the chunks: counts[.][label] <- its exclusive
+//                       prefix over the chunks, in place; the label's total -> offsets[label + 1]
+//   gs_offsets_kernel   one workgroup: offsets <- the prefix of the totals
+//   gs_scatter_kernel   the chunks again: row = offsets[label] + counts[chunk][label] + (the label's points in the waves before this
+//                       one) + (its points in the lanes below this one); the bounds by integer min / max on the floats' bits
+// The table is chunk-major, so that a wave reads and writes 64 neighbouring labels of one chunk at once.  The only atomics are integer
+// min / max (in LDS, then one per touched label and workgroup in memory): order does not matter to them, the same words on every run.
+#define GS_MAX_S CPPF_GATHER_SEGMENTS_MAX
+static_assert(GS_MAX_S == GI_CHUNK, "thread s of a chunk's workgroup serves label s");
+static_assert(GS_MAX_S == CPPF_SEGMENTS_MAX, "a label of cppf_depth_segments is a segment here");
+
+// The stable rank of a lane among the lanes of its wave with the same label (ok = false: no label), and by the way cnt[label] <- the
+// number of such lanes, for every label in the wave: one trip per distinct label -- the first lane still waiting names the label, a
+// ballot finds its lanes.  Labels of neighbouring pixels agree, so a wave mostly takes one or two trips (64 at the worst).
+__device__ __forceinline__ int gs_rank(int label, bool ok, int lane, uint16_t* __restrict__ cnt)
+{
+    int rank = 0;
+    bool waiting = ok;
+    for (;;) {
+        const unsigned long long todo = __ballot(waiting);
+        if (todo == 0ull) break;
+        const int leader = __ffsll((long long)todo) - 1;
+        const int l = __shfl(label, leader, 64);
+        const bool mine = waiting && label == l;
+        const unsigned long long b = __ballot(mine);
+        if (mine) {
+            rank = __popcll(b & ((1ull << lane) - 1ull));
+            waiting = false;
+            if (lane == leader) cnt[l] = (uint16_t)__popcll(b);
+        }
+    }
+    return rank;
+}
+
+__device__ __forceinline__ void gs_zero(uint16_t (*wcnt)[GS_MAX_S])
+{
+    uint32_t* z = (uint32_t*)&wcnt[0][0];
+    for (int j = threadIdx.x; j < GI_WAVES * GS_MAX_S / 2; j += GI_CHUNK) z[j] = 0u;
+}
+
+// min / max in the order of the sign-magnitude key (-0.0 below +0.0) by integer atomics on the floats' own bits: among non-negative
+// floats the order is the signed integers', among negative ones the reverse of the unsigned integers', and every negative float
+// is a larger unsigned and a smaller signed integer than every non-negative one.  v: the bits of a value that is not NaN.
+template <typename T> __device__ __forceinline__ void gs_min(T* p, uint32_t v)
+{
+    if (v >> 31) atomicMax((unsigned int*)p, v); else atomicMin((int*)p, (int)v);
+}
+template <typename T> __device__ __forceinline__ void gs_max(T* p, uint32_t v)
+{
+    if (v >> 31) atomicMin((unsigned int*)p, v); else atomicMax((int*)p, (int)v);
+}
+#define GS_PINF 0x7f800000u
+#define GS_NINF 0xff800000u
+
+__global__ __launch_bounds__(GI_CHUNK) void gs_count_kernel(const int32_t* __restrict__ labels, int n_seg, int64_t n_dense,
+                                                            int32_t* __restrict__ counts, uint32_t* __restrict__ bounds)
+{
+    __shared__ uint16_t wcnt[GI_WAVES][GS_MAX_S];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    gs_zero(wcnt);
+    if (bounds && blockIdx.x == 0 && (int)threadIdx.x < n_seg)
+        for (int e = 0; e < 6; ++e) bounds[6 * threadIdx.x + e] = e < 3 ? GS_PINF : GS_NINF;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * GI_CHUNK + threadIdx.x;
+    const int32_t l = i < n_dense ? labels[i] : -1;
+    gs_rank(l, (uint32_t)l < (uint32_t)n_seg, lane, wcnt[w]);
+    __syncthreads();
+    if ((int)threadIdx.x < n_seg) {
+        int s = 0;
+        for (int j = 0; j < GI_WAVES; ++j) s += wcnt[j][threadIdx.x];
+        counts[(int64_t)blockIdx.x * n_seg + threadIdx.x] = s;
+    }
+}
+
+// launch: ceil(n_seg / 64) workgroups of GI_CHUNK threads
+__global__ __launch_bounds__(GI_CHUNK) void gs_scan_kernel(int32_t* __restrict__ counts, int n_seg, int64_t n_chunks,
+                                                           int32_t* __restrict__ offsets)
+{
+    __shared__ int part[GI_WAVES][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int s = blockIdx.x * 64 + lane;
+    const int64_t per = (n_chunks + GI_WAVES - 1) / GI_WAVES;
+    const int64_t c0 = w * per < n_chunks ? w * per : n_chunks, c1 = c0 + per < n_chunks ? c0 + per : n_chunks;
+    int sum = 0;
+    if (s < n_seg)
+        for (int64_t c = c0; c < c1; ++c) sum += counts[c * n_seg + s];
+    part[w][lane] = sum;
+    __syncthreads();
+    if (s >= n_seg) return;
+    int run = 0, total = 0;
+    for (int j = 0; j < GI_WAVES; ++j) { run += j < w ? part[j][lane] : 0; total += part[j][lane]; }
+    if (w == 0) offsets[s + 1] = total;
+    for (int64_t c = c0; c < c1; ++c) {
+        const int v = counts[c * n_seg + s];
+        counts[c * n_seg + s] = run;
+        run += v;
+    }
+}
+
+// offsets[1 + s] holds label s's total; offsets <- {0, the inclusive prefix of the totals}.  One workgroup of GI_CHUNK threads.
+__global__ __launch_bounds__(GI_CHUNK) void gs_offsets_kernel(int32_t* __restrict__ offsets, int n_seg)
+{
+    __shared__ int wtot[GI_WAVES];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int v = (int)threadIdx.x < n_seg ? offsets[threadIdx.x + 1] : 0;
+    for (int off = 1; off < 64; off <<= 1) {
+        const int u = __shfl_up(v, off, 64);
+        if (lane >= off) v += u;
+    }
+    if (lane == 63) wtot[w] = v;
+    __syncthreads();
+    for (int j = 0; j < w; ++j) v += wtot[j];
+    if ((int)threadIdx.x < n_seg) offsets[threadIdx.x + 1] = v;
+    if (threadIdx.x == 0) offsets[0] = 0;
+}
+
+__global__ __launch_bounds__(GI_CHUNK) void gs_scatter_kernel(const float* __restrict__ hi, const float* __restrict__ hi_nrm,
+                                                              const int32_t* __restrict__ labels, int n_seg, int64_t n_dense,
+                                                              const int32_t* __restrict__ counts, const int32_t* __restrict__ offsets,
+                                                              int64_t capacity, float* __restrict__ pts, float* __restrict__ nrm,
+                                                              int32_t* __restrict__ src, uint32_t* __restrict__ bounds)
+{
+    __shared__ uint16_t wcnt[GI_WAVES][GS_MAX_S];
+    __shared__ int row_base[GS_MAX_S];
+    __shared__ uint32_t box[6][GS_MAX_S];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    gs_zero(wcnt);
+    if ((int)threadIdx.x < n_seg) {
+        row_base[threadIdx.x] = offsets[threadIdx.x] + counts[(int64_t)blockIdx.x * n_seg + threadIdx.x];
+        if (bounds)
+            for (int e = 0; e < 6; ++e) box[e][threadIdx.x] = e < 3 ? GS_PINF : GS_NINF;
+    }
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * GI_CHUNK + threadIdx.x;
+    const int32_t l = i < n_dense ? labels[i] : -1;
+    const bool ok = (uint32_t)l < (uint32_t)n_seg;
+    const int rank = gs_rank(l, ok, lane, wcnt[w]);
+    __syncthreads();
+    int here = 0;                                                             // label threadIdx.x's points in this chunk
+    if ((int)threadIdx.x < n_seg)
+        for (int j = 0; j < GI_WAVES; ++j) { const int c = wcnt[j][threadIdx.x]; wcnt[j][threadIdx.x] = (uint16_t)here; here += c; }
+    __syncthreads();
+    if (ok) {
+        float p[3], q[3];
+        for (int e = 0; e < 3; ++e) { p[e] = hi[3 * i + e]; q[e] = hi_nrm[3 * i + e]; }
+        const int64_t pos = (int64_t)row_base[l] + wcnt[w][l] + rank;
+        if (pos < capacity) {
+            for (int e = 0; e < 3; ++e) { pts[3 * pos + e] = p[e]; nrm[3 * pos + e] = q[e]; }
+            src[pos] = (int32_t)i;
+        }
+        if (bounds) {
+            const uint32_t b[3] = {__float_as_uint(p[0]), __float_as_uint(p[1]), __float_as_uint(p[2])};
+            if ((b[0] & GS_PINF) != GS_PINF && (b[1] & GS_PINF) != GS_PINF && (b[2] & GS_PINF) != GS_PINF)      // all three finite
+                for (int e = 0; e < 3; ++e) { gs_min(&box[e][l], b[e]); gs_max(&box[3 + e][l], b[e]); }
+        }
+    }
+    if (!bounds) return;
+    __syncthreads();
+    if (here > 0)
+        for (int e = 0; e < 3; ++e) {
+            gs_min(&bounds[6 * threadIdx.x + e], box[e][threadIdx.x]);
+            gs_max(&bounds[6 * threadIdx.x + 3 + e], box[3 + e][threadIdx.x]);
+        }
+}
+
+// n_dense = 0: offsets all zero, bounds empty.  One workgroup of GI_CHUNK threads.
+__global__ __launch_bounds__(GI_CHUNK) void gs_empty_kernel(int32_t* __restrict__ offsets, uint32_t* __restrict__ bounds, int n_seg)
+{
+    if ((int)threadIdx.x <= n_seg) offsets[threadIdx.x] = 0;
+    if ((int)threadIdx.x == GI_CHUNK - 1) offsets[n_seg] = 0;                 // (n_seg = 1024: one entry more than threads)
+    if (bounds && (int)threadIdx.x < n_seg)
+        for (int e = 0; e < 6; ++e) bounds[6 * threadIdx.x + e] = e < 3 ? GS_PINF : GS_NINF;
+}
+
+extern "C" int cppf_gather_segments(const float* hi, const float* hi_nrm, const int32_t* labels, int n_segments, int64_t n_dense,
+                                    int64_t capacity, int32_t* offsets, float* pts, float* nrm, int32_t* src, float* bounds,
+                                    int32_t* chunk_counts, void* stream)
+{
+    if (n_segments < 1 || n_segments > GS_MAX_S || n_dense < 0 || capacity < 0) return CPPF_EINVAL;
+    if (n_dense > INT32_MAX) return CPPF_EINVAL;                              // offsets and src are int32
+    if (!offsets || (capacity > 0 && (!pts || !nrm || !src))) return CPPF_EINVAL;
+    if (n_dense > 0 && (!hi || !hi_nrm || !labels || !chunk_counts)) return CPPF_EINVAL;
+    const int64_t nc = (n_dense + GI_CHUNK - 1) / GI_CHUNK;
+    if (nc > CPPF_GATHER_MAX_CHUNKS) return CPPF_EUNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    uint32_t* box = (uint32_t*)bounds;
+    if (nc == 0) {
+        hipLaunchKernelGGL(gs_empty_kernel, dim3(1), dim3(GI_CHUNK), 0, st, offsets, box, n_segments);
+    } else {
+        hipLaunchKernelGGL(gs_count_kernel, dim3((unsigned)nc), dim3(GI_CHUNK), 0, st, labels, n_segments, n_dense, chunk_counts, box);
+        hipLaunchKernelGGL(gs_scan_kernel, dim3((unsigned)((n_segments + 63) / 64)), dim3(GI_CHUNK), 0, st, chunk_counts, n_segments, nc,
+                           offsets);
+        hipLaunchKernelGGL(gs_offsets_kernel, dim3(1), dim3(GI_CHUNK), 0, st, offsets, n_segments);
+        hipLaunchKernelGGL(gs_scatter_kernel, dim3((unsigned)nc), dim3(GI_CHUNK), 0, st, hi, hi_nrm, labels, n_segments, n_dense,
+                           chunk_counts, offsets, capacity, pts, nrm, src, box);
+    }
     if (hipError_t e = hipGetLastError()) return (int)e;
     return 0;
 }

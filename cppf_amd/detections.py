@@ -9,6 +9,9 @@ on the device (evaluation.nms_3d -> cppf_box_nms_batch, all categories in one ca
                      (res, knn)) -> pool_detections
   pool_detections    scene_poses / scene_frame dicts, one per category -> detections, per-category NMS, optionally a second,
                      cross-category pass over the survivors
+  segment_detections depth frame -> its depth segments taken as instance masks -> the instance path of every category on every
+                     segment (one resident batch per category) -> select_per_segment -> NMS.  No scene stage
+  select_per_segment the choice among a segment's candidates, a pure host function
 """
 from collections import OrderedDict
 
@@ -86,6 +89,15 @@ def pool_detections(outs, names, cfgs=None, nms_thresh=0.3, cross_category=False
             if r is not None and _finite(r):
                 det.update(coarse=dict(RT=det["RT"], scales=det["scales"], scale=det["extents"]), **_box(r))
             dets.append(det)
+    extra = {}
+    if verified:
+        extra["filtered"] = OrderedDict(zip(names, dropped))
+    return _suppress(dets, names, cfgs, nms_thresh, cross_category, device, dropped if verified else None, **extra)
+
+
+def _suppress(dets, names, cfgs, nms_thresh, cross_category, device, dropped=None, per_category=True, **extra):
+    """pool_detections' second half: the NMS over detection dicts (each with RT, extents, score, category) and the dict it returns.
+    per_category=False: ONE pass over all detections as one group instead of a pass per category (cross_category then adds nothing)."""
     n = len(dets)
     cat = np.array([d["category"] for d in dets], np.int64).reshape(n)
     scores = np.array([d["score"] for d in dets], np.float64).reshape(n)
@@ -93,8 +105,9 @@ def pool_detections(outs, names, cfgs=None, nms_thresh=0.3, cross_category=False
     extents = np.stack([d.pop("extents") for d in dets]) if n else np.zeros((0, 3))
     keep = np.arange(n)
     if nms_thresh is not None and n:
-        keep = np.concatenate(E.nms_3d(RTs, extents, scores, nms_thresh, groups=cat, device=device) + [np.zeros(0, np.int64)])
-        if cross_category and len(keep):
+        keep = np.concatenate(E.nms_3d(RTs, extents, scores, nms_thresh, groups=cat if per_category else None, device=device)
+                              + [np.zeros(0, np.int64)])
+        if per_category and cross_category and len(keep):
             keep = np.sort(keep)
             (again,) = E.nms_3d(RTs[keep], extents[keep], scores[keep], nms_thresh, device=device)
             keep = keep[again]
@@ -104,9 +117,7 @@ def pool_detections(outs, names, cfgs=None, nms_thresh=0.3, cross_category=False
     per_cat = lambda idx: OrderedDict((nm, int((cat[idx] == c).sum())) for c, nm in enumerate(names))
     total, left = per_cat(np.arange(n)), per_cat(keep)
     suppressed = OrderedDict((nm, total[nm] - left[nm]) for nm in names)
-    extra = {}
-    if verified:
-        extra["filtered"] = OrderedDict(zip(names, dropped))
+    if dropped is not None:
         total = OrderedDict((nm, total[nm] + dropped[c]) for c, nm in enumerate(names))
     result = dict(pred_class_ids=(cat[keep] + 1).astype(np.int32), pred_RTs=RTs[keep].reshape(-1, 4, 4),
                   pred_scales=(np.stack([d["scales"] for d in kept]) if kept else np.zeros((0, 3))), pred_scores=scores[keep])
@@ -160,4 +171,133 @@ def frame_detections(depth, intrinsics, networks, n_pairs=5_000_000, seed=0, jit
     return res
 
 
-__all__ = ["pool_detections", "frame_detections"]
+def select_per_segment(cands, rule="best"):
+    """The choice among the candidates of segment_detections, on the host: cands is a list of dicts with `segment`, `category` (the
+    index of the network) and `score`.  rule="best": per segment the candidate with the highest score, an equal score going to the
+    lower category index (then to the earlier candidate); a candidate whose score is NaN is never chosen, and a segment with no
+    candidate has no entry.  The chosen candidates come back in ascending segment order.  rule="all": every candidate, in the order
+    given.  The dicts themselves are returned, not copies."""
+    if rule == "all":
+        return list(cands)
+    if rule != "best":
+        raise ValueError(f"select must be 'best' or 'all', got {rule!r}")
+    best = {}
+    for c in cands:
+        score = float(c["score"])
+        if np.isnan(score):
+            continue
+        have = best.get(c["segment"])
+        if have is None or score > float(have["score"]) or (score == float(have["score"]) and c["category"] < have["category"]):
+            best[c["segment"]] = c
+    return [best[s] for s in sorted(best)]
+
+
+def segment_detections(depth, intrinsics, networks, runner, segments=None, n_pairs=100_000, seed=0, jitter=None, select="best",
+                       score="agreement", nms_thresh=0.3, min_points=None, max_segments=None, max_extent_ratio=None, segment_kw=None):
+    """One depth frame -> detections, taking the frame's depth SEGMENTS as the instance masks: no scene vote, no
+    proposals, no back-vote -- every segment's dense points go through the instance path of every category network, each (segment,
+    category) candidate gets a score that means the same for every network, and per segment the best candidate is kept.
+    networks: as for frame_detections; runner: a BatchPoseRunner that holds every category's two encoders (what refine= takes);
+    segments: segments.frame_segments' dict for this frame (None: frame_segments(depth, intrinsics, **segment_kw)).
+    Per distinct (cfg.res, cfg.knn) one labelled_frame_cloud and one segments.segment_clouds call (cppf_gather_segments: one read-back
+    of the offsets, one of the bounds when max_extent_ratio is set).  Per category the segments with at least min_points points
+    (default: the point encoder's k) go through runner.put / run as ONE resident batch, n_pairs pairs each, object j of the batch
+    drawing its pairs from (seed, j) -- the way scene_poses.refine_poses feeds the runner.
+    max_segments: only the largest segments by segments["sizes"] (pixels) are candidates, ties to the lower label.
+    max_extent_ratio=r: a (segment, category) pair is skipped when the diagonal of the segment's bounds exceeds r * |2 cfg.scale_mean|.
+    A candidate is scene_poses.refined_pose's dict plus segment, n_points, n_surv, n_pairs, agreement = n_surv / n_pairs (fp64; column
+    14 of the runner's record over the pairs drawn: a ratio in [0, 1], this project's definition), class_name, category and score
+    (score="agreement", or "peak": the vote peak, which is NOT comparable between networks).  A record the runner marks refused
+    (record[:, 12] < 0) yields no candidate; the runner's late check of that batch is settled here, as refine_poses does.
+    select="best": select_per_segment's choice, then ONE pooled NMS pass over all categories; select="all": every candidate, then
+    pool_detections' per-category NMS.  nms_thresh=None: no suppression.
+    Returns pool_detections' dict (detections -- each with class_name, category, RT, scales, score, pose (the candidate), proposal
+    (its index in candidates) and segment --, result, kept_per_category, proposals_per_category, suppressed, cfgs) plus segments,
+    candidates, refused [(segment, class_name)] and skipped = dict(max_segments=[segment], min_points=[(segment, class_name)],
+    extent=[(segment, class_name)])."""
+    import torch
+    from ._lib import CppfError
+    from .scene_poses import refined_pose
+    from .segments import frame_segments, labelled_frame_cloud, segment_clouds
+    if not networks:
+        raise ValueError("segment_detections needs at least one category network")
+    if select not in ("best", "all"):
+        raise ValueError(f"select must be 'best' or 'all', got {select!r}")
+    if score not in ("agreement", "peak"):
+        raise ValueError(f"score must be 'agreement' or 'peak', got {score!r}")
+    for name, (_, _, cfg) in networks.items():
+        if cfg.category not in runner.encoders or cfg.category not in runner.point_encoders:
+            raise ValueError(f"segment_detections: the runner needs the pair encoder and the point encoder of {cfg.category!r}")
+    if segments is None:
+        segments = frame_segments(depth, intrinsics, **(segment_kw or {}))
+    S = int(segments["n_segments"])
+    allowed = np.ones(S, bool)
+    skipped = dict(max_segments=[], min_points=[], extent=[])
+    if max_segments is not None and S > int(max_segments):
+        sizes = np.asarray(segments["sizes"].cpu().numpy() if torch.is_tensor(segments["sizes"]) else segments["sizes"], np.int64)[:S]
+        order = np.argsort(-sizes, kind="stable")                             # descending size, ties to the lower label
+        allowed[order[max(int(max_segments), 0):]] = False
+        skipped["max_segments"] = [int(s) for s in np.nonzero(~allowed)[0]]
+    names, cfgs, packed, cands, refused, dev = [], [], {}, [], [], None
+    for c, (name, (point_encoder, encoder, cfg)) in enumerate(networks.items()):
+        names.append(name); cfgs.append(cfg)
+        key = (float(cfg.res), int(cfg.knn))
+        if key not in packed:
+            g = segment_clouds(labelled_frame_cloud(depth, intrinsics, cfg, segments, jitter), S)
+            g["bounds_host"] = g["bounds"].cpu().numpy().astype(np.float64) if max_extent_ratio is not None else None
+            packed[key] = g
+        g = packed[key]
+        dev = g["pts"].device
+        need = max(int(runner.point_encoders[cfg.category].k) if min_points is None else int(min_points), 1)
+        limit = None if max_extent_ratio is None else float(max_extent_ratio) * float(np.linalg.norm(2.0 * np.asarray(cfg.scale_mean, np.float64)))
+        take = []
+        for s in np.nonzero(allowed)[0]:
+            s = int(s)
+            if g["clouds"][s][0].shape[0] < need:
+                skipped["min_points"].append((s, name))
+            elif limit is not None and not np.linalg.norm(g["bounds_host"][s, 3:] - g["bounds_host"][s, :3]) <= limit:
+                skipped["extent"].append((s, name))
+            else:
+                take.append(s)
+        if not take:
+            continue
+        objs = runner.put([dict(pc=g["clouds"][s][0], normals=g["clouds"][s][1], cfg=cfg, n_pairs=int(n_pairs)) for s in take])
+        recs = runner.run(objs, seed=seed)
+        batch = runner._batch_no - 1
+        recs = recs.cpu().numpy() if torch.is_tensor(recs) else np.asarray(recs)
+        try:
+            runner.check()
+        except CppfError as e:
+            if getattr(e, "batch", None) != batch:
+                raise
+        for j, s in enumerate(take):
+            if recs[j, 12] < 0:
+                refused.append((s, name))
+                continue
+            p = refined_pose(recs[j], cfg, g["clouds"][s][0].shape[0])
+            n_surv = int(recs[j, 14])
+            p.update(segment=s, n_surv=n_surv, n_pairs=int(n_pairs), agreement=np.float64(n_surv) / np.float64(int(n_pairs)),
+                     class_name=name, category=c)
+            cands.append(p)
+    res = pool_segment_candidates(cands, names, cfgs, select, score, nms_thresh, dev)
+    res.update(segments=segments, candidates=cands, refused=refused, skipped=skipped)
+    return res
+
+
+def pool_segment_candidates(cands, names, cfgs=None, select="best", score="agreement", nms_thresh=0.3, device=None):
+    """segment_detections' last step on its own, host arithmetic plus the NMS: the candidates (each gets score = its `agreement` or its
+    `peak`) -> select_per_segment -> detections -> one pooled NMS pass (select="best") or pool_detections' pass per category
+    (select="all").  The same candidates may be pooled again under another rule without running a network."""
+    if select not in ("best", "all"):
+        raise ValueError(f"select must be 'best' or 'all', got {select!r}")
+    if score not in ("agreement", "peak"):
+        raise ValueError(f"score must be 'agreement' or 'peak', got {score!r}")
+    for p in cands:
+        p["score"] = float(p[score])
+    index = {id(p): k for k, p in enumerate(cands)}
+    dets = [dict(class_name=p["class_name"], category=p["category"], score=p["score"], pose=p, proposal=index[id(p)], segment=p["segment"],
+                 **_box(p)) for p in select_per_segment(cands, select) if _finite(p) and np.isfinite(p["score"])]
+    return _suppress(dets, list(names), cfgs, nms_thresh, False, device, per_category=select == "all")
+
+
+__all__ = ["pool_detections", "frame_detections", "segment_detections", "select_per_segment", "pool_segment_candidates"]

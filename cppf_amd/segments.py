@@ -13,13 +13,15 @@ points of a pair from ONE segment.  Everything here is opt-in.
                    frame_detections (segments=)
   segment_inputs   scene_stage.cloud_inputs on labelled_frame_cloud's cloud (scene_stage.scene_cloud with the segments' label image),
                    the pairs drawn inside segments (scene_training.sample_scene_pairs)
+  segment_clouds   cppf_gather_segments: the labelled cloud's dense points packed segment by segment, and each
+                   segment's bounds -- the segments as instance clouds (detections.segment_detections)
 
 The kernels are csrc/segments.hip's and csrc/concave.hip's; the distance tests and compactions of support_mask are torch."""
 import numpy as np
 import torch
 
 from ._torch_util import call, canon, require_cuda
-from .scene_stage import SceneCloud, cloud_inputs, on_device, scene_cloud
+from .scene_stage import GATHER_CHUNK, GATHER_MAX_CHUNKS, SceneCloud, cloud_inputs, on_device, scene_cloud
 
 F32, I32, I16, U8 = torch.float32, torch.int32, torch.int16, torch.uint8
 SEGMENTS_MAX = 1024                       # include/cppf.h: CPPF_SEGMENTS_MAX
@@ -330,5 +332,70 @@ def segment_inputs(depth, intrinsics, point_encoder, cfg, n_pairs, seed, segment
     return (*cloud_inputs(cloud, point_encoder, P, seed, pairs=idx), inst)
 
 
+def check_segment_cloud_args(n_segments, n_dense, capacity):
+    """cppf_gather_segments' refusals that need no device, as ValueError"""
+    S, M, cap = int(n_segments), int(n_dense), int(capacity)
+    if not 1 <= S <= SEGMENTS_MAX:
+        raise ValueError(f"segment_clouds takes 1..{SEGMENTS_MAX} segments, got {S}")
+    if M < 0 or cap < 0:
+        raise ValueError(f"negative size: n_dense {M}, capacity {cap}")
+    if M > 2 ** 31 - 1:
+        raise ValueError(f"{M} dense points pass the int32 offsets")
+    if (M + GATHER_CHUNK - 1) // GATHER_CHUNK > GATHER_MAX_CHUNKS:
+        raise ValueError(f"{M} dense points: one call takes at most {GATHER_CHUNK * GATHER_MAX_CHUNKS}")
+
+
+def _labelled(cloud, who):
+    if not isinstance(cloud, SceneCloud) or cloud.hi_labels is None:
+        raise ValueError(f"{who} needs a cloud with labels (segments.labelled_frame_cloud's SceneCloud), got one without")
+    return cloud
+
+
+def segment_clouds_device(cloud, n_segments, capacity=None, out=None):
+    """cppf_gather_segments on labelled_frame_cloud's SceneCloud, enqueued on the current stream with nothing read back: the dense
+    cloud packed segment by segment.  Returns dict(offsets i32[S+1], pts f32[capacity,3], nrm f32[capacity,3], src i32[capacity],
+    bounds f32[S,6] = {min x, y, z, max x, y, z} of each segment's finite points) of device tensors; segment s's points are rows
+    offsets[s]:offsets[s+1], in increasing dense index -- cloud.hi[cloud.hi_labels == s].  capacity: the dense cloud's size by
+    default (segments are disjoint: always enough); out: such a dict to write into (the caller's buffers)."""
+    cloud = _labelled(cloud, "segment_clouds")
+    hi, hi_nrm, lab = cloud.hi, cloud.hi_nrm, cloud.hi_labels
+    dev = hi.device
+    S, M = int(n_segments), hi.shape[0]
+    capacity = M if capacity is None else int(capacity)
+    check_segment_cloud_args(S, M, capacity)
+    if out is None:
+        out = dict(offsets=torch.empty(S + 1, dtype=I32, device=dev), pts=torch.empty((max(capacity, 1), 3), dtype=F32, device=dev),
+                   nrm=torch.empty((max(capacity, 1), 3), dtype=F32, device=dev), src=torch.empty(max(capacity, 1), dtype=I32, device=dev),
+                   bounds=torch.empty((S, 6), dtype=F32, device=dev))
+    counts = torch.empty(max(S * ((M + GATHER_CHUNK - 1) // GATHER_CHUNK), 1), dtype=I32, device=dev)
+    call("cppf_gather_segments", dev, hi, hi_nrm, lab, S, M, capacity, out["offsets"], out["pts"], out["nrm"], out["src"], out.get("bounds"),
+         counts)
+    return out
+
+
+def segment_clouds(cloud, n_segments):
+    """The segments of a labelled frame cloud as instance clouds: dict(clouds: a list of S (pts f32[n_s,3], nrm f32[n_s,3]) views of
+    the packed device buffers, segment s = cloud.hi[cloud.hi_labels == s] and its normals; offsets i64[S+1] numpy; pts, nrm, src: the
+    packed device buffers (T rows); bounds f32[S,6] device).  One call, one read-back of the S + 1 offsets.  cloud: labelled_frame_cloud's
+    SceneCloud; one without hi_labels is refused (ValueError).  n_segments = 0: no segments, nothing is launched."""
+    cloud = _labelled(cloud, "segment_clouds")
+    dev, S = cloud.hi.device, int(n_segments)
+    if S == 0:
+        return dict(clouds=[], offsets=np.zeros(1, np.int64), pts=cloud.hi[:0], nrm=cloud.hi_nrm[:0],
+                    src=torch.empty(0, dtype=I32, device=dev), bounds=torch.empty((0, 6), dtype=F32, device=dev))
+    hi, hi_nrm, lab = (canon(cloud.hi, F32, dev, "hi", (3,)), canon(cloud.hi_nrm, F32, dev, "hi_nrm", (3,)),
+                       canon(cloud.hi_labels, I32, dev, "hi_labels"))
+    if lab.shape != (hi.shape[0],) or hi_nrm.shape != hi.shape:
+        raise ValueError(f"segment_clouds: hi {tuple(hi.shape)}, hi_nrm {tuple(hi_nrm.shape)}, hi_labels {tuple(lab.shape)}: expected "
+                         "[M,3], [M,3], [M]")
+    g = segment_clouds_device(cloud._replace(hi=hi, hi_nrm=hi_nrm, hi_labels=lab), S)
+    off = g["offsets"].cpu().numpy().astype(np.int64)
+    T = int(off[S])
+    pts, nrm = g["pts"][:T], g["nrm"][:T]
+    return dict(clouds=[(pts[int(a):int(b)], nrm[int(a):int(b)]) for a, b in zip(off[:-1], off[1:])], offsets=off, pts=pts, nrm=nrm,
+                src=g["src"][:T], bounds=g["bounds"])
+
+
 __all__ = ["plane_ransac", "support_mask", "depth_segments", "frame_segments", "segment_inputs", "labelled_frame_cloud", "segment_members",
-           "depth_tensor", "off_planes", "concave_edges", "concave_edges_device", "concave_options", "check_concave_args"]
+           "depth_tensor", "off_planes", "concave_edges", "concave_edges_device", "concave_options", "check_concave_args",
+           "segment_clouds", "segment_clouds_device", "check_segment_cloud_args"]

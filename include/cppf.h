@@ -972,6 +972,39 @@ int cppf_gather_instances(const float* hi, const float* hi_nrm, const int32_t* o
                           float* nrm, int32_t* src, int32_t* chunk_counts, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Segment clouds (csrc/instances.hip; additive, ABI version unchanged): the dense cloud packed by a per-point LABEL -- the segments
+ * of cppf_depth_segments as instance clouds, without the scene stage in between.  cppf_gather_instances takes at most 32 possibly
+ * overlapping proposals as mask rows through an owner map; segments are up to CPPF_SEGMENTS_MAX disjoint labels of the dense points
+ * themselves, so one call serves a whole frame.
+ *
+ * cppf_gather_segments: a stable partition of the dense cloud by label.
+ *   in:  hi, hi_nrm device f32[n_dense,3]; labels device i32[n_dense] (SceneCloud.hi_labels).  A label outside [0, n_segments) --
+ *        -1 included -- belongs to no segment: the point is skipped, never an error.
+ *   out: offsets device i32[n_segments+1]: the exclusive prefix of the segments' point counts -- always complete.
+ *        pts, nrm device f32[capacity,3], src device i32[capacity]: rows offsets[s] .. offsets[s+1] hold hi[i], hi_nrm[i] and i for
+ *        the points with labels[i] == s in increasing i (what hi[labels == s] gives on the host).  Nothing is written at or beyond
+ *        row `capacity`: when offsets[n_segments] > capacity the call still returns 0.  Segments are disjoint: n_dense rows always
+ *        suffice.  pts / nrm / src may be NULL with capacity 0 (a count-only call).
+ *        bounds NULL or device f32[n_segments,6] = {min x, y, z, max x, y, z} over the segment's points whose three coordinates
+ *        are all finite, in the order of the sign-magnitude integer key (-0.0 lies below +0.0); a segment with no such point gets
+ *        {+inf, +inf, +inf, -inf, -inf, -inf}.
+ *        chunk_counts device i32[CPPF_GATHER_COUNTS(n_segments, n_dense)]: the call's only intermediate, a typed argument and not a
+ *        workspace -- CHUNK-major (n_segments integers per chunk of CPPF_GATHER_CHUNK points); after the call entry [c][s] holds
+ *        segment s's points in the chunks before c.  Overwritten by every call.
+ *   Four launches on `stream` (per-chunk counts from wave ballots; their prefix over the chunks, per label; the prefix of the
+ *   totals; the copy), no host synchronisation, no read-back, no floating-point atomics -- the bounds are integer min / max on the
+ *   floats' bits, which do not depend on order -- so every output word is the same on every run, and the call can be captured in a
+ *   graph.  n_dense = 0: one launch that writes zero offsets and the empty bounds.
+ *   CPPF_EINVAL: n_segments outside 1..CPPF_GATHER_SEGMENTS_MAX, a negative size, n_dense > 2^31-1, a null pointer (pts / nrm / src
+ *   may be NULL with capacity 0; every input and chunk_counts with n_dense 0).
+ *   CPPF_EUNSUPPORTED: more than CPPF_GATHER_MAX_CHUNKS chunks.
+ * ------------------------------------------------------------------------------------------- */
+#define CPPF_GATHER_SEGMENTS_MAX 1024            /* = CPPF_SEGMENTS_MAX */
+int cppf_gather_segments(const float* hi, const float* hi_nrm, const int32_t* labels, int n_segments, int64_t n_dense,
+                         int64_t capacity, int32_t* offsets, float* pts, float* nrm, int32_t* src, float* bounds,
+                         int32_t* chunk_counts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Training views (utils/dataset.py:103-207, csrc/raster.hip): the pyrender `RenderFlags.DEPTH_ONLY` render of one mesh through
  * the dataset's PinholeCamera (:108-138), and the covered pixels as the dataset's point cloud.  Parity with pyrender is UNPINNED
  * (pyrender and its 24-bit depth buffer are not part of the project); the definition below is, to the operation, and

@@ -57,6 +57,15 @@ upright on one support plane and may touch (G = 0) -- instead of floating in emp
 (segments.frame_segments(concave={})); both may be given.
 
     python scripts/eval_mesh_frames.py --procedural --weights ... --frames 20 --objects 4 --tabletop --mask-free --segments --planes 1 --concave
+
+--segment-instances [--planes N] [--concave] [--select best|all] [--score agreement|peak] [--max-extent-ratio R] (a mode of its own, with or
+without --tabletop): the frame's depth segments are taken as the instance masks -- detections.segment_detections: every
+segment through the instance path of every category, the best candidate per segment by a score that means the same for every network.
+The timed run uses --select / --score; the same candidates are then pooled under the other three combinations on the host, and the
+record (profiles/segment_instances_eval.json) holds the four AP tables, the candidates and refusals per frame and how often the best
+candidate of an object's own segment has the object's category.  Figures, no threshold.
+
+    python scripts/eval_mesh_frames.py --procedural --weights ... --frames 20 --objects 4 --tabletop --segment-instances --planes 1
 """
 import argparse
 import json
@@ -232,6 +241,64 @@ def _detections(args, sampler, encs, pencs, dev):
     return results, ms, counts, n_prop, n_gt
 
 
+SEGMENT_VARIANTS = [("best", "agreement"), ("all", "agreement"), ("best", "peak"), ("all", "peak")]
+
+
+def _segment_instances(args, sampler, encs, pencs, dev):
+    """--segment-instances: every frame through detections.segment_detections (timed: the segmentation, the labelled cloud, the gather,
+    every category's batch, the selection and the NMS under --select / --score); the frame's candidates are then pooled again, untimed
+    and on the host, under the other three of SEGMENT_VARIANTS.  Per ground-truth object with a segment of its own (the segment that
+    holds most of its pixels, at least half of them) it is counted whether select_per_segment's best candidate of that segment, under
+    each score, has the object's category.  -> ({variant: records}, ms per frame, counters)"""
+    from collections import OrderedDict
+    from cppf_amd.batch import BatchPoseRunner
+    from cppf_amd.detections import pool_segment_candidates, segment_detections, select_per_segment
+    names, cats = sampler.synset_names, list(sampler.categories)
+    nets = OrderedDict((c, (pencs[c], encs[c], CATEGORIES[c])) for c in cats)
+    runner = BatchPoseRunner(encs, dev, point_encoders=pencs)
+    primary = (args.select, "peak" if args.score == "peak" else "agreement")
+    results = {f"{s}/{k}": [] for s, k in SEGMENT_VARIANTS}
+    ms, count = [], dict(ground_truths=0, segments=0, candidates=0, refused=0, skipped_min_points=0, skipped_extent=0, detections=0,
+                         objects_with_a_segment=0, best_true_category={"agreement": 0, "peak": 0})
+    for i in range(args.frames):
+        fr = sampler.sample()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = segment_detections(fr.depth_mm, fr.intrinsics, nets, runner, n_pairs=args.n_pairs, seed=i, select=primary[0], score=primary[1],
+                                 nms_thresh=args.nms if args.nms is not None else 0.3, max_extent_ratio=args.max_extent_ratio,
+                                 segment_kw=dict(n_planes=args.seg_planes, min_pixels=args.seg_min_pixels, tol_mm=args.seg_tol_mm,
+                                                 slope_permille=args.seg_slope, concave={} if args.concave else None))
+        ms.append((time.perf_counter() - t0) * 1e3)
+        cands, seg = res["candidates"], res["segments"]
+        args.seg_log.append(seg["n_segments"])
+        for s, k in SEGMENT_VARIANTS:
+            pooled = res if (s, k) == primary else pool_segment_candidates(cands, cats, None, s, k, args.nms if args.nms is not None else 0.3, dev)
+            dets = pooled["detections"][:20]                                 # (the evaluation's match tables hold 20 predictions per image)
+            results[f"{s}/{k}"].append(_mask_free_record(fr, [(names.index(d["class_name"]), d["pose"], d["score"]) for d in dets]))
+        count["ground_truths"] += len(fr.categories)
+        count["segments"] += seg["n_segments"]
+        count["candidates"] += len(cands)
+        count["refused"] += len(res["refused"])
+        count["skipped_min_points"] += len(res["skipped"]["min_points"])
+        count["skipped_extent"] += len(res["skipped"]["extent"])
+        count["detections"] += len(res["detections"])
+        # the true category of a segment: the object that owns it
+        seg_lab, gt_lab = seg["labels"].cpu().numpy(), fr.labels.cpu().numpy()
+        owners = {}
+        for k_obj, cat in enumerate(fr.categories):
+            m = gt_lab == k_obj
+            inside = seg_lab[m]
+            inside = inside[inside >= 0]
+            if inside.size and np.bincount(inside).max() * 2 >= m.sum():
+                owners[int(np.bincount(inside).argmax())] = cat
+        count["objects_with_a_segment"] += len(owners)
+        for k in ("agreement", "peak"):
+            for p in cands:
+                p["score"] = float(p[k])
+            count["best_true_category"][k] += sum(owners.get(p["segment"]) == p["class_name"] for p in select_per_segment(cands, "best"))
+    return results, ms, count
+
+
 def _verified_frames(args, sampler, encs, pencs, n_frames, seed0):
     """n_frames frames of `sampler` through scene_frame(verify=True) per category (pair seed seed0 + i) -> ([(frame, [dict(poses)])],
     ms per frame).  Only the pose lists are kept: pool_detections reads nothing else."""
@@ -378,8 +445,13 @@ def main():
                     "with 3D box NMS per category at IoU threshold T (the reference's 0.3); AP with and without it from the same frames")
     ap.add_argument("--cross-category", action="store_true", help="--mask-free --nms: also a second NMS pass over the survivors of "
                     "all categories (scores of different networks are not calibrated against each other)")
-    ap.add_argument("--score", choices=("diff", "agreement"), default="diff", help="--mask-free: 'agreement' evaluates proposal "
-                    "verification (scene_frame(verify=True)): the same proposals ranked by diff, by agreement and by agreement behind the filters")
+    ap.add_argument("--score", choices=("diff", "agreement", "peak"), default="diff", help="--mask-free: 'agreement' evaluates proposal "
+                    "verification (scene_frame(verify=True)): the same proposals ranked by diff, by agreement and by agreement behind the filters; "
+                    "--segment-instances: 'agreement' (also what the default stands for there) or 'peak', segment_detections' scores")
+    ap.add_argument("--segment-instances", action="store_true", help="the frame's depth segments taken as instance masks: "
+                    "detections.segment_detections, no scene stage (DESIGN.md 3.7m); with --planes / --concave / --select / --score")
+    ap.add_argument("--select", choices=("best", "all"), default="best", help="--segment-instances: the best candidate per segment, or all")
+    ap.add_argument("--max-extent-ratio", type=float, default=None, help="--segment-instances: segment_detections' max_extent_ratio")
     ap.add_argument("--min-agreement", type=float, default=None, help="--mask-free --score agreement: the filter's bound (default: chosen "
                     "on --tune-frames separate frames)")
     ap.add_argument("--min-fill", type=float, default=None, help="--mask-free --score agreement: drop proposals whose mask fills less of "
@@ -403,21 +475,27 @@ def main():
                     "profiles/scene_detections_eval.json with --nms, profiles/scene_verify_eval.json with --score agreement)")
     args = ap.parse_args()
     args.seg_log = []
-    verify_mode = args.score == "agreement" or args.min_agreement is not None or args.min_fill is not None
+    verify_mode = not args.segment_instances and (args.score == "agreement" or args.min_agreement is not None or args.min_fill is not None)
+    if args.segment_instances and (args.mask_free or args.segments or args.refine or args.cross_category):
+        sys.exit("--segment-instances is a mode of its own: it takes --planes, --concave, --select, --score, --nms, --n-pairs and --tabletop")
+    if args.score == "peak" and not args.segment_instances:
+        sys.exit("--score peak belongs to --segment-instances")
+    if args.segment_instances and args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "segment_instances_eval.json")
     if (args.cross_category or verify_mode) and args.nms is None:
         args.nms = 0.3
     if verify_mode and not args.mask_free:
         sys.exit("--score agreement / --min-agreement / --min-fill belong to --mask-free")
     if verify_mode and args.out is None:
         args.out = os.path.join(ROOT, "profiles", "scene_verify_eval.json")
-    if args.nms is not None and not args.mask_free:
+    if args.nms is not None and not (args.mask_free or args.segment_instances):
         sys.exit("--nms / --cross-category belong to --mask-free")
     if args.refine and (not args.mask_free or args.nms is not None or verify_mode):
         sys.exit("--refine belongs to the plain --mask-free run (no --nms, no --score agreement)")
     if args.segments and (not args.mask_free or verify_mode):
         sys.exit("--segments belongs to --mask-free (plain, --nms or --refine)")
-    if args.concave and not args.segments:
-        sys.exit("--concave belongs to --segments")
+    if args.concave and not (args.segments or args.segment_instances):
+        sys.exit("--concave belongs to --segments or --segment-instances")
     if args.tabletop and verify_mode:
         sys.exit("--tabletop: the verification run tunes on a second sampler of floating objects; not wired up")
     if args.segments and args.out is None:
@@ -458,6 +536,44 @@ def main():
         sampler = MF.MeshFrameSampler(cat_paths, args.objects, device=dev, seed=args.seed)
     if verify_mode:
         _verify_eval(args, cat_paths, sampler, encs, pencs, trained, weights, dev)
+        tmp.cleanup()
+        return
+    if args.segment_instances:
+        results, ms, count = _segment_instances(args, sampler, encs, pencs, dev)
+        deg, sh = [5, 10, 15], [5, 10, 15]
+        iou = [float(t) for t in np.round(np.linspace(0, 1, 101), 2)]
+        score = "peak" if args.score == "peak" else "agreement"
+        n_fr = max(args.frames, 1)
+        rec = dict(device=torch.cuda.get_device_name(0), mode="segment instances: detections.segment_detections -- the depth segments as "
+                   "instance masks, every category's instance path on every segment, no scene stage; the same candidates pooled under "
+                   "select best / all and score agreement / peak", frames=args.frames, objects_per_frame=args.objects, n_pairs=args.n_pairs,
+                   nms_thresh=args.nms if args.nms is not None else 0.3, max_extent_ratio=args.max_extent_ratio, seed=args.seed,
+                   timed_variant=f"{args.select}/{score}", categories={c: len(p) for c, p in cat_paths.items()},
+                   procedural=bool(args.procedural), trained=trained, weights=weights, ground_truths=count["ground_truths"],
+                   ms_per_frame_median=float(np.median(ms[min(3, len(ms) - 1):])), segments_per_frame=count["segments"] / n_fr,
+                   candidates_per_frame=count["candidates"] / n_fr, refused_per_frame=count["refused"] / n_fr,
+                   skipped_min_points_per_frame=count["skipped_min_points"] / n_fr, skipped_extent_per_frame=count["skipped_extent"] / n_fr,
+                   detections_per_frame=count["detections"] / n_fr, objects_with_a_segment=count["objects_with_a_segment"],
+                   best_picked_the_true_category=count["best_true_category"],
+                   segments=dict(n_planes=args.seg_planes, min_pixels=args.seg_min_pixels, tol_mm=args.seg_tol_mm, slope_permille=args.seg_slope,
+                                 concave=bool(args.concave)),
+                   variants={}, note="figures: no threshold is attached to these APs")
+        if args.tabletop:
+            rec["tabletop"] = dict(min_gap=args.min_gap)
+        print(f"{args.frames} frames, {count['ground_truths']} ground truths, {rec['segments_per_frame']:.1f} segments, "
+              f"{rec['candidates_per_frame']:.1f} candidates and {rec['refused_per_frame']:.2f} refusals per frame; "
+              f"{rec['ms_per_frame_median']:.1f} ms per frame (median after the first 3; {rec['timed_variant']}); best picked the true category of "
+              f"{count['objects_with_a_segment']} objects with a segment: {count['best_true_category']}")
+        for v, recs in results.items():
+            iou_aps, pose_aps, _, _ = E.compute_degree_cm_mAP(recs, sampler.synset_names, None, deg, sh, iou, 0.1, True, device=dev)
+            one = dict(evaluated_predictions=int(sum(len(r["pred_class_ids"]) for r in recs)), iou_ap={}, pose_ap={})
+            print(f"--- select/score {v}: {one['evaluated_predictions']} predictions")
+            _tables(iou_aps, pose_aps, sampler.synset_names, list(cat_paths), deg, sh, one)
+            rec["variants"][v] = one
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(rec, fh, indent=1)
+            fh.write("\n")
         tmp.cleanup()
         return
     if args.mask_free and args.nms is not None:
